@@ -152,6 +152,17 @@ def parse():
     p.add_argument("--cu-candidates", default="0,32,64,96",
                    help="CU reserve candidates of the calibration (CUs left free of the decrypt grid)")
     p.add_argument("--cu-calib-steps", type=int, default=6, help="timed steps per calibration candidate")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last of them delivered (the transmux batch it "
+                        "completed: info rows, plaintext lengths, PES tables, checksums and a fixed seeded sample "
+                        "of the elementary-stream bytes; see _batch_outputs) as DIR/<name>.npy, rank 0 only.  The "
+                        "stream is synthetic with a fixed seed, so two builds run with the same arguments can be "
+                        "compared array for array")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the benchmark measures beside its headline figure in runs of their "
+                        "own.  A plain run already does only what the headline needs (set-up, warmup, the timed "
+                        "steps, the result line: its diagnostics are read from counters of those same steps), so "
+                        "today the option adds nothing; extra measurements belong behind it")
     p.add_argument("--verbose", action="store_true")
     return p.parse_args()
 
@@ -674,6 +685,16 @@ def main() -> int:
         if use_gpu:
             torch.cuda.synchronize(device)
 
+    dump = {"b": None}  # --dump-outputs: the transmux batch the last timed step completed
+    if args.dump_outputs and args.sync_steps:  # flush() hands no batch out: note each one it completes
+        complete_batch = pipe.complete
+
+        def noting_complete(b):
+            if b is not None:
+                dump["b"] = b
+            complete_batch(b)
+
+        pipe.complete = noting_complete
     calib = _calibrate(args, node, step, sync, world)  # before warmup: not in the timed window
     for _ in range(args.warmup):
         step()
@@ -687,7 +708,9 @@ def main() -> int:
     t0 = time.perf_counter()
     if _PROF is not None and not _PROF_C3:
         _PROF.enable()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if i == args.steps - 1 and args.dump_outputs and not args.sync_steps:
+            dump["b"] = state["b"]  # the batch this last step completes
         step()
     sync()
     if _PROF is not None:
@@ -722,6 +745,15 @@ def main() -> int:
               f"#   node ms {node.timer.summary_ms(args.steps)}\n"
               f"#   transmux ms {pipe.timer.summary_ms(args.steps)}", file=sys.stderr)
     _dump_profile(rank)
+    if args.dump_outputs:
+        def next_batch():
+            b = state["b"]
+            step()
+            return dump["b"] if args.sync_steps else b
+
+        if rank == 0:
+            batch = _last_batch(dump["b"], next_batch, world, args.lag + 4)
+            _write_outputs(args.dump_outputs, _batch_outputs(batch, _job_ident(batch), origin.pool_size))
     if rank == 0:
         print(json.dumps(result), flush=True)
     if world > 1:
@@ -874,7 +906,10 @@ def _fleet(args, world, rank, device, use_gpu, node, origin, players, desc, encr
             _PROF.enable()
         blocks, tb = [], t0  # soak analysis: wall ms per step over blocks of the window
         bs = max(1, args.steps // 10)
+        last, last_i = None, args.steps - 1 if args.dump_outputs else -1
         for i in range(args.steps):
+            if i == last_i:
+                last = state["b"]  # --dump-outputs: the transmux batch this last timed step completes
             step()
             if (i + 1) % bs == 0:
                 tn = time.perf_counter()
@@ -898,6 +933,8 @@ def _fleet(args, world, rank, device, use_gpu, node, origin, players, desc, encr
         # keep serving until every player has acknowledged both marks (collective rounds)
         t_end = time.perf_counter() + 120
         while True:
+            if args.dump_outputs and last is None:  # a run too short to complete a batch in its window
+                last = state["b"]
             step()
             got = server.marks.get("t1", {})
             ok = np.array([int(all(not o or w in got for w, o in enumerate(server.open)))], dtype=np.int64)
@@ -959,6 +996,15 @@ def _fleet(args, world, rank, device, use_gpu, node, origin, players, desc, encr
                   f"{[round(m0[w].get('calib_us', 0)) for w in sorted(m0)]} -> "
                   f"{[round(m1[w].get('calib_us', 0)) for w in sorted(m1)]}\n"
                   f"#   player CPU per buffered fragment (us) {_player_cpu(m0, m1)}", file=sys.stderr)
+        if args.dump_outputs:
+            def next_batch():
+                b = state["b"]
+                step()
+                return b
+
+            if rank == 0:
+                last = _last_batch(last, next_batch, world, args.lag + 4)
+                _write_outputs(args.dump_outputs, _batch_outputs(last, _fleet_ident(server, last), origin.pool_size))
         if rank == 0:
             print(json.dumps(result), flush=True)
     finally:
@@ -1211,6 +1257,123 @@ def _label_rehearsal(result: dict) -> None:
     for r in result.get("per_rank", []):  # the exchange ran over the rehearsal transport, not xGMI
         if r.get("bound") == "xgmi":
             r["bound"] = f"exchange-{dp['rccl_rehearsal']}"
+
+
+DUMP_SEED = 7  # --dump-outputs: seed of the sampled ES byte positions
+DUMP_ES_SAMPLES = 4096  # sampled bytes per fragment and class (video, audio, id3)
+DUMP_MAX_ROWS = 512  # distinct packaged segments written at most (the first in (level, pool index) order)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _last_batch(batch, next_batch, world: int, tries: int):
+    """The batch ``--dump-outputs`` writes: the one the last timed step completed, or -- when
+    the run was too short for any step of its window to complete one -- the first one of a few
+    more steps (one rank only: extra rounds are collective, and ranks may not agree on how many)."""
+    for _ in range(tries):
+        if batch is not None or world > 1:
+            break
+        batch = next_batch()
+    if batch is None:
+        raise SystemExit("bench.py: --dump-outputs: no timed step completed a transmux batch; raise --steps")
+    return batch
+
+
+def _job_ident(batch) -> np.ndarray:
+    """int64[n, 2] = (level, sn) of each fragment of an in-process player's batch."""
+    return np.array([(j.frag.level, j.frag.sn) for j in batch.jobs], dtype=np.int64).reshape(-1, 2)
+
+
+def _fleet_ident(server, batch) -> np.ndarray:
+    """int64[n, 2] = (level, sn) of each fragment of a fleet batch, from the request slots
+    the server keeps per player (the batch's tag holds the tokens)."""
+    from hlsjs_p2p_wrapper_amd.parallel import fleet as _fl
+
+    tok = np.asarray(batch.tag[0], dtype=np.int64)
+    w = tok >> _fl.TOKEN_SHIFT
+    slot = (tok & _fl._RID_MASK) % _fl._RING
+    out = np.zeros((len(tok), 2), dtype=np.int64)
+    for p in np.unique(w).tolist():
+        sel = w == p
+        out[sel] = server._skey[p][slot[sel]][:, [1, 3]]  # segment key = (swarm, level, urlId, sn)
+    return out
+
+
+def _batch_outputs(batch, ident: np.ndarray, pool_size: int) -> dict:
+    """What one completed transmux batch delivered, as float arrays in an order that does not
+    depend on which player asked first.  The stream repeats ``pool_size`` packaged segments per
+    rendition (``sn % pool_size``) with one key and IV, so a fragment's output is fixed by
+    ``(level, sn % pool_size)``: one row per distinct pair in the batch (a fragment that has a
+    result and passed its receive check; the lowest ``sn``), sorted by that pair.
+
+    * ``segment``      float64[P, 2]  (level, sn % pool_size) of each row
+    * ``info``         float64[P, I]  the demux info row, named slots of ``ops.tsdemux.INFO`` in slot order
+    * ``plain_bytes``  float64[P]     plaintext length after the decrypt (-1: bad padding)
+    * ``pes``          float64[P, 3, max_pes, 3]  (es offset, pts, dts) per class and PES; 0 past the PES count
+    * ``es_checksum``  float64[P, 3, 2]  per class, over every ES byte: sum(b[i]) and sum((i % 251 + 1) * b[i])
+    * ``es_sample``    float32[P, 3, S]  per class, the ES bytes at S fixed seeded positions (-1: class empty)
+    """
+    from hlsjs_p2p_wrapper_amd.ops import tsdemux as _ts
+    from hlsjs_p2p_wrapper_amd.player.transmux import MediaPipeline
+
+    n = batch.n or len(batch.jobs or ())
+    rows = np.zeros((n, _ts.INFO_WORDS), dtype=np.int64)
+    plain = np.full(n, -1, dtype=np.int64)
+    group = np.full(n, -1, dtype=np.int64)  # which demux group of the batch holds fragment i, and where
+    place = np.zeros(n, dtype=np.int64)
+    for g, ((idx, _res, _eo, _lens), (hinfo, hlens)) in enumerate(zip(batch.infos or (), batch.host or ())):
+        idx = np.asarray(idx, dtype=np.int64)
+        k = len(idx)
+        rows[idx] = (hinfo.numpy() if isinstance(hinfo, torch.Tensor) else np.asarray(hinfo))[:k]
+        plain[idx] = (hlens.numpy() if isinstance(hlens, torch.Tensor) else np.asarray(hlens))[:k]
+        group[idx], place[idx] = g, np.arange(k)
+    usable = (group >= 0) & MediaPipeline._verified(batch, n)
+    level, sn = ident[:, 0], ident[:, 1]
+    cid = level * pool_size + sn % pool_size
+    order = np.lexsort((np.arange(n), sn, cid))
+    order = order[usable[order]]
+    first = np.ones(len(order), dtype=bool)
+    first[1:] = cid[order][1:] != cid[order][:-1]
+    chosen = order[first][:DUMP_MAX_ROWS]
+    P, S = len(chosen), DUMP_ES_SAMPLES
+    slots = sorted(_ts.INFO.values())
+    slot_of = _ts.INFO
+    u = np.sort(np.random.default_rng(DUMP_SEED).random(S))
+    max_pes = int(batch.infos[0][1].pes.shape[2]) if P else _ts.DEFAULT_MAX_PES
+    out = {"segment": np.stack([level[chosen], sn[chosen] % pool_size], axis=1).astype(np.float64),
+           "info": rows[chosen][:, slots].astype(np.float64),
+           "plain_bytes": plain[chosen].astype(np.float64),
+           "pes": np.zeros((P, 3, max_pes, 3), dtype=np.float64),
+           "es_checksum": np.zeros((P, 3, 2), dtype=np.float64),
+           "es_sample": np.full((P, 3, S), -1.0, dtype=np.float32)}
+    for r, i in enumerate(chosen.tolist()):
+        _idx, res, es_offs, _lens = batch.infos[group[i]]
+        j, row = int(place[i]), rows[i]
+        pes = res.pes[j].cpu().numpy()
+        base, es = int(es_offs[j]), res.es
+        starts = (base, base + int(row[slot_of["audio_es_offset"]]), base + int(row[slot_of["id3_es_offset"]]))
+        sizes = (int(row[slot_of["video_bytes"]]), int(row[slot_of["audio_bytes"]]), int(row[slot_of["id3_bytes"]]))
+        counts = (int(row[slot_of["n_video_pes"]]), int(row[slot_of["n_audio_pes"]]), int(row[slot_of["n_id3_pes"]]))
+        for c in range(3):
+            k = max(0, min(counts[c], max_pes))
+            out["pes"][r, c, :k] = pes[c, :k]
+            a, m = starts[c], sizes[c]
+            if m <= 0 or a < 0 or a + m > es.numel():  # (an error row: its status bits say why)
+                continue
+            b = es[a:a + m].to(torch.int64)
+            wgt = torch.arange(m, device=b.device, dtype=torch.int64) % 251 + 1
+            out["es_checksum"][r, c] = (float(b.sum()), float((b * wgt).sum()))
+            pos = torch.from_numpy((u * m).astype(np.int64)).to(b.device)
+            out["es_sample"][r, c] = b[pos].to(torch.float32).cpu().numpy()
+    return out
+
+
+def _write_outputs(path: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes to write, over the {DUMP_MAX_BYTES} limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _mem(use_gpu, device) -> str:
