@@ -18,7 +18,7 @@ import torch
 
 from ._native import device as _dev
 from ._native import runtime as _rt
-from .desc import pack_to_device
+from .desc import check_ranges, pack_to_device
 
 _key_cache: Dict[bytes, np.ndarray] = {}
 _key_cache_le: Dict[bytes, np.ndarray] = {}
@@ -79,16 +79,16 @@ def cbc_decrypt_batch(src: torch.Tensor, src_offs: Sequence[int], nbytes: Sequen
     nb = np.asarray(nbytes, dtype=np.int64)
     if B == 0:
         return torch.empty(0, dtype=torch.int64, device=src.device)
+    so = np.asarray(src_offs, dtype=np.int64)
+    do = np.asarray(dst_offs, dtype=np.int64)
+    check_ranges("cbc_decrypt_batch", "source", so, nb, src.numel())
+    check_ranges("cbc_decrypt_batch", "destination", do, nb, dst.numel())
     if np.any(nb % 16) or np.any(nb < 16):
         raise ValueError("AES-CBC segments must be non-empty multiples of 16 bytes")
     if np.any(nb >= 1 << 31):
         raise ValueError("AES-CBC segments must be under 2 GiB (the kernel's buffer ranges)")
-    so = np.asarray(src_offs, dtype=np.int64)
-    do = np.asarray(dst_offs, dtype=np.int64)
     if np.any(so % 16) or np.any(do % 16):
         raise ValueError("segment offsets must be 16-byte aligned")
-    if np.any(so + nb > src.numel()) or np.any(do + nb > dst.numel()):
-        raise ValueError("segment range out of bounds")
     k0 = keys[0]
     if all(k is k0 or k == k0 for k in keys):  # one key per stream: expand / stack once
         drk = np.broadcast_to(round_keys(bytes(k0)).astype(np.uint32), (B, 44))

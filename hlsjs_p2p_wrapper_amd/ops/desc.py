@@ -24,6 +24,21 @@ _DT = {
 }
 
 
+def check_ranges(op: str, what: str, offs: np.ndarray, lens: np.ndarray, numel: int) -> None:
+    """Reject byte ranges ``[offs[i], offs[i] + lens[i])`` that do not lie inside a tensor of
+    ``numel`` bytes, before the op branches on the device: the device bindings trust their
+    descriptors, and ``-16 + 16 <= numel`` lets a negative offset through an upper-bound test.
+    ``what`` names the tensor (``source`` / ``destination`` / ``ES``) in the message."""
+    if offs.shape != lens.shape:
+        raise ValueError(f"{op}: {what} offsets and lengths differ in size")
+    if np.any(offs < 0):
+        raise ValueError(f"{op}: negative {what} offset")
+    if np.any(lens < 0):
+        raise ValueError(f"{op}: negative length")
+    if np.any(offs + lens > numel):
+        raise ValueError(f"{op}: {what} range out of bounds")
+
+
 def pack_to_device(arrays: Dict[str, np.ndarray], device: torch.device) -> Dict[str, torch.Tensor]:
     """Copy ``arrays`` to ``device`` in one transfer; returns typed device views.
 

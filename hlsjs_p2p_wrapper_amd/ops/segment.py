@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from ._native import device as _dev
-from .desc import pack_to_device
+from .desc import check_ranges, pack_to_device
 
 
 def pack_keys(levels, url_ids, sns, swarm: int = 0) -> np.ndarray:
@@ -41,8 +41,8 @@ def copy_segments(src: torch.Tensor, dst: torch.Tensor, src_offs: Sequence[int],
     n = np.asarray(lens, dtype=np.int64)
     if len(n) == 0:
         return
-    if np.any(so + n > src.numel()) or np.any(do + n > dst.numel()) or np.any(n < 0):
-        raise ValueError("copy_segments: out of bounds")
+    check_ranges("copy_segments", "source", so, n, src.numel())
+    check_ranges("copy_segments", "destination", do, n, dst.numel())
     if src.device.type == "cpu":
         s = src.numpy()
         d = dst.numpy()

@@ -22,7 +22,7 @@ import torch
 
 from ._native import device as _dev
 from ._native import runtime as _rt
-from .desc import pack_to_device
+from .desc import check_ranges, pack_to_device
 
 PACKET = 188
 CLASSES = ("video", "audio", "id3")
@@ -71,8 +71,8 @@ def demux_batch(buf: torch.Tensor, offs: Sequence[int], lens: Union[Sequence[int
         cap = np.asarray(caps, dtype=np.int64)
     else:
         cap = np.asarray(lens, dtype=np.int64)
-    if np.any(o + cap > buf.numel()) or np.any(eo + cap > es.numel()):
-        raise ValueError("demux_batch: range out of bounds")
+    check_ranges("demux_batch", "source", o, cap, buf.numel())
+    check_ranges("demux_batch", "ES", eo, cap, es.numel())
     dev = buf.device
     if dev.type == "cpu":
         n = lens.numpy().astype(np.int64) if isinstance(lens, torch.Tensor) else cap
