@@ -176,7 +176,7 @@ ACCEL_MODULES = [
     "models/segment_view.py", "models/track_view.py",
     "player/hls.py", "player/config.py", "utils/trace.py", "integration/player_interface.py",
     "models/media_map.py", "parallel/comm.py", "parallel/fleet.py", "ops/desc.py", "ops/aes.py", "ops/tsdemux.py",
-    "ops/crc.py", "ops/segment.py",
+    "ops/crc.py", "ops/segment.py", "ops/esindex.py",
 ]
 ACCEL_MANIFEST = "_accel.json"
 

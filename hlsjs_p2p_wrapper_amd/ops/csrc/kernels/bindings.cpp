@@ -23,6 +23,10 @@ hipError_t launch_crc32_batch(const uint8_t*, const int64_t*, const int64_t*, co
 hipError_t launch_ts_demux(const uint8_t*, const int64_t*, const int64_t*, const int64_t*, int, int64_t, uint32_t*,
                            int64_t*, int32_t*, uint8_t*, const int64_t*, int64_t*, int64_t, int64_t*, hipStream_t,
                            const void*, const int64_t*);
+int es_index_tile_bytes();
+hipError_t launch_es_index(const uint8_t*, int64_t, const int64_t*, const int64_t*, const int64_t*, int, int64_t,
+                           const int64_t*, const int64_t*, int64_t, int64_t, int32_t*, int32_t*, int32_t*, int32_t*,
+                           int64_t*, hipStream_t);
 hipError_t launch_segment_copy(const uint8_t*, uint8_t*, const int64_t*, const int64_t*, const int64_t*,
                                const int64_t*, int, int64_t, hipStream_t);
 }  // namespace dev
@@ -162,6 +166,33 @@ void ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int
      "ts_demux");
 }
 
+// Sample index of a demuxed batch (es_index.hip): es / info / pes are ts_demux's outputs, cap the
+// host upper bound of each segment's ES bytes (the Python wrapper has checked es_off + cap
+// against es), tile_prefix the exclusive prefix of ceil(cap / es_index_tile_bytes()).
+void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
+              int64_t max_pes, int64_t max_nal, Tensor scratch, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_nal > 0 && total_tiles >= 0, "es_index: max_pes / max_nal / total_tiles out of range");
+  check(es, "es", torch::kUInt8);
+  check(es_off, "es_off", torch::kInt64);
+  check(cap, "cap", torch::kInt64, B);
+  check(tile_prefix, "tile_prefix", torch::kInt64, B + 1);
+  check(info, "info", torch::kInt64, B * 24);
+  check(pes, "pes", torch::kInt64, B * 3 * max_pes * 3);
+  check(scratch, "scratch", torch::kInt32, 2 * total_tiles + B * (max_nal + 1));  // counts | prefixes | positions
+  check(nal, "nal", torch::kInt32, B * max_nal * 4);
+  check(au, "au", torch::kInt32, B * max_pes * 4);
+  check(aframes, "aframes", torch::kInt32, B * max_pes * 2);
+  check(sinfo, "sinfo", torch::kInt64, B * 8);
+  same_device(es, sinfo);
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0, "es must be 16-byte aligned");
+  ok(D::launch_es_index(cptr<uint8_t>(es), es.numel(), cptr<int64_t>(es_off), cptr<int64_t>(cap),
+                        cptr<int64_t>(tile_prefix), static_cast<int>(B), total_tiles, cptr<int64_t>(info),
+                        cptr<int64_t>(pes), max_pes, max_nal, mptr<int32_t>(scratch), mptr<int32_t>(nal),
+                        mptr<int32_t>(au), mptr<int32_t>(aframes), mptr<int64_t>(sinfo), stream()),
+     "es_index");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -289,6 +320,9 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int total_blocks, "
         "Tensor(a!) meta, Tensor(b!) pts_dts, Tensor(c!) blk_sums, Tensor(d!) es, Tensor es_off, Tensor(e!) pes, "
         "int max_pes, Tensor(f!) info) -> ()");
+  m.def("es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
+        "int max_pes, int max_nal, Tensor(a!) scratch, Tensor(b!) nal, Tensor(c!) au, Tensor(d!) aframes, "
+        "Tensor(e!) sinfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -297,6 +331,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("aes128_cbc_decrypt", &aes128_cbc_decrypt);
   m.impl("crc32_batch", &crc32_batch);
   m.impl("ts_demux", &ts_demux);
+  m.impl("es_index", &es_index);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -314,6 +349,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("expect"), py::arg("ok_out"), py::arg("total_tiles"), py::arg("scatter_idx") = py::none(),
         py::arg("scatter_out") = py::none());
   m.def("ts_demux", &ts_demux);
+  m.def("es_index", &es_index);
+  m.def("es_index_tile_bytes", &D::es_index_tile_bytes);
   m.def("segment_copy", &segment_copy);
   m.def("device_cus", &device_cus);
   m.def("h2d_batch", &h2d_batch, pybind11::arg("dst"), pybind11::arg("dst_off"), pybind11::arg("src_ptr"),

@@ -1,0 +1,398 @@
+// Sample index of demuxed segments (docs/ESINDEX.md) — CDNA4 / gfx950.
+//
+// Input: what ts_demux.hip leaves in HBM (ES bytes, PES tables, info rows).  Output per
+// segment, identical to the host implementation runtime/es.cpp index_segment:
+//   nal:     int32[seg][max_nal][4] = (offset, length, type, access unit)   (-1 rows beyond)
+//   au:      int32[seg][max_pes][4] = (first NAL, NAL count, flags, size)    (-1 rows beyond)
+//   aframes: int32[seg][max_pes][2] = (ADTS frames, bytes consumed) per audio PES
+//   sinfo:   int64[seg][8]
+//
+// Four launches on the caller's stream, no host round trip (the video ES lengths come from
+// the demux's info rows; host caps size the tile space and bound every access):
+//   1. es_count_kernel  — one workgroup per 16 KiB tile of one segment's video ES: every lane
+//                         tests the 16 start-code positions of its 16 bytes in registers
+//                         (SWAR zero / one byte flags over the 16-byte load plus one dword of
+//                         look-ahead); counts reduce in the wave, then through LDS.
+//   2. es_prefix_kernel — one wave per segment: exclusive tile prefixes, n_nal, status.
+//   3. es_emit_kernel   — the count's grid: recomputes the matches and writes the start-code
+//                         position of rank tile prefix + earlier iterations + earlier waves +
+//                         earlier lanes + bit order, for ranks <= max_nal (the NAL after the
+//                         last recorded one ends it).
+//   4. es_finish_kernel — one workgroup per segment: a lane per recorded NAL (length, type,
+//                         access unit by binary search of the PES offsets), a lane per access
+//                         unit (NAL range, flags), then wave 0 counts the keyframe units and
+//                         walks the ADTS frames with a lane per audio PES.
+// No workgroup waits for another one: the order comes from the launches alone.
+#include "common.h"
+
+namespace hlsp2p {
+namespace dev {
+
+constexpr int kEsThreads = 256;
+constexpr int kEsIters = 4;
+constexpr int kEsIterBytes = kEsThreads * 16;
+constexpr int kEsTile = kEsIters * kEsIterBytes;  // 16 KiB
+constexpr int kEsInfo = 24;                       // demux info row (runtime/ts.hpp)
+constexpr int kEsVideoBytes = 6, kEsAudioBytes = 7, kEsVideoPes = 9, kEsAudioPes = 10, kEsVideoType = 12,
+              kEsAudioType = 13, kEsAudioOffset = 22;
+constexpr int kSinfo = 8;  // status, n_nal, n_au, n_keyframe_aus, first_keyframe_au, n_adts_frames, rate, channels
+constexpr int64_t kNalOverflow = 1, kAdtsError = 2, kUnsupportedVideo = 4;
+constexpr int kAuKey = 1, kAuSps = 2, kAuPps = 4, kAuAud = 8;
+
+int es_index_tile_bytes() { return kEsTile; }
+
+__device__ __forceinline__ int64_t es_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+__device__ __forceinline__ bool es_video_supported(const int64_t* __restrict__ inf) {
+  return inf[kEsVideoType] == 0x1B || inf[kEsVideoType] == 0x24;
+}
+
+// bytes of video ES to index: 0 for an unsupported codec, never beyond the host cap
+__device__ __forceinline__ int64_t es_video_len(const int64_t* __restrict__ inf, int64_t cap) {
+  return es_video_supported(inf) ? es_clamp(inf[kEsVideoBytes], 0, cap) : 0;
+}
+
+// inclusive prefix sum over the wave64 in DPP moves (row_shr:1/2/4/8, row_bcast:15/31)
+__device__ __forceinline__ uint32_t es_wave_scan(uint32_t v) {
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x143, 0xc, 0xf, false));
+  return v;
+}
+
+// 0x80 in every byte of x that is zero (exact: no carry leaves a byte)
+__device__ __forceinline__ uint32_t es_zero_bytes(uint32_t x) {
+  return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+}
+
+// Bit j set: a start code begins at byte b + j of the video ES (00 00 01 with the NAL header
+// byte inside the n bytes).  The ES is read through a buffer resource that ends with the ES
+// tensor, so a load can never leave it; bytes at or past n (audio, slack) may take part in
+// the flags, and the limit below drops every position whose header byte is not inside.
+__device__ __forceinline__ uint32_t es_match16(__amdgpu_buffer_rsrc_t rsrc, int b, int n) {
+  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+  const int lim = n - 3 - b;  // positions j < lim have b + j + 3 < n
+  if (lim <= 0) return 0;
+  const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, b, 0, 0);
+  const uint32_t w4 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, b + 16, 0, 0);
+  const uint32_t w[5] = {v.x, v.y, v.z, v.w, w4};
+  uint32_t z[5], o[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    z[k] = es_zero_bytes(w[k]);
+    o[k] = es_zero_bytes(w[k] ^ 0x01010101u);
+  }
+  uint32_t mask = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t m = z[k] & __builtin_amdgcn_alignbyte(z[k + 1], z[k], 1) & __builtin_amdgcn_alignbyte(o[k + 1], o[k], 2);
+    mask |= ((((m >> 7) & 0x01010101u) * 0x01020408u) >> 24) << (4 * k);  // byte flags -> 4 bits
+  }
+  return lim >= 16 ? mask : mask & ((1u << lim) - 1u);
+}
+
+struct EsTile {
+  int seg;
+  int n;     // video ES bytes to index
+  int base;  // first byte of the tile
+  __amdgpu_buffer_rsrc_t rsrc;
+};
+
+__device__ __forceinline__ EsTile es_tile(const uint8_t* __restrict__ es, int64_t es_numel,
+                                          const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
+                                          const int64_t* __restrict__ tile_prefix, int nseg,
+                                          const int64_t* __restrict__ info) {
+  EsTile t;
+  const int64_t gt = blockIdx.x;
+  t.seg = find_seg_wave(tile_prefix, nseg, gt);
+  t.base = static_cast<int>(gt - tile_prefix[t.seg]) * kEsTile;
+  t.n = static_cast<int>(es_video_len(info + static_cast<int64_t>(t.seg) * kEsInfo, cap[t.seg]));
+  const int64_t off = es_off[t.seg];
+  const int64_t avail = es_numel - off;
+  t.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(es + off), 0,
+                                             static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+  return t;
+}
+
+// ---------------------------------------------------------------- 1. count
+__global__ __launch_bounds__(kEsThreads) void es_count_kernel(
+    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
+    const int64_t* __restrict__ cap, const int64_t* __restrict__ tile_prefix, int nseg,
+    const int64_t* __restrict__ info, int32_t* __restrict__ tile_cnt) {
+  __shared__ uint32_t s_cnt[kEsThreads / 64];
+  const EsTile t = es_tile(es, es_numel, es_off, cap, tile_prefix, nseg, info);
+  const int tid = threadIdx.x;
+  uint32_t c = 0;
+  if (t.base < t.n) {
+#pragma unroll
+    for (int it = 0; it < kEsIters; ++it) c += __popc(es_match16(t.rsrc, t.base + it * kEsIterBytes + tid * 16, t.n));
+  }
+  const uint32_t inc = es_wave_scan(c);
+  if ((tid & 63) == 63) s_cnt[tid >> 6] = inc;
+  __syncthreads();
+  if (tid == 0) tile_cnt[blockIdx.x] = static_cast<int32_t>(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
+}
+
+// ---------------------------------------------------------------- 2. prefix
+__global__ __launch_bounds__(64) void es_prefix_kernel(const int64_t* __restrict__ tile_prefix,
+                                                       const int32_t* __restrict__ tile_cnt,
+                                                       int32_t* __restrict__ tile_pre, const int64_t* __restrict__ info,
+                                                       int64_t max_nal, int64_t* __restrict__ sinfo) {
+  const int seg = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int64_t t0 = tile_prefix[seg];
+  const int64_t nt = tile_prefix[seg + 1] - t0;
+  uint32_t carry = 0;
+  for (int64_t tb = 0; tb < nt; tb += 64) {
+    const int64_t t = tb + lane;
+    const uint32_t v = t < nt ? static_cast<uint32_t>(tile_cnt[t0 + t]) : 0u;
+    const uint32_t inc = es_wave_scan(v);
+    if (t < nt) tile_pre[t0 + t] = static_cast<int32_t>(carry + inc - v);
+    carry += static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(inc), 63));
+  }
+  if (lane == 0) {  // carry is wave-uniform
+    int64_t* si = sinfo + static_cast<int64_t>(seg) * kSinfo;
+    int64_t status = es_video_supported(info + static_cast<int64_t>(seg) * kEsInfo) ? 0 : kUnsupportedVideo;
+    if (static_cast<int64_t>(carry) > max_nal) status |= kNalOverflow;
+    si[0] = status;
+    si[1] = carry;
+  }
+}
+
+// ---------------------------------------------------------------- 3. emit
+__global__ __launch_bounds__(kEsThreads) void es_emit_kernel(
+    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
+    const int64_t* __restrict__ cap, const int64_t* __restrict__ tile_prefix, int nseg,
+    const int64_t* __restrict__ info, const int32_t* __restrict__ tile_pre, int64_t max_nal,
+    int32_t* __restrict__ pos) {
+  __shared__ uint32_t s_w[kEsIters][kEsThreads / 64];
+  const EsTile t = es_tile(es, es_numel, es_off, cap, tile_prefix, nseg, info);
+  if (t.base >= t.n) return;  // block-uniform
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint32_t m[kEsIters], inc[kEsIters];
+#pragma unroll
+  for (int it = 0; it < kEsIters; ++it) m[it] = es_match16(t.rsrc, t.base + it * kEsIterBytes + tid * 16, t.n);
+#pragma unroll
+  for (int it = 0; it < kEsIters; ++it) {
+    inc[it] = es_wave_scan(__popc(m[it]));
+    if (lane == 63) s_w[it][wave] = inc[it];
+  }
+  __syncthreads();
+  int32_t* out = pos + static_cast<int64_t>(t.seg) * (max_nal + 1);
+  int64_t before = tile_pre[blockIdx.x];  // start codes of earlier tiles, iterations and waves
+#pragma unroll
+  for (int it = 0; it < kEsIters; ++it) {
+    int64_t r = before + inc[it] - __popc(m[it]);
+    for (int w = 0; w < kEsThreads / 64; ++w) {
+      if (w < wave) r += s_w[it][w];
+      before += s_w[it][w];
+    }
+    const int b = t.base + it * kEsIterBytes + tid * 16;
+    for (uint32_t mm = m[it]; mm != 0 && r <= max_nal; mm &= mm - 1, ++r) out[r] = b + __ffs(mm) - 1;
+  }
+}
+
+// ---------------------------------------------------------------- 4. finish
+// first k in [0, cnt) with pos[k] + 3 >= x (NAL starts ascend), cnt if none
+__device__ __forceinline__ int es_first_nal_at(const int32_t* __restrict__ pos, int cnt, int64_t x) {
+  int lo = 0, hi = cnt;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (static_cast<int64_t>(pos[mid]) + 3 >= x) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+__device__ __forceinline__ int es_adts_rate(int idx) {
+  switch (idx) {
+    case 0: return 96000; case 1: return 88200; case 2: return 64000; case 3: return 48000;
+    case 4: return 44100; case 5: return 32000; case 6: return 24000; case 7: return 22050;
+    case 8: return 16000; case 9: return 12000; case 10: return 11025; case 11: return 8000;
+    case 12: return 7350; default: return 0;
+  }
+}
+
+__global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
+    const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
+    const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
+    const int32_t* __restrict__ pos_all, int32_t* __restrict__ nal_all, int32_t* __restrict__ au_all,
+    int32_t* __restrict__ af_all, int64_t* __restrict__ sinfo) {
+  const int seg = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int64_t* inf = info + static_cast<int64_t>(seg) * kEsInfo;
+  int64_t* si = sinfo + static_cast<int64_t>(seg) * kSinfo;
+  const int64_t room = cap[seg];
+  const uint8_t* V = es + es_off[seg];
+  const int64_t n = es_video_len(inf, room);
+  const int64_t n_nal = si[1];
+  const int nn = static_cast<int>(n_nal < max_nal ? n_nal : max_nal);
+  const bool hevc = inf[kEsVideoType] == 0x24;
+  const int m = es_video_supported(inf) ? static_cast<int>(es_clamp(inf[kEsVideoPes], 0, max_pes)) : 0;
+  const int64_t* vp = pes + static_cast<int64_t>(seg) * 3 * max_pes * 3;  // class 0
+  const int64_t* ap = vp + max_pes * 3;                                      // class 1
+  const int32_t* pos = pos_all + static_cast<int64_t>(seg) * (max_nal + 1);
+  int32_t* nal = nal_all + static_cast<int64_t>(seg) * max_nal * 4;
+  int32_t* au = au_all + static_cast<int64_t>(seg) * max_pes * 4;
+  int32_t* af = af_all + static_cast<int64_t>(seg) * max_pes * 2;
+
+  // ---- a lane per NAL row
+  for (int64_t k = tid; k < max_nal; k += kEsThreads) {
+    int32_t r0 = -1, r1 = -1, r2 = -1, r3 = -1;
+    if (k < nn) {
+      const int64_t s = static_cast<int64_t>(pos[k]) + 3;
+      int64_t e = n;
+      if (k + 1 < n_nal) {  // rank k + 1 <= max_nal is recorded
+        const int64_t p1 = pos[k + 1];
+        const int64_t z1 = (p1 > 0 && V[p1 - 1] == 0) ? 1 : 0;
+        e = p1 - z1 > s ? p1 - z1 : s;
+      }
+      const int hb = V[s];
+      int a_lo = 0, a_hi = m;  // AU: largest a < m with offset <= s, else -1
+      while (a_lo < a_hi) {
+        const int mid = (a_lo + a_hi) >> 1;
+        if (vp[3 * mid] <= s) a_lo = mid + 1; else a_hi = mid;
+      }
+      r0 = static_cast<int32_t>(s);
+      r1 = static_cast<int32_t>(e - s);
+      r2 = e == s ? -1 : hevc ? (hb >> 1) & 0x3f : hb & 0x1f;
+      r3 = a_lo - 1;
+    }
+    nal[4 * k] = r0;
+    nal[4 * k + 1] = r1;
+    nal[4 * k + 2] = r2;
+    nal[4 * k + 3] = r3;
+  }
+  __syncthreads();  // NAL rows of this segment are visible to the whole workgroup
+
+  // ---- a lane per access unit row
+  for (int64_t a = tid; a < max_pes; a += kEsThreads) {
+    int32_t r0 = -1, r1 = -1, r2 = -1, r3 = -1;
+    if (a < m) {
+      const int64_t o = vp[3 * a];
+      const int64_t o_next = a + 1 < m ? vp[3 * (a + 1)] : n;
+      const int first = es_first_nal_at(pos, nn, o);
+      const int end = a + 1 < m ? es_first_nal_at(pos, nn, o_next) : nn;
+      int flags = 0;
+      for (int k = first; k < end; ++k) {
+        const int ty = nal[4 * k + 2];
+        if (hevc) {
+          flags |= (ty >= 16 && ty <= 21 ? kAuKey : 0) | (ty == 33 ? kAuSps : 0) | (ty == 34 ? kAuPps : 0) |
+                   (ty == 35 ? kAuAud : 0);
+        } else {
+          flags |= (ty == 5 ? kAuKey : 0) | (ty == 7 ? kAuSps : 0) | (ty == 8 ? kAuPps : 0) | (ty == 9 ? kAuAud : 0);
+        }
+      }
+      r1 = end > first ? end - first : 0;
+      r0 = r1 > 0 ? first : -1;
+      r2 = flags;
+      r3 = static_cast<int32_t>(o_next - o);
+    }
+    au[4 * a] = r0;
+    au[4 * a + 1] = r1;
+    au[4 * a + 2] = r2;
+    au[4 * a + 3] = r3;
+  }
+  __syncthreads();
+  if (tid >= 64) return;
+
+  // ---- wave 0: keyframe units, then the ADTS walk (a lane per audio PES)
+  const int lane = tid;
+  int n_key = 0, first_key = 0x7fffffff;
+  for (int a = lane; a < m; a += 64) {
+    if (au[4 * a + 2] & kAuKey) {
+      ++n_key;
+      if (a < first_key) first_key = a;
+    }
+  }
+  const bool adts = inf[kEsAudioType] == 0x0F;
+  const int64_t a_off = es_clamp(inf[kEsAudioOffset], 0, room);
+  const int64_t a_len = es_clamp(inf[kEsAudioBytes], 0, room - a_off);
+  const uint8_t* A = V + a_off;
+  const int ma = adts ? static_cast<int>(es_clamp(inf[kEsAudioPes], 0, max_pes)) : 0;
+  int n_frames = 0, err = 0, rate = 0, chans = 0;
+  for (int64_t k = lane; k < max_pes; k += 64) {
+    int32_t frames = -1, used = -1;
+    if (k < ma) {
+      const int64_t start = es_clamp(ap[3 * k], 0, a_len);
+      const int64_t end = k + 1 < ma ? es_clamp(ap[3 * (k + 1)], start, a_len) : a_len;
+      int64_t q = start;
+      frames = 0;
+      while (q != end) {
+        if (q + 7 > end || A[q] != 0xFF || (A[q + 1] & 0xF6) != 0xF0) {
+          err = 1;
+          break;
+        }
+        const int64_t len = (static_cast<int64_t>(A[q + 3] & 3) << 11) | (static_cast<int64_t>(A[q + 4]) << 3) |
+                            (A[q + 5] >> 5);
+        const int hdr = (A[q + 1] & 1) ? 7 : 9;
+        if (len < hdr || q + len > end) {
+          err = 1;
+          break;
+        }
+        if (k == 0 && frames == 0) {
+          rate = es_adts_rate((A[q + 2] >> 2) & 15);
+          chans = ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6);
+        }
+        ++frames;
+        q += len;
+      }
+      used = static_cast<int32_t>(q - start);
+      n_frames += frames;
+    }
+    af[2 * k] = frames;
+    af[2 * k + 1] = used;
+  }
+  n_key = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(es_wave_scan(n_key)), 63));
+  n_frames = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(es_wave_scan(n_frames)), 63));
+  const bool any_err = __ballot(err != 0) != 0;
+  for (int d = 32; d > 0; d >>= 1) {
+    const int other = __shfl_xor(first_key, d);
+    first_key = other < first_key ? other : first_key;
+  }
+  if (lane == 0) {  // rate / chans: lane 0 walked audio PES 0
+    si[0] |= any_err ? kAdtsError : 0;
+    si[2] = m;
+    si[3] = n_key;
+    si[4] = n_key > 0 ? first_key : -1;
+    si[5] = n_frames;
+    si[6] = rate;
+    si[7] = chans;
+  }
+}
+
+// scratch (int32): [tile_cnt: total_tiles | tile_pre: total_tiles | pos: nseg x (max_nal + 1)]
+hipError_t launch_es_index(const uint8_t* es, int64_t es_numel, const int64_t* es_off, const int64_t* cap,
+                           const int64_t* tile_prefix, int nseg, int64_t total_tiles, const int64_t* info,
+                           const int64_t* pes, int64_t max_pes, int64_t max_nal, int32_t* scratch, int32_t* nal,
+                           int32_t* au, int32_t* aframes, int64_t* sinfo, hipStream_t stream) {
+  if (nseg <= 0) return hipSuccess;
+  int32_t* tile_cnt = scratch;
+  int32_t* tile_pre = tile_cnt + total_tiles;
+  int32_t* pos = tile_pre + total_tiles;
+  hipError_t e = hipSuccess;
+  if (total_tiles > 0) {
+    hipLaunchKernelGGL(es_count_kernel, dim3(static_cast<unsigned>(total_tiles)), dim3(kEsThreads), 0, stream, es,
+                       es_numel, es_off, cap, tile_prefix, nseg, info, tile_cnt);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(es_prefix_kernel, dim3(nseg), dim3(64), 0, stream, tile_prefix, tile_cnt, tile_pre, info, max_nal,
+                     sinfo);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  if (total_tiles > 0) {
+    hipLaunchKernelGGL(es_emit_kernel, dim3(static_cast<unsigned>(total_tiles)), dim3(kEsThreads), 0, stream, es,
+                       es_numel, es_off, cap, tile_prefix, nseg, info, tile_pre, max_nal, pos);
+    e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(es_finish_kernel, dim3(nseg), dim3(kEsThreads), 0, stream, es, es_off, cap, info, pes, max_pes,
+                     max_nal, pos, nal, au, aframes, sinfo);
+  return hipGetLastError();
+}
+
+}  // namespace dev
+}  // namespace hlsp2p

@@ -19,6 +19,7 @@
 
 #include "aes_host.hpp"
 #include "crc_host.hpp"
+#include "es.hpp"
 #include "locator.hpp"
 #include "planner.hpp"
 #include "shm_control.hpp"
@@ -301,6 +302,40 @@ PYBIND11_MODULE(_runtime, m) {
   m.def("mpeg_crc32", [](Arr<uint8_t> data) { return ts::mpeg_crc32(data.data(), static_cast<size_t>(data.size())); });
   m.attr("TS_INFO_WORDS") = ts::kInfoWords;
   m.attr("TS_CLASSES") = ts::kClasses;
+  // Batched CPU sample index with the device kernels' layout (docs/ESINDEX.md).
+  //   es: flat uint8 (segment b's ES at es_off[b], cap[b] bytes readable); info / pes: demux_batch's
+  //   nal: int32[B, max_nal, 4]; au: int32[B, max_pes, 4]; aframes: int32[B, max_pes, 2]; sinfo: int64[B, 8]
+  m.def("index_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
+                          int64_t max_pes, int64_t max_nal, py::array nal, py::array au, py::array aframes,
+                          py::array sinfo) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("index_batch: max_pes and max_nal must be positive");
+    int32_t* np = mut_ptr<int32_t>(nal, "nal");
+    int32_t* up = mut_ptr<int32_t>(au, "au");
+    int32_t* fp = mut_ptr<int32_t>(aframes, "aframes");
+    int64_t* sp = mut_ptr<int64_t>(sinfo, "sinfo");
+    if (cap.size() != B || info.size() < B * ts::kInfoWords || pes.size() < B * ts::kClasses * max_pes * 3 ||
+        nal.size() < B * max_nal * 4 || au.size() < B * max_pes * 4 || aframes.size() < B * max_pes * 2 ||
+        sinfo.size() < B * es::kSinfoWords)
+      throw std::invalid_argument("index_batch: an argument is too small");
+    const int64_t* eo = es_off.data();
+    const int64_t* c = cap.data();
+    int64_t total = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (eo[b] < 0 || c[b] < 0 || eo[b] + c[b] > es.size()) throw std::invalid_argument("index_batch: ES out of bounds");
+      total += c[b];
+    }
+    const uint8_t* e = es.data();
+    const int64_t* ip = info.data();
+    const int64_t* pp = pes.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      es::index_segment(e + eo[b], c[b], ip + b * ts::kInfoWords, pp + b * ts::kClasses * max_pes * 3, max_pes, max_nal,
+                        np + b * max_nal * 4, up + b * max_pes * 4, fp + b * max_pes * 2, sp + b * es::kSinfoWords);
+    }, total);
+  });
+  m.attr("ES_SINFO_WORDS") = es::kSinfoWords;
+  m.attr("ES_DEFAULT_MAX_NAL") = es::kDefaultMaxNal;
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

@@ -91,6 +91,9 @@ def _default_config() -> Dict[str, Any]:
         "tickInterval": 100,
         # keep demuxed ES tensors referenced by the media element (False: account only)
         "retainMediaData": False,
+        # index NAL units, access units and ADTS frames of every fragment on the transmux
+        # device (docs/ESINDEX.md): FRAG_PARSING_DATA gains "samples", FRAG_PARSED "independent"
+        "indexSamples": False,
     }
 
 

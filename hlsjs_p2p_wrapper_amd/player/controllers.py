@@ -768,7 +768,8 @@ class StreamController:
         # transmux batch verifies it on the way through the decrypt
         ticket = getattr(payload, "swarm_verify", None)
         pipeline_for(dev, self.loop).submit(
-            TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket))
+            TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
+                        bool(self.hls.config.get("indexSamples"))))
 
     def _on_parsed(self, frag: Fragment, stats: Any, r: Any) -> None:  # r: dict-like transmux result
         hls = self.hls
@@ -822,14 +823,24 @@ class StreamController:
             dur = frag.duration
         start = frag.start
         end = start + dur
+        # indexSamples: the fragment's sample index (ops/esindex.py) rides on the parsing events; a
+        # result without one (a fleet player's: the columnar path does not index) leaves them as is
+        samples = r.get("samples") if hls.config.get("indexSamples") else None
         if listening(Events.FRAG_PARSING_DATA):
-            hls.trigger(Events.FRAG_PARSING_DATA, {"frag": frag, "type": "video", "startPTS": start, "endPTS": end,
-                                                   "data1": r["video"], "nb": nv, "pts": (vfirst, vlast)})
-            hls.trigger(Events.FRAG_PARSING_DATA, {"frag": frag, "type": "audio", "startPTS": start, "endPTS": end,
-                                                   "data1": r["audio"], "nb": info["n_audio_pes"],
-                                                   "pts": (info["audio_first_pts"], info["audio_last_pts"])})
+            vdata = {"frag": frag, "type": "video", "startPTS": start, "endPTS": end,
+                     "data1": r["video"], "nb": nv, "pts": (vfirst, vlast)}
+            adata = {"frag": frag, "type": "audio", "startPTS": start, "endPTS": end,
+                     "data1": r["audio"], "nb": info["n_audio_pes"],
+                     "pts": (info["audio_first_pts"], info["audio_last_pts"])}
+            if samples is not None:
+                vdata["samples"] = adata["samples"] = samples
+            hls.trigger(Events.FRAG_PARSING_DATA, vdata)
+            hls.trigger(Events.FRAG_PARSING_DATA, adata)
         if listening(Events.FRAG_PARSED):
-            hls.trigger(Events.FRAG_PARSED, {"frag": frag})
+            pdata = {"frag": frag}
+            if samples is not None:
+                pdata["independent"] = samples["independent"]
+            hls.trigger(Events.FRAG_PARSED, pdata)
         media = hls.media
         vb, ab = info.get("video_bytes"), info.get("audio_bytes")  # the ES views stay unbuilt
         nbytes = int(vb + ab) if vb is not None and ab is not None else int(r["video"].numel() + r["audio"].numel())

@@ -37,10 +37,11 @@ class TransmuxJob:
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
     code inside the compiled module."""
 
-    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify")
+    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
-                 callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None) -> None:
+                 callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
+                 index: bool = False) -> None:
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -50,6 +51,9 @@ class TransmuxJob:
         # a received segment's pending CRC check (agent/node.py VerifyTicket: ``expect``,
         # ``report(ok)``): the batch verifies the bytes -- fused into the decrypt -- reports the
         # outcome, and a fragment that fails gets a ``verify_failed`` error result
+        self.index = index
+        # True: the batch also indexes this fragment's NAL units, access units and ADTS frames
+        # (ops/esindex.py) and its result gains ``samples``
 
     def __repr__(self) -> str:
         return f"TransmuxJob(key={'set' if self.key else None}, frag={self.frag!r})"
@@ -222,6 +226,7 @@ class MediaPipeline:
         t2 = time.perf_counter()
         tm.add("decrypt_launch", t2 - t1)
         infos = []
+        index = []
         for idx, buf, offs, lens, caps in groups:
             es_offs, pos = [], 0
             for c in caps:
@@ -230,6 +235,7 @@ class MediaPipeline:
             es = torch.empty(pos + ALIGN, dtype=torch.uint8, device=dev)
             res = _ts.demux_batch(buf, offs, lens, es, es_offs, caps=caps)
             infos.append((idx, res, es_offs, lens))
+            index.append(self._index(jobs, idx, res, caps))
         # async D2H of the small per-segment info rows (+ plaintext lengths) into pinned
         # host memory, then one event: completing the batch is the stage's only sync
         host = []
@@ -250,7 +256,22 @@ class MediaPipeline:
             ev = self._event()
         tm.add("demux_launch", time.perf_counter() - t2)
         return _Batch(jobs, infos=infos, host=host, event=ev, results=results, verify=host_verify,
-                      expect_mask=_mask(len(jobs), vjobs))
+                      expect_mask=_mask(len(jobs), vjobs), index=index if any(index) else None)
+
+    def _index(self, jobs, idx, res: "_ts.DemuxResult", caps):
+        """The sample index of one demuxed group when any of its jobs asked for it: one
+        ``index_batch`` call on the group's stream, its ``sinfo`` rows on their way to pinned
+        host memory before the batch's event.  Returns ``(EsIndex, host sinfo)`` or None."""
+        if not any(jobs[i].index for i in idx):
+            return None
+        from ..ops import esindex as _esx
+
+        ix = _esx.index_batch(res, caps)
+        if ix.sinfo.device.type == "cpu":
+            return ix, ix.sinfo.numpy()
+        hs = torch.empty(ix.sinfo.shape, dtype=torch.int64, pin_memory=True)
+        hs.copy_(ix.sinfo, non_blocking=True)
+        return ix, hs
 
     def _launch_native(self, jobs, src, src_offs, sizes, enc, clear, results, t1, vjobs=()) -> "_Batch":
         """GPU batch in ONE native call (``kernels/transmux.cpp``): descriptor math, one
@@ -306,16 +327,21 @@ class MediaPipeline:
         groups, dec, host_block, fused = _native_device().transmux_launch(src, offs, nb, flags, drk, iv, td0, isb,
                                                                           _ts.DEFAULT_MAX_PES, ex, cw, ctab)
         infos, host = [], []
+        want_index = any(j.index for j in jobs)
+        index = []
         for gidx, info, pes, es, es_offs, hinfo, hlens in groups:
             batch_idx = [idx[k] for k in gidx.tolist()]
-            infos.append((batch_idx, _ts.DemuxResult(info, pes, es, es_offs), es_offs, hlens))
+            res = _ts.DemuxResult(info, pes, es, es_offs)
+            infos.append((batch_idx, res, es_offs, hlens))
             host.append((hinfo, hlens))
+            if want_index:  # after the group's demux, on the same stream
+                index.append(self._index(jobs, batch_idx, res, [sizes[i] for i in batch_idx]))
         if fused is not None:  # rows of the launch -> job indices
             verify.append((np.asarray(idx, dtype=np.int64)[fused[0]], fused[1]))
         ev = self._event()
         tm.add("demux_launch", time.perf_counter() - t2)
         return _Batch(jobs, infos=infos, host=host, event=ev, results=results, keep=(dec, host_block), start=ev0,
-                      verify=verify or None, expect_mask=mask)
+                      verify=verify or None, expect_mask=mask, index=index if any(index) else None)
 
     # ------------------------------------------------------------------ columnar batch
     def launch_columns(self, src: torch.Tensor, offs: np.ndarray, nbytes: np.ndarray, enc: np.ndarray,
@@ -492,7 +518,7 @@ class MediaPipeline:
         t4 = time.perf_counter()
         tm.add("wait_device", t4 - t3)
         results = b.results
-        for (idx, res, es_offs, lens), (hinfo, hlens) in zip(b.infos, b.host):
+        for g, ((idx, res, es_offs, lens), (hinfo, hlens)) in enumerate(zip(b.infos, b.host)):
             hinfo = hinfo.numpy() if isinstance(hinfo, torch.Tensor) else hinfo
             plain_lens = hlens.numpy() if isinstance(hlens, torch.Tensor) else hlens
             rows = hinfo.tolist()
@@ -506,6 +532,13 @@ class MediaPipeline:
                 if plain_lens[k] < 0:
                     r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
                 results[i] = r
+            gi = b.index[g] if b.index is not None else None
+            if gi is not None:  # the jobs of this group that asked for the sample index
+                ix, hs = gi
+                srows = (hs.numpy() if isinstance(hs, torch.Tensor) else hs).tolist()
+                for k, i in enumerate(idx):
+                    if b.jobs[i].index:
+                        results[i]["samples"] = Samples(srows[k], ix, k)
         tm.add("results", time.perf_counter() - t4)
         return results  # type: ignore[return-value]
 
@@ -580,6 +613,60 @@ class InfoRow:
         return f"InfoRow({self.to_dict()})"
 
 
+class Samples:
+    """Read-only mapping of one fragment's sample index (``TransmuxJob.index``): the ``sinfo``
+    fields by name (:data:`ops.esindex.SINFO`), ``independent`` (access unit 0 holds a
+    keyframe), and ``nal`` / ``au`` / ``aframes``: the fragment's rows of the batch's device
+    tables, viewed on first access."""
+
+    __slots__ = ("_row", "_ix", "_k")
+    _TABLES = ("nal", "au", "aframes")
+
+    def __init__(self, row, ix, k: int) -> None:
+        self._row = row
+        self._ix = ix
+        self._k = k
+
+    def __getitem__(self, name: str):
+        from ..ops.esindex import SINFO
+
+        slot = SINFO.get(name)
+        if slot is not None:
+            return self._row[slot]
+        if name == "independent":
+            return self._row[SINFO["first_keyframe_au"]] == 0
+        if name in self._TABLES:
+            return getattr(self._ix, name)[self._k]
+        raise KeyError(name)
+
+    def get(self, name: str, default=None):
+        try:
+            return self[name]
+        except KeyError:
+            return default
+
+    def keys(self):
+        from ..ops.esindex import SINFO
+
+        return list(SINFO) + ["independent", *self._TABLES]
+
+    def items(self):
+        return ((k, self[k]) for k in self.keys())
+
+    def __contains__(self, name) -> bool:
+        return name in self.keys()
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self) -> int:
+        return len(self.keys())
+
+    def __repr__(self) -> str:
+        fields = {k: self[k] for k in self.keys() if k not in self._TABLES}
+        return f"Samples({fields})"
+
+
 @dataclass(eq=False)
 class _Batch:
     jobs: List[TransmuxJob]
@@ -594,6 +681,7 @@ class _Batch:
     start: Any = None  # timing event recorded before the batch's first launch
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
+    index: Any = None  # per group of infos: (EsIndex, host sinfo rows) or None (no job of the batch asked: None)
 
 
 _local = threading.local()

@@ -1,7 +1,7 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
-(the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather) and the MFMA
-CRC with HIP events and reports us / GB/s of input.  Checks results against the host
-oracles once.
+(the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
+index over the demuxed ES and the MFMA CRC with HIP events and reports us / GB/s of input.
+Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
 """
@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import aes, crc, segment, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import aes, crc, esindex, segment, tsdemux
 
 
 def timed(fn, iters):
@@ -58,6 +58,12 @@ def main():
     g, c = r.segment(0), cpu.segment(0)
     assert g["video_bytes"] == c["video_bytes"] and torch.equal(g["video"]["es"].cpu(), c["video"]["es"]), \
         "demux mismatch"
+    # the sample index over the ES the demux just wrote (count + prefix + emit + finish)
+    ix = esindex.index_batch(r, caps)
+    res["esindex_us"] = timed(lambda: esindex.index_batch(r, caps), args.iters)
+    hx = esindex.index_batch(cpu, [len(ref)])
+    assert all(torch.equal(getattr(ix, k)[0].cpu(), getattr(hx, k)[0]) for k in ("sinfo", "nal", "au", "aframes")), \
+        "esindex mismatch"
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
@@ -66,7 +72,7 @@ def main():
     res["copy_us"] = timed(lambda: segment.copy_segments(src, cp, offs, offs, lens), args.iters)
     assert torch.equal(cp[offs[5]:offs[5] + lens[5]], src[offs[5]:offs[5] + lens[5]]), "copy mismatch"
     res["torch_copy_us"] = timed(lambda: cp.copy_(src), args.iters)
-    for k in ("aes", "demux", "crc", "copy", "torch_copy"):
+    for k in ("aes", "demux", "esindex", "crc", "copy", "torch_copy"):
         res[f"{k}_GBps"] = round(total / (res[f"{k}_us"] * 1e-6) / 1e9, 1)
         res[f"{k}_us"] = round(res[f"{k}_us"], 1)
     res["bytes"] = total
