@@ -27,6 +27,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 RUNTIME_SRC = CSRC / "runtime"
 KERNEL_SRC = CSRC / "kernels"
+SHARED_SRC = CSRC / "shared"  # layouts and sizes both builds include (layout.hpp)
 REPO = HERE.parent.parent
 BUILD = REPO / "build" / "native"
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"
@@ -74,7 +75,7 @@ def device_path() -> Path:
 
 def build_runtime(force: bool = False, sanitize: bool = False, verbose: bool = False) -> Path:
     srcs = sorted(RUNTIME_SRC.glob("*.cpp"))
-    hdrs = sorted(RUNTIME_SRC.glob("*.hpp"))
+    hdrs = sorted(RUNTIME_SRC.glob("*.hpp")) + sorted(SHARED_SRC.glob("*.hpp"))
     # the sanitizer build keeps the module name (_runtime) in its own directory; load it
     # with asan_runtime_path() under LD_PRELOAD=libasan (tests/test_asan_runtime.py)
     out = runtime_path() if not sanitize else asan_runtime_path()
@@ -87,7 +88,7 @@ def build_runtime(force: bool = False, sanitize: bool = False, verbose: bool = F
         flags = ["-O1", "-g", "-std=c++17", "-fPIC", "-fsanitize=address,undefined", "-fno-omit-frame-pointer"]
     objdir = BUILD / ("runtime_asan" if sanitize else "runtime")
     objdir.mkdir(parents=True, exist_ok=True)
-    incs = _pybind_includes() + [f"-I{RUNTIME_SRC}"]
+    incs = _pybind_includes() + [f"-I{RUNTIME_SRC}", f"-I{SHARED_SRC}"]
 
     def compile_one(src: Path) -> Path:
         obj = objdir / (src.stem + ".o")
@@ -118,7 +119,7 @@ def build_device(force: bool = False, verbose: bool = False) -> Path:
     """Compile the HIP kernels for gfx950 and link the torch binding module ``_C``."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     kern = sorted(KERNEL_SRC.glob("*.hip"))
-    hdrs = sorted(KERNEL_SRC.glob("*.h")) + sorted(KERNEL_SRC.glob("*.hpp"))
+    hdrs = sorted(KERNEL_SRC.glob("*.h")) + sorted(KERNEL_SRC.glob("*.hpp")) + sorted(SHARED_SRC.glob("*.hpp"))
     # host-only translation units: bindings.cpp (torch ops) and rccl_comm.cpp (RCCL data plane)
     host_srcs = sorted(KERNEL_SRC.glob("*.cpp"))
     out = device_path()
@@ -127,10 +128,11 @@ def build_device(force: bool = False, verbose: bool = False) -> Path:
     objdir = BUILD / "device"
     objdir.mkdir(parents=True, exist_ok=True)
     kflags = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
-              "-D__HIP_PLATFORM_AMD__", f"-I{KERNEL_SRC}"]
+              "-D__HIP_PLATFORM_AMD__", f"-I{KERNEL_SRC}", f"-I{SHARED_SRC}"]
     torch_incs, libdirs = _torch_paths()
-    bflags = ["-O2", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM", f"-I{ROCM}/include",
-              "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", f"-I{KERNEL_SRC}",
+    # host files: C++20 for the designated initializers that fill the launch structs (kernels/launch.h)
+    bflags = ["-O2", "-std=c++20", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-DUSE_ROCM", f"-I{ROCM}/include",
+              "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H", f"-I{KERNEL_SRC}", f"-I{SHARED_SRC}",
               *torch_incs, *_pybind_includes()]
 
     def compile_kernel(src: Path) -> Path:

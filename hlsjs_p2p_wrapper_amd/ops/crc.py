@@ -132,8 +132,9 @@ def _crc32_batch_py(buf: torch.Tensor, o: np.ndarray, n: np.ndarray, expect, exp
     """The same device launch assembled in Python (kept as the reference for the native
     ``crc32_launch``; tests compare the two)."""
     B = len(o)
-    groups = (n + 255) // 256
-    tiles = (groups + 31) // 32
+    C = _dev()
+    groups = (n + C.CRC_GROUP_BYTES - 1) // C.CRC_GROUP_BYTES
+    tiles = (groups + C.CRC_TILE_GROUPS - 1) // C.CRC_TILE_GROUPS
     tile_prefix = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(tiles, out=tile_prefix[1:])
     res_off = np.zeros(B, dtype=np.int64)
@@ -150,8 +151,8 @@ def _crc32_batch_py(buf: torch.Tensor, o: np.ndarray, n: np.ndarray, expect, exp
     crc = torch.empty(B, dtype=torch.int32, device=buf.device)
     exp_t = expect_dev if expect_dev is not None else d.get("ex")
     ok = torch.empty(B, dtype=torch.uint8, device=buf.device) if exp_t is not None else None
-    _dev().crc32_batch(buf, d["o"], d["n"], d["tp"], d["ro"], w, tables, residues, crc, exp_t, ok,
-                       int(tile_prefix[-1]), d.get("si"), scatter_to)
+    C.crc32_batch(buf, d["o"], d["n"], d["tp"], d["ro"], w, tables, residues, crc, exp_t, ok,
+                  int(tile_prefix[-1]), d.get("si"), scatter_to)
     return crc, ok
 
 

@@ -32,6 +32,7 @@
 #include "common.h"
 
 #include "aes_dev.h"
+#include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -70,7 +71,9 @@ struct AesCrc {
   const v4i* wfrag;         // [8 steps][64 lanes] B fragments
   uint32_t* masks;
 };
-constexpr int kCrcSteps = 8;  // [chain parity jj][data dword d]
+constexpr int kCrcSteps = crc::kFusedAesSteps;  // [chain parity jj][data dword d]
+static_assert(kCrcSteps == 8 && crc::kFusedMaskDwords == 64 && 64 * kBlk * 16 == crc::kChunkBytes,
+              "a decrypt chunk is one CRC chunk: 64 lanes x kBlk blocks, one mask dword per lane");
 
 __device__ __forceinline__ void crc_chunk_masks(const uint4 (&c)[kBlk], const v4i (&w)[kCrcSteps], int lane,
                                                 uint32_t* __restrict__ out) {
@@ -112,6 +115,7 @@ struct AesHdr {
   uint4* rec;
 };
 constexpr uint32_t kDiv188Magic = 2924233053u;  // floor(x / 188) = umulhi(x, M) >> 7 for all 32-bit x
+static_assert(ts::kPacket == 188, "the header-record division");
 
 // tdl: little-endian Td0 (256 words); isb: inverse S-box (256 bytes)
 // drk: per-segment little-endian equivalent-inverse-cipher round keys (44 words)
@@ -228,25 +232,18 @@ void aes_grid(int64_t total_chunks, int num_cu, int64_t& grid, int64_t& per_wg) 
 }
 }  // namespace
 
-// crc_mask_off / crc_wfrag / crc_masks: the fused ciphertext CRC (nullptr: off);
-// hdr_off / hdr_rec: packet-header records for the demux scan (nullptr: off)
-hipError_t launch_aes128_cbc_decrypt(const uint8_t* src, uint8_t* dst, const int64_t* src_off, const int64_t* dst_off,
-                                     const int64_t* blk_prefix, const int64_t* chunk_prefix, const uint32_t* drk,
-                                     const uint32_t* ivw, const uint32_t* tdl, const uint8_t* isb, int64_t* out_len,
-                                     int nseg, int64_t total_chunks, int num_cu, hipStream_t stream,
-                                     const int64_t* crc_mask_off, const void* crc_wfrag, uint32_t* crc_masks,
-                                     const int64_t* hdr_off, void* hdr_rec) {
-  if (total_chunks <= 0) return hipSuccess;
+hipError_t launch_aes128_cbc_decrypt(const AesDecryptArgs& a) {
+  if (a.total_chunks <= 0) return hipSuccess;
   int64_t grid, per_wg;
-  aes_grid(total_chunks, num_cu, grid, per_wg);
-  const AesCrc crc{crc_mask_off, reinterpret_cast<const v4i*>(crc_wfrag), crc_masks};
-#define AES_LAUNCH(M, H)                                                                                          \
-  hipLaunchKernelGGL((aes128_cbc_decrypt_kernel<M, H>), dim3(static_cast<unsigned>(grid)), dim3(kAesThreads), 0,     \
-                     stream, src, dst, src_off, dst_off, blk_prefix, chunk_prefix, drk, ivw, tdl, isb, out_len, nseg, \
-                     total_chunks, per_wg, crc, hdr)
-  const AesHdr hdr{hdr_off, reinterpret_cast<uint4*>(hdr_rec)};
-  const bool with_hdr = hdr_off != nullptr && hdr_rec != nullptr;
-  if (crc_mask_off == nullptr) {
+  aes_grid(a.total_chunks, a.num_cu, grid, per_wg);
+  const AesCrc crc{a.crc.mask_off, reinterpret_cast<const v4i*>(a.crc.wfrag), a.crc.masks};
+  const AesHdr hdr{a.hdr.off, reinterpret_cast<uint4*>(a.hdr.rec)};
+#define AES_LAUNCH(M, H)                                                                                        \
+  hipLaunchKernelGGL((aes128_cbc_decrypt_kernel<M, H>), dim3(static_cast<unsigned>(grid)), dim3(kAesThreads), 0, \
+                     a.stream, a.src, a.dst, a.src_off, a.dst_off, a.blk_prefix, a.chunk_prefix, a.drk, a.iv,     \
+                     a.td0, a.isb, a.out_len, a.nseg, a.total_chunks, per_wg, crc, hdr)
+  const bool with_hdr = hdr.off != nullptr && hdr.rec != nullptr;
+  if (crc.mask_off == nullptr) {
     if (with_hdr) AES_LAUNCH(0, 1); else AES_LAUNCH(0, 0);
   } else {
     if (with_hdr) AES_LAUNCH(1, 1); else AES_LAUNCH(1, 0);

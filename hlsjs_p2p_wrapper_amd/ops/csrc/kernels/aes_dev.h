@@ -24,7 +24,6 @@ constexpr uint32_t kIsRegion = 0x20000u;
 // the per-lane table base (S1 bytes 0 and 2); bits 24..31 = 0
 #define AES_SEL(k) (0x0c020000u | ((4u + (k)) << 8))
 #define AES_LDS32(addr) (*reinterpret_cast<const uint32_t*>(s_bytes + (addr)))
-#define AES_TD(t, w, k) AES_LDS32(__builtin_amdgcn_perm((w), td_base[t], AES_SEL(k)))
 #define AES_IS(w, k) AES_LDS32(((((w) >> (8 * (k))) & 0xffu) << 7) + is_base)
 
 // CDNA4 3-input bitwise op (truth table 0x96 = a ^ b ^ c); the round key is an SGPR operand

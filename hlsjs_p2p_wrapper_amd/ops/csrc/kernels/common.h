@@ -6,34 +6,14 @@
 namespace hlsp2p {
 namespace dev {
 
-constexpr int kWave = 64;
-
-// Host-side launch status (filled by launchers, returned to the binding).
-struct LaunchStatus {
-  hipError_t err;
-};
-
-__device__ __forceinline__ uint32_t bswap32(uint32_t x) { return __builtin_bswap32(x); }
-
-__device__ __forceinline__ uint32_t rotr(uint32_t x, int s) { return (x >> s) | (x << (32 - s)); }
-
 // Monotone segment walk: first index s with prefix[s + 1] > v, starting from `s`.
 __device__ __forceinline__ int advance_seg(const int64_t* __restrict__ prefix, int s, int64_t v) {
   while (prefix[s + 1] <= v) ++s;
   return s;
 }
 
-// Binary search: largest s in [0, n) with prefix[s] <= v  (prefix has n+1 entries).
-__device__ __forceinline__ int find_seg(const int64_t* __restrict__ prefix, int n, int64_t v) {
-  int lo = 0, hi = n;  // invariant: prefix[lo] <= v < prefix[hi]
-  while (hi - lo > 1) {
-    int mid = (lo + hi) >> 1;
-    if (prefix[mid] <= v) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-// Same result as find_seg for a wave-uniform v, with all 64 lanes active: each lane tests
+// Largest s in [0, n) with prefix[s] <= v (prefix has n + 1 entries, ascending) for a
+// wave-uniform v, with all 64 lanes active: each lane tests
 // one prefix entry and a ballot counts the entries <= v, so segment lookup costs ONE
 // global round trip per 64-way level (n <= 64: one) instead of log2(n) dependent loads
 // at the head of every workgroup.
@@ -49,6 +29,20 @@ __device__ __forceinline__ int find_seg_wave(const int64_t* __restrict__ prefix,
   }
   const bool le = lane < cnt && prefix[lo + lane] <= v;
   return __builtin_amdgcn_readfirstlane(lo + __popcll(__ballot(le)) - 1);
+}
+
+// Inclusive prefix sum over the wave64 in six DPP-modified moves and adds, no LDS traffic
+// (a __shfl_up ladder is six ds_bpermute round trips): row_shr:1/2/4/8 scan each 16-lane row
+// (bound_ctrl fills 0 past the row start), row_bcast:15 adds row 0's / row 2's total to rows 1
+// and 3, row_bcast:31 adds rows 0-1's total to rows 2 and 3.
+__device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t v) {
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, true));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));
+  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x143, 0xc, 0xf, false));
+  return v;
 }
 
 // Workgroup copy of `count` elements global -> LDS with every load of the thread issued
@@ -73,9 +67,6 @@ __device__ __forceinline__ void lds_fill(T* __restrict__ dst, const T* __restric
     dst[i < last ? i : last] = v[k];
   }
 }
-
-// Host helpers
-inline int ceil_div(int64_t a, int64_t b) { return static_cast<int>((a + b - 1) / b); }
 
 }  // namespace dev
 }  // namespace hlsp2p

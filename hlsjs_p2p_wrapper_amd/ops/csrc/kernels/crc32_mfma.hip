@@ -27,7 +27,10 @@
 // operators (byte-slice tables in LDS): Horner over runs of groups, then a log tree, then
 // it undoes the zero padding of the last group (A^-8p) and adds the init/xor-out terms.
 // Result is bit-identical to zlib.crc32.
+#include <type_traits>
+
 #include "common.h"
+#include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -38,9 +41,9 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 // 8 waves share one 64 KiB LDS copy of W: 2 workgroups per CU = 4 waves per SIMD, so one
 // wave's global loads / nibble expansion overlap other waves' MFMAs.
 constexpr int kCrcThreads = 512;
-constexpr int kTileBytes = 32 * 256;
-constexpr int kNumP = 40;
-constexpr int kSlice = 1024;  // u32 per byte-slice table set
+using namespace crc;  // tile geometry, table counts (shared/layout.hpp)
+static_assert(kTileGroups == 32 && kGroupBytes == 256 && kTileBytes == 32 * 256,
+              "the residue kernels' lane map: a wave tile is 32 MFMA rows of one 256-byte group each");
 
 // 16 bytes at byte offset `o` of a segment of `len` > 0 bytes, zero beyond the end (last
 // tile).  Segment starts are 16-byte aligned, so the aligned 16-byte chunk holding a
@@ -59,13 +62,28 @@ __device__ __forceinline__ uint4 load_tail(const uint8_t* __restrict__ buf, int6
   return v;
 }
 
-__global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_kernel(
+// FP4 variant on the block-scaled f8f6f4 matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4,
+// e2m1 A and B, unit scales).  An FP4 MFMA takes the cycles of the i8 32x32x32 one but
+// covers 64 k, so a tile needs 32 MFMAs instead of 64; each consumes ONE data dword per lane
+// (vs 16 bytes masked to one bit), fed as 4 operand dwords -- bits 0/1/2/3 of every nibble:
+// d & 0x11111111 (= 0.5), d & 0x22222222 (= 1.0), d & 0x44444444 (= 2.0),
+// (d >> 1) & 0x44444444 (= 2.0) -- with B pre-scaled by the inverse on the host
+// (crc_host.cpp: mfma_group_weights_fp4), so every nonzero product is exactly 1.0 and the
+// f32 accumulator is an exact count (<= 2048): its parity is the GF(2) residue bit.
+// Step s = 4q + w uses dword w of the lane's 16-byte chunk q (same loads as the i8 path).
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+
+// The body of both residue kernels: kFp4 picks the matrix-core path and its fragment count.
+template <bool kFp4>
+__device__ __forceinline__ void group_residues(
     const uint8_t* __restrict__ buf, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
     const int64_t* __restrict__ tile_prefix, const int64_t* __restrict__ res_off, const v4i* __restrict__ wfrag,
     uint32_t* __restrict__ residues, int nseg, int64_t total_tiles, int64_t tiles_per_wave) {
-  __shared__ v4i s_w[64 * 64];  // 64 KiB: [step][lane] fragments
+  constexpr int kSteps = kFp4 ? 32 : 64;
+  __shared__ v4i s_w[kSteps * 64];  // 32 / 64 KiB: [step][lane] fragments
   const int tid = threadIdx.x;
-  lds_fill<64 * 64 / kCrcThreads>(s_w, wfrag, 64 * 64, tid, kCrcThreads);
+  lds_fill<kSteps * 64 / kCrcThreads>(s_w, wfrag, kSteps * 64, tid, kCrcThreads);
   __syncthreads();
 
   const int lane = tid & 63;
@@ -76,7 +94,7 @@ __global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_kernel(
   const int64_t t_end = t_begin + tiles_per_wave < total_tiles ? t_begin + tiles_per_wave : total_tiles;
   if (t_begin >= t_end) return;
   // Software pipeline over the wave's tiles: the lane's 128 bytes of tile t+1 (8 x dwordx4,
-  // 8 KB per wave) are in flight while tile t's 64 MFMAs run.  Without it every tile paid a
+  // 8 KB per wave) are in flight while tile t's MFMAs run.  Without it every tile paid a
   // full HBM round trip before its MFMAs (~2.5 TB/s chip-wide).
   int seg = find_seg_wave(tile_prefix, nseg, t_begin);
   int64_t base = seg_off[seg], len = seg_len[seg], tstart = tile_prefix[seg], tend = tile_prefix[seg + 1];
@@ -112,116 +130,38 @@ __global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_kernel(
       }
       load_tile(t + 1 - tstart);
     }
-    v16i acc = {};
-    // not unrolled (an unrolled q loop hoists all 64 B fragments into registers); the chunk
+    typename std::conditional<kFp4, v16f, v16i>::type acc = {};
+    // not unrolled (an unrolled q loop hoists all the B fragments into registers); the chunk
     // registers rotate instead of being indexed, so nothing goes to scratch
 #pragma unroll 1
     for (int q = 0; q < 8; ++q) {
-      // 8 MFMAs per 16-byte chunk, one per bit position jb: A = the raw bytes masked to
-      // bit jb (4 v_and), B pre-scaled by 2^(7-jb) on the host, so each nonzero product is
-      // +-128 and the GF(2) sum lands in bit 7 of the accumulator
+      if constexpr (kFp4) {
+        const uint32_t dw[4] = {c0.x, c0.y, c0.z, c0.w};
 #pragma unroll
-      for (int jb = 0; jb < 8; ++jb) {
-        const uint32_t m = 0x01010101u << jb;
-        v4i a;
-        a.x = static_cast<int>(c0.x & m);
-        a.y = static_cast<int>(c0.y & m);
-        a.z = static_cast<int>(c0.z & m);
-        a.w = static_cast<int>(c0.w & m);
-        const v4i b = s_w[(8 * q + jb) * 64 + lane];
-        acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
-      }
-      c0 = c1; c1 = c2; c2 = c3; c3 = c4; c4 = c5; c5 = c6; c6 = c7;
-    }
-    // lane `row` takes its group's residue from the 16 ballots; one masked store (see the
-    // fp4 kernel)
-    uint32_t res = 0;
+        for (int w = 0; w < 4; ++w) {
+          const uint32_t d = dw[w];
+          const v8i a = {static_cast<int>(d & 0x11111111u), static_cast<int>(d & 0x22222222u),
+                         static_cast<int>(d & 0x44444444u), static_cast<int>((d >> 1) & 0x44444444u), 0, 0, 0, 0};
+          const v4i b4 = s_w[(4 * q + w) * 64 + lane];
+          const v8i b = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
+          // cbsz = blgp = 4: e2m1 A and B; scale exponents 0 select the unscaled form
+          acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, 0, 0, 0);
+        }
+      } else {
+        // 8 MFMAs per 16-byte chunk, one per bit position jb: A = the raw bytes masked to
+        // bit jb (4 v_and), B pre-scaled by 2^(7-jb) on the host, so each nonzero product is
+        // +-128 and the GF(2) sum lands in bit 7 of the accumulator
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const uint64_t m = __ballot(acc[i] & 0x80);  // 128 x GF(2) sum: parity is bit 7
-      const int row = (i & 3) + 8 * (i >> 2);
-      res = lane == row ? static_cast<uint32_t>(m) : res;
-      res = lane == row + 4 ? static_cast<uint32_t>(m >> 32) : res;
-    }
-    const int64_t groups = (c_len + 255) >> 8;
-    const int64_t g = tile * 32 + lane;
-    if (lane < 32 && g < groups) residues[c_roff + g] = res;
-  }
-}
-
-// FP4 variant on the block-scaled f8f6f4 matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4,
-// e2m1 A and B, unit scales).  An FP4 MFMA takes the cycles of the i8 32x32x32 one but
-// covers 64 k, so a tile needs 32 MFMAs instead of 64; each consumes ONE data dword per lane
-// (vs 16 bytes masked to one bit), fed as 4 operand dwords -- bits 0/1/2/3 of every nibble:
-// d & 0x11111111 (= 0.5), d & 0x22222222 (= 1.0), d & 0x44444444 (= 2.0),
-// (d >> 1) & 0x44444444 (= 2.0) -- with B pre-scaled by the inverse on the host
-// (crc_host.cpp: mfma_group_weights_fp4), so every nonzero product is exactly 1.0 and the
-// f32 accumulator is an exact count (<= 2048): its parity is the GF(2) residue bit.
-// Step s = 4q + w uses dword w of the lane's 16-byte chunk q (same loads as the i8 path).
-typedef int v8i __attribute__((ext_vector_type(8)));
-typedef float v16f __attribute__((ext_vector_type(16)));
-
-__global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_fp4_kernel(
-    const uint8_t* __restrict__ buf, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
-    const int64_t* __restrict__ tile_prefix, const int64_t* __restrict__ res_off, const v4i* __restrict__ wfrag,
-    uint32_t* __restrict__ residues, int nseg, int64_t total_tiles, int64_t tiles_per_wave) {
-  __shared__ v4i s_w[32 * 64];  // 32 KiB: [step][lane] fragments
-  const int tid = threadIdx.x;
-  lds_fill<32 * 64 / kCrcThreads>(s_w, wfrag, 32 * 64, tid, kCrcThreads);
-  __syncthreads();
-
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t gwave = static_cast<int64_t>(blockIdx.x) * (kCrcThreads / 64) + wave;
-  const int64_t t_begin = gwave * tiles_per_wave;
-  const int64_t t_end = t_begin + tiles_per_wave < total_tiles ? t_begin + tiles_per_wave : total_tiles;
-  if (t_begin >= t_end) return;
-  int seg = find_seg_wave(tile_prefix, nseg, t_begin);
-  int64_t base = seg_off[seg], len = seg_len[seg], tstart = tile_prefix[seg], tend = tile_prefix[seg + 1];
-  int64_t roff = res_off[seg];
-  uint4 n0, n1, n2, n3, n4, n5, n6, n7;  // the next tile's chunks
-  auto load_tile = [&](int64_t tile) {
-    const int64_t my = tile * kTileBytes + r * 256 + h * 16;
-    if ((tile + 1) * kTileBytes <= len) {
-      const uint4* p = reinterpret_cast<const uint4*>(buf + base + my);
-      n0 = p[0]; n1 = p[2]; n2 = p[4]; n3 = p[6]; n4 = p[8]; n5 = p[10]; n6 = p[12]; n7 = p[14];
-    } else {
-      n0 = load_tail(buf, base, my, len);        n1 = load_tail(buf, base, my + 32, len);
-      n2 = load_tail(buf, base, my + 64, len);   n3 = load_tail(buf, base, my + 96, len);
-      n4 = load_tail(buf, base, my + 128, len);  n5 = load_tail(buf, base, my + 160, len);
-      n6 = load_tail(buf, base, my + 192, len);  n7 = load_tail(buf, base, my + 224, len);
-    }
-  };
-  load_tile(t_begin - tstart);
-  for (int64_t t = t_begin; t < t_end; ++t) {
-    uint4 c0 = n0, c1 = n1, c2 = n2, c3 = n3, c4 = n4, c5 = n5, c6 = n6, c7 = n7;
-    const int64_t tile = t - tstart;
-    const int64_t c_len = len, c_roff = roff;
-    if (t + 1 < t_end) {
-      if (t + 1 >= tend) {
-        seg = advance_seg(tile_prefix, seg, t + 1);
-        base = seg_off[seg];
-        len = seg_len[seg];
-        tstart = tile_prefix[seg];
-        tend = tile_prefix[seg + 1];
-        roff = res_off[seg];
-      }
-      load_tile(t + 1 - tstart);
-    }
-    v16f acc = {};
-#pragma unroll 1
-    for (int q = 0; q < 8; ++q) {
-      const uint32_t dw[4] = {c0.x, c0.y, c0.z, c0.w};
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const uint32_t d = dw[w];
-        const v8i a = {static_cast<int>(d & 0x11111111u), static_cast<int>(d & 0x22222222u),
-                       static_cast<int>(d & 0x44444444u), static_cast<int>((d >> 1) & 0x44444444u), 0, 0, 0, 0};
-        const v4i b4 = s_w[(4 * q + w) * 64 + lane];
-        const v8i b = {b4.x, b4.y, b4.z, b4.w, 0, 0, 0, 0};
-        // cbsz = blgp = 4: e2m1 A and B; scale exponents 0 select the unscaled form
-        acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, 4, 4, 0, 0, 0, 0);
+        for (int jb = 0; jb < 8; ++jb) {
+          const uint32_t m = 0x01010101u << jb;
+          v4i a;
+          a.x = static_cast<int>(c0.x & m);
+          a.y = static_cast<int>(c0.y & m);
+          a.z = static_cast<int>(c0.z & m);
+          a.w = static_cast<int>(c0.w & m);
+          const v4i b = s_w[(8 * q + jb) * 64 + lane];
+          acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(a, b, acc, 0, 0, 0);
+        }
       }
       c0 = c1; c1 = c2; c2 = c3; c3 = c4; c4 = c5; c5 = c6; c6 = c7;
     }
@@ -231,7 +171,8 @@ __global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_fp4_kernel(
     uint32_t res = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const uint64_t m = __ballot(static_cast<int>(acc[i]) & 1);  // exact count: parity = GF(2) sum
+      // fp4: an exact count, parity = GF(2) sum; i8: 128 x the GF(2) sum, parity is bit 7
+      const uint64_t m = kFp4 ? __ballot(static_cast<int>(acc[i]) & 1) : __ballot(static_cast<int>(acc[i]) & 0x80);
       const int row = (i & 3) + 8 * (i >> 2);
       res = lane == row ? static_cast<uint32_t>(m) : res;
       res = lane == row + 4 ? static_cast<uint32_t>(m >> 32) : res;
@@ -242,13 +183,26 @@ __global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_fp4_kernel(
   }
 }
 
+__global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_kernel(
+    const uint8_t* __restrict__ buf, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
+    const int64_t* __restrict__ tile_prefix, const int64_t* __restrict__ res_off, const v4i* __restrict__ wfrag,
+    uint32_t* __restrict__ residues, int nseg, int64_t total_tiles, int64_t tiles_per_wave) {
+  group_residues<false>(buf, seg_off, seg_len, tile_prefix, res_off, wfrag, residues, nseg, total_tiles, tiles_per_wave);
+}
+
+__global__ __launch_bounds__(kCrcThreads) void crc32_group_residue_fp4_kernel(
+    const uint8_t* __restrict__ buf, const int64_t* __restrict__ seg_off, const int64_t* __restrict__ seg_len,
+    const int64_t* __restrict__ tile_prefix, const int64_t* __restrict__ res_off, const v4i* __restrict__ wfrag,
+    uint32_t* __restrict__ residues, int nseg, int64_t total_tiles, int64_t tiles_per_wave) {
+  group_residues<true>(buf, seg_off, seg_len, tile_prefix, res_off, wfrag, residues, nseg, total_tiles, tiles_per_wave);
+}
+
 __device__ __forceinline__ uint32_t apply_tab(const uint32_t* __restrict__ t, uint32_t v) {
   return t[v & 0xff] ^ t[256 + ((v >> 8) & 0xff)] ^ t[512 + ((v >> 16) & 0xff)] ^ t[768 + (v >> 24)];
 }
 
 constexpr int kCombineThreads = 1024;
 constexpr int kCombineLdsTables = 15;  // P_8 .. P_22
-constexpr int kNumQ = 12;              // Q_b = A^(-8 * 2^b): pad removal (pad < 4096 bytes)
 // Residue of the group [FF FF FF FF 00 .. 00]: for n >= 4 the zlib init value 0xFFFFFFFF
 // equals XOR-ing FF into the message's first 4 bytes, so it folds into group 0's residue
 // (= zlib(FF^4 0^(G-4)) ^ zlib(0^G)) instead of a 20-step chain of dependent global table
@@ -274,7 +228,7 @@ __device__ __forceinline__ uint32_t key_digest(const int64_t* __restrict__ k) {
   return uint32_t(z ^ (z >> 32));
 }
 
-// One workgroup per segment.  tables: P_0..P_39 then Q_0..Q_11 (each kSlice u32).  Group
+// One workgroup per segment.  tables: P_0..P_39 then Q_0..Q_11 (each kSliceWords u32).  Group
 // residues of 2^kLg bytes: 256-byte groups (the residue kernels above) or 4096-byte chunks
 // (the CRC fused into the decrypt, folded by crc32_fold_combine_kernel).
 template <int kLg>
@@ -291,12 +245,12 @@ __device__ __forceinline__ void combine_segment(
   while ((static_cast<int64_t>(kCombineThreads) << lgL) < G) ++lgL;
   const int need = kLg - 8 + 1 + lgL + 10;  // P_8 .. P_(kLg + lgL + 10) from LDS
   const int lds_tables = need <= kCombineLdsTables ? need : kCombineLdsTables;
-  lds_fill<kCombineLdsTables * kSlice / 4 / kCombineThreads + 1>(
-      reinterpret_cast<uint4*>(s_tab), reinterpret_cast<const uint4*>(tables + 8 * kSlice), lds_tables * kSlice / 4,
+  lds_fill<kCombineLdsTables * kSliceWords / 4 / kCombineThreads + 1>(
+      reinterpret_cast<uint4*>(s_tab), reinterpret_cast<const uint4*>(tables + 8 * kSliceWords), lds_tables * kSliceWords / 4,
       tid, kCombineThreads);
-  lds_fill<kLg * kSlice / 4 / kCombineThreads>(reinterpret_cast<uint4*>(s_q),
-                                                reinterpret_cast<const uint4*>(tables + kNumP * kSlice),
-                                                kLg * kSlice / 4, tid, kCombineThreads);
+  lds_fill<kLg * kSliceWords / 4 / kCombineThreads>(reinterpret_cast<uint4*>(s_q),
+                                                reinterpret_cast<const uint4*>(tables + kNumP * kSliceWords),
+                                                kLg * kSliceWords / 4, tid, kCombineThreads);
   __syncthreads();
   const int64_t L = int64_t(1) << lgL;
   const int64_t span = L * kCombineThreads;
@@ -304,7 +258,7 @@ __device__ __forceinline__ void combine_segment(
   const uint32_t* __restrict__ res = residues + res_off[seg];
   const uint32_t fold0 = n >= 4 ? (kLg == 8 ? kInitFold256 : kInitFold4096) : 0u;
   uint32_t acc = 0;
-  const uint32_t* pg = s_tab + (kLg - 8) * kSlice;  // A^(8 * 2^kLg): one group
+  const uint32_t* pg = s_tab + (kLg - 8) * kSliceWords;  // A^(8 * 2^kLg): one group
   // Horner over this thread's run of L groups, 8 residues loaded ahead per step (a
   // load-per-iteration loop paid one global round trip per group: L of them in series)
   constexpr int kAhead = 8;
@@ -330,7 +284,7 @@ __device__ __forceinline__ void combine_segment(
     const int stride = 1 << m;
     const int b = kLg + lgL + m;  // shift of 2^b bytes
     if ((tid & (2 * stride - 1)) == 0) {
-      const uint32_t* tab = (b - 8) < lds_tables ? s_tab + (b - 8) * kSlice : tables + static_cast<int64_t>(b) * kSlice;
+      const uint32_t* tab = (b - 8) < lds_tables ? s_tab + (b - 8) * kSliceWords : tables + static_cast<int64_t>(b) * kSliceWords;
       s_acc[tid] = apply_tab(tab, s_acc[tid]) ^ s_acc[tid + stride];
     }
     __syncthreads();
@@ -339,12 +293,12 @@ __device__ __forceinline__ void combine_segment(
     uint32_t raw = s_acc[0];
     const int64_t pad = (G << kLg) - n;
     for (int b = 0; b < kLg; ++b)
-      if ((pad >> b) & 1) raw = apply_tab(s_q + b * kSlice, raw);
+      if ((pad >> b) & 1) raw = apply_tab(s_q + b * kSliceWords, raw);
     uint32_t init = 0;  // folded into group 0 (n >= 4)
     if (n < 4) {
       init = 0xFFFFFFFFu;
       for (int b = 0; b < 2; ++b)
-        if ((n >> b) & 1) init = apply_tab(tables + static_cast<int64_t>(b) * kSlice, init);
+        if ((n >> b) & 1) init = apply_tab(tables + static_cast<int64_t>(b) * kSliceWords, init);
     }
     const uint32_t crc = raw ^ init ^ 0xFFFFFFFFu;
     crc_out[seg] = crc;
@@ -367,8 +321,8 @@ __global__ __launch_bounds__(kCombineThreads) void crc32_combine_kernel(
     const uint32_t* __restrict__ tables, uint32_t* __restrict__ crc_out, const uint32_t* __restrict__ expect,
     uint8_t* __restrict__ ok_out, const int64_t* __restrict__ scatter_idx, uint32_t* __restrict__ scatter_out,
     int64_t scatter_n, const int64_t* __restrict__ keys) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_tab[kCombineLdsTables * kSlice];  // 60 KiB
-  __shared__ __attribute__((aligned(16))) uint32_t s_q[kLg * kSlice];                  // 32 / 48 KiB
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[kCombineLdsTables * kSliceWords];  // 60 KiB
+  __shared__ __attribute__((aligned(16))) uint32_t s_q[kLg * kSliceWords];                  // 32 / 48 KiB
   __shared__ uint32_t s_acc[kCombineThreads];
   combine_segment<kLg>(blockIdx.x, threadIdx.x, s_tab, s_q, s_acc, residues, res_off, seg_len, tables, crc_out, expect,
                        ok_out, scatter_idx, scatter_out, scatter_n, keys);
@@ -384,8 +338,10 @@ __global__ __launch_bounds__(kCombineThreads) void crc32_combine_kernel(
 // bits of chunk l & 31 (rows (i & 3) + 8 (i >> 2) + 4 (l >> 5)); one cross-half swap completes
 // the word.  (Round 4's first fold transposed one-level masks with 16 ballots per chunk and a
 // 5-level table tree: 45-50 us per 256-segment batch.)
-constexpr int kFoldSteps = 32;
-constexpr int kMaskDwords = 64;  // per chunk
+constexpr int kFoldSteps = crc::kFusedFoldSteps;
+constexpr int kMaskDwords = crc::kFusedMaskDwords;  // per chunk
+static_assert(kMaskDwords == 2 * kFoldSteps && crc::kChunkBytes == 1 << 12 && kNumQ == 12,
+              "fold: k half hh of step s reads mask dword s + 32 hh; 4096-byte chunks combine with kLg = 12");
 // One 32-chunk tile of the fold: chunks [cbase, cbase + 32) below cend, one wave.
 __device__ __forceinline__ void fold_tile(const uint32_t* __restrict__ masks, const v4i* __restrict__ s_w,
                                           uint32_t* __restrict__ chunk_res, int64_t cbase, int64_t cend, int lane) {
@@ -434,8 +390,8 @@ __global__ __launch_bounds__(kCombineThreads) void crc32_fold_combine_kernel(
     uint32_t* __restrict__ crc_out, const uint32_t* __restrict__ expect, uint8_t* __restrict__ ok_out,
     const int64_t* __restrict__ scatter_idx, uint32_t* __restrict__ scatter_out, int64_t scatter_n) {
   __shared__ v4i s_w[kFoldSteps * 64];                                                  // 32 KiB
-  __shared__ __attribute__((aligned(16))) uint32_t s_tab[kCombineLdsTables * kSlice];  // 60 KiB
-  __shared__ __attribute__((aligned(16))) uint32_t s_q[12 * kSlice];                   // 48 KiB
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[kCombineLdsTables * kSliceWords];  // 60 KiB
+  __shared__ __attribute__((aligned(16))) uint32_t s_q[12 * kSliceWords];                   // 48 KiB
   __shared__ uint32_t s_acc[kCombineThreads];
   const int seg = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   lds_fill<kFoldSteps * 64 / kCombineThreads>(s_w, wfold, kFoldSteps * 64, tid, kCombineThreads);
@@ -449,48 +405,37 @@ __global__ __launch_bounds__(kCombineThreads) void crc32_fold_combine_kernel(
                       scatter_idx, scatter_out, scatter_n, nullptr);
 }
 
-// masks: 64 dwords per 4096-byte chunk for each segment, the segment's chunks starting at
-// dword 64 * chunk_off[seg]; wfold: the fold's A fragments; chunk_res: scratch of total_chunks
-// words.  Same outputs as launch_crc32_batch.
-hipError_t launch_crc32_from_masks(const uint32_t* masks, const void* wfold, const int64_t* chunk_off,
-                                   const int64_t* seg_len, const uint32_t* tables, uint32_t* chunk_res,
-                                   uint32_t* crc_out, const uint32_t* expect, uint8_t* ok_out,
-                                   const int64_t* scatter_idx, uint32_t* scatter_out, int64_t scatter_n, int nseg,
-                                   int64_t /*total_chunks*/, int /*num_cu*/, hipStream_t stream) {
-  if (nseg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(crc32_fold_combine_kernel, dim3(static_cast<unsigned>(nseg)), dim3(kCombineThreads), 0, stream,
-                     masks, reinterpret_cast<const v4i*>(wfold), chunk_off, seg_len, tables, chunk_res, crc_out, expect,
-                     ok_out, scatter_idx, scatter_out, scatter_n);
+hipError_t launch_crc32_from_masks(const Crc32FromMasksArgs& a) {
+  if (a.nseg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(crc32_fold_combine_kernel, dim3(static_cast<unsigned>(a.nseg)), dim3(kCombineThreads), 0, a.stream,
+                     a.masks, reinterpret_cast<const v4i*>(a.wfold), a.chunk_off, a.seg_len, a.tables, a.chunk_res,
+                     a.out.crc_out, a.out.expect, a.out.ok_out, a.out.scatter_idx, a.out.scatter_out, a.out.scatter_n);
   return hipGetLastError();
 }
 
-hipError_t launch_crc32_batch(const uint8_t* buf, const int64_t* seg_off, const int64_t* seg_len,
-                              const int64_t* tile_prefix, const int64_t* res_off, const void* wfrag,
-                              const uint32_t* tables, uint32_t* residues, uint32_t* crc_out, const uint32_t* expect,
-                              uint8_t* ok_out, const int64_t* scatter_idx, uint32_t* scatter_out, int64_t scatter_n,
-                              int nseg, int64_t total_tiles, int num_cu, bool fp4, hipStream_t stream,
-                              const int64_t* keys) {
-  if (nseg <= 0) return hipSuccess;
-  if (total_tiles > 0) {
-    const int64_t waves_max = static_cast<int64_t>(num_cu) * 2 * (kCrcThreads / 64);
-    int64_t tiles_per_wave = (total_tiles + waves_max - 1) / waves_max;
+hipError_t launch_crc32_batch(const Crc32BatchArgs& a) {
+  if (a.nseg <= 0) return hipSuccess;
+  if (a.total_tiles > 0) {
+    const int64_t waves_max = static_cast<int64_t>(a.num_cu) * 2 * (kCrcThreads / 64);
+    int64_t tiles_per_wave = (a.total_tiles + waves_max - 1) / waves_max;
     if (tiles_per_wave < 1) tiles_per_wave = 1;
-    const int64_t waves = (total_tiles + tiles_per_wave - 1) / tiles_per_wave;
+    const int64_t waves = (a.total_tiles + tiles_per_wave - 1) / tiles_per_wave;
     const int64_t grid = (waves + (kCrcThreads / 64) - 1) / (kCrcThreads / 64);
-    if (fp4)
+    const v4i* w = reinterpret_cast<const v4i*>(a.wfrag);
+    if (a.fp4)
       hipLaunchKernelGGL(crc32_group_residue_fp4_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcThreads), 0,
-                         stream, buf, seg_off, seg_len, tile_prefix, res_off, reinterpret_cast<const v4i*>(wfrag),
-                         residues, nseg, total_tiles, tiles_per_wave);
+                         a.stream, a.buf, a.seg_off, a.seg_len, a.tile_prefix, a.res_off, w, a.residues, a.nseg,
+                         a.total_tiles, tiles_per_wave);
     else
-      hipLaunchKernelGGL(crc32_group_residue_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcThreads), 0, stream,
-                         buf, seg_off, seg_len, tile_prefix, res_off, reinterpret_cast<const v4i*>(wfrag), residues,
-                         nseg, total_tiles, tiles_per_wave);
+      hipLaunchKernelGGL(crc32_group_residue_kernel, dim3(static_cast<unsigned>(grid)), dim3(kCrcThreads), 0, a.stream,
+                         a.buf, a.seg_off, a.seg_len, a.tile_prefix, a.res_off, w, a.residues, a.nseg, a.total_tiles,
+                         tiles_per_wave);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(crc32_combine_kernel<8>, dim3(static_cast<unsigned>(nseg)), dim3(kCombineThreads), 0, stream,
-                     residues, res_off, seg_len, tables, crc_out, expect, ok_out, scatter_idx, scatter_out, scatter_n,
-                     keys);
+  hipLaunchKernelGGL(crc32_combine_kernel<8>, dim3(static_cast<unsigned>(a.nseg)), dim3(kCombineThreads), 0, a.stream,
+                     a.residues, a.res_off, a.seg_len, a.tables, a.out.crc_out, a.out.expect, a.out.ok_out,
+                     a.out.scatter_idx, a.out.scatter_out, a.out.scatter_n, a.keys);
   return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 //                         walks the ADTS frames with a lane per audio PES.
 // No workgroup waits for another one: the order comes from the launches alone.
 #include "common.h"
+#include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -32,35 +33,17 @@ constexpr int kEsThreads = 256;
 constexpr int kEsIters = 4;
 constexpr int kEsIterBytes = kEsThreads * 16;
 constexpr int kEsTile = kEsIters * kEsIterBytes;  // 16 KiB
-constexpr int kEsInfo = 24;                       // demux info row (runtime/ts.hpp)
-constexpr int kEsVideoBytes = 6, kEsAudioBytes = 7, kEsVideoPes = 9, kEsAudioPes = 10, kEsVideoType = 12,
-              kEsAudioType = 13, kEsAudioOffset = 22;
-constexpr int kSinfo = 8;  // status, n_nal, n_au, n_keyframe_aus, first_keyframe_au, n_adts_frames, rate, channels
-constexpr int64_t kNalOverflow = 1, kAdtsError = 2, kUnsupportedVideo = 4;
-constexpr int kAuKey = 1, kAuSps = 2, kAuPps = 4, kAuAud = 8;
-
 int es_index_tile_bytes() { return kEsTile; }
 
 __device__ __forceinline__ int64_t es_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
 
 __device__ __forceinline__ bool es_video_supported(const int64_t* __restrict__ inf) {
-  return inf[kEsVideoType] == 0x1B || inf[kEsVideoType] == 0x24;
+  return inf[ts::kVideoType] == 0x1B || inf[ts::kVideoType] == 0x24;
 }
 
 // bytes of video ES to index: 0 for an unsupported codec, never beyond the host cap
 __device__ __forceinline__ int64_t es_video_len(const int64_t* __restrict__ inf, int64_t cap) {
-  return es_video_supported(inf) ? es_clamp(inf[kEsVideoBytes], 0, cap) : 0;
-}
-
-// inclusive prefix sum over the wave64 in DPP moves (row_shr:1/2/4/8, row_bcast:15/31)
-__device__ __forceinline__ uint32_t es_wave_scan(uint32_t v) {
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x143, 0xc, 0xf, false));
-  return v;
+  return es_video_supported(inf) ? es_clamp(inf[ts::kVideoBytes], 0, cap) : 0;
 }
 
 // 0x80 in every byte of x that is zero (exact: no carry leaves a byte)
@@ -109,7 +92,7 @@ __device__ __forceinline__ EsTile es_tile(const uint8_t* __restrict__ es, int64_
   const int64_t gt = blockIdx.x;
   t.seg = find_seg_wave(tile_prefix, nseg, gt);
   t.base = static_cast<int>(gt - tile_prefix[t.seg]) * kEsTile;
-  t.n = static_cast<int>(es_video_len(info + static_cast<int64_t>(t.seg) * kEsInfo, cap[t.seg]));
+  t.n = static_cast<int>(es_video_len(info + static_cast<int64_t>(t.seg) * ts::kInfoWords, cap[t.seg]));
   const int64_t off = es_off[t.seg];
   const int64_t avail = es_numel - off;
   t.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(es + off), 0,
@@ -130,7 +113,7 @@ __global__ __launch_bounds__(kEsThreads) void es_count_kernel(
 #pragma unroll
     for (int it = 0; it < kEsIters; ++it) c += __popc(es_match16(t.rsrc, t.base + it * kEsIterBytes + tid * 16, t.n));
   }
-  const uint32_t inc = es_wave_scan(c);
+  const uint32_t inc = wave_scan_dpp(c);
   if ((tid & 63) == 63) s_cnt[tid >> 6] = inc;
   __syncthreads();
   if (tid == 0) tile_cnt[blockIdx.x] = static_cast<int32_t>(s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3]);
@@ -149,14 +132,15 @@ __global__ __launch_bounds__(64) void es_prefix_kernel(const int64_t* __restrict
   for (int64_t tb = 0; tb < nt; tb += 64) {
     const int64_t t = tb + lane;
     const uint32_t v = t < nt ? static_cast<uint32_t>(tile_cnt[t0 + t]) : 0u;
-    const uint32_t inc = es_wave_scan(v);
+    const uint32_t inc = wave_scan_dpp(v);
     if (t < nt) tile_pre[t0 + t] = static_cast<int32_t>(carry + inc - v);
     carry += static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(inc), 63));
   }
   if (lane == 0) {  // carry is wave-uniform
-    int64_t* si = sinfo + static_cast<int64_t>(seg) * kSinfo;
-    int64_t status = es_video_supported(info + static_cast<int64_t>(seg) * kEsInfo) ? 0 : kUnsupportedVideo;
-    if (static_cast<int64_t>(carry) > max_nal) status |= kNalOverflow;
+    int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
+    const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
+    int64_t status = es_video_supported(inf) ? 0 : es::kUnsupportedVideo;
+    if (static_cast<int64_t>(carry) > max_nal) status |= es::kNalOverflow;
     si[0] = status;
     si[1] = carry;
   }
@@ -177,7 +161,7 @@ __global__ __launch_bounds__(kEsThreads) void es_emit_kernel(
   for (int it = 0; it < kEsIters; ++it) m[it] = es_match16(t.rsrc, t.base + it * kEsIterBytes + tid * 16, t.n);
 #pragma unroll
   for (int it = 0; it < kEsIters; ++it) {
-    inc[it] = es_wave_scan(__popc(m[it]));
+    inc[it] = wave_scan_dpp(__popc(m[it]));
     if (lane == 63) s_w[it][wave] = inc[it];
   }
   __syncthreads();
@@ -222,15 +206,15 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
     int32_t* __restrict__ af_all, int64_t* __restrict__ sinfo) {
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
-  const int64_t* inf = info + static_cast<int64_t>(seg) * kEsInfo;
-  int64_t* si = sinfo + static_cast<int64_t>(seg) * kSinfo;
+  const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
+  int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
   const int64_t room = cap[seg];
   const uint8_t* V = es + es_off[seg];
   const int64_t n = es_video_len(inf, room);
   const int64_t n_nal = si[1];
   const int nn = static_cast<int>(n_nal < max_nal ? n_nal : max_nal);
-  const bool hevc = inf[kEsVideoType] == 0x24;
-  const int m = es_video_supported(inf) ? static_cast<int>(es_clamp(inf[kEsVideoPes], 0, max_pes)) : 0;
+  const bool hevc = inf[ts::kVideoType] == 0x24;
+  const int m = es_video_supported(inf) ? static_cast<int>(es_clamp(inf[ts::kNumVideoPes], 0, max_pes)) : 0;
   const int64_t* vp = pes + static_cast<int64_t>(seg) * 3 * max_pes * 3;  // class 0
   const int64_t* ap = vp + max_pes * 3;                                      // class 1
   const int32_t* pos = pos_all + static_cast<int64_t>(seg) * (max_nal + 1);
@@ -279,10 +263,11 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
       for (int k = first; k < end; ++k) {
         const int ty = nal[4 * k + 2];
         if (hevc) {
-          flags |= (ty >= 16 && ty <= 21 ? kAuKey : 0) | (ty == 33 ? kAuSps : 0) | (ty == 34 ? kAuPps : 0) |
-                   (ty == 35 ? kAuAud : 0);
+          flags |= (ty >= 16 && ty <= 21 ? es::kAuKeyframe : 0) | (ty == 33 ? es::kAuSps : 0) |
+                   (ty == 34 ? es::kAuPps : 0) | (ty == 35 ? es::kAuAud : 0);
         } else {
-          flags |= (ty == 5 ? kAuKey : 0) | (ty == 7 ? kAuSps : 0) | (ty == 8 ? kAuPps : 0) | (ty == 9 ? kAuAud : 0);
+          flags |= (ty == 5 ? es::kAuKeyframe : 0) | (ty == 7 ? es::kAuSps : 0) | (ty == 8 ? es::kAuPps : 0) |
+                   (ty == 9 ? es::kAuAud : 0);
         }
       }
       r1 = end > first ? end - first : 0;
@@ -302,16 +287,16 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   const int lane = tid;
   int n_key = 0, first_key = 0x7fffffff;
   for (int a = lane; a < m; a += 64) {
-    if (au[4 * a + 2] & kAuKey) {
+    if (au[4 * a + 2] & es::kAuKeyframe) {
       ++n_key;
       if (a < first_key) first_key = a;
     }
   }
-  const bool adts = inf[kEsAudioType] == 0x0F;
-  const int64_t a_off = es_clamp(inf[kEsAudioOffset], 0, room);
-  const int64_t a_len = es_clamp(inf[kEsAudioBytes], 0, room - a_off);
+  const bool adts = inf[ts::kAudioType] == 0x0F;
+  const int64_t a_off = es_clamp(inf[ts::kAudioEsOffset], 0, room);
+  const int64_t a_len = es_clamp(inf[ts::kAudioBytes], 0, room - a_off);
   const uint8_t* A = V + a_off;
-  const int ma = adts ? static_cast<int>(es_clamp(inf[kEsAudioPes], 0, max_pes)) : 0;
+  const int ma = adts ? static_cast<int>(es_clamp(inf[ts::kNumAudioPes], 0, max_pes)) : 0;
   int n_frames = 0, err = 0, rate = 0, chans = 0;
   for (int64_t k = lane; k < max_pes; k += 64) {
     int32_t frames = -1, used = -1;
@@ -345,15 +330,15 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
     af[2 * k] = frames;
     af[2 * k + 1] = used;
   }
-  n_key = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(es_wave_scan(n_key)), 63));
-  n_frames = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(es_wave_scan(n_frames)), 63));
+  n_key = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(wave_scan_dpp(n_key)), 63));
+  n_frames = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(wave_scan_dpp(n_frames)), 63));
   const bool any_err = __ballot(err != 0) != 0;
   for (int d = 32; d > 0; d >>= 1) {
     const int other = __shfl_xor(first_key, d);
     first_key = other < first_key ? other : first_key;
   }
   if (lane == 0) {  // rate / chans: lane 0 walked audio PES 0
-    si[0] |= any_err ? kAdtsError : 0;
+    si[0] |= any_err ? es::kAdtsError : 0;
     si[2] = m;
     si[3] = n_key;
     si[4] = n_key > 0 ? first_key : -1;
@@ -363,34 +348,32 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   }
 }
 
-// scratch (int32): [tile_cnt: total_tiles | tile_pre: total_tiles | pos: nseg x (max_nal + 1)]
-hipError_t launch_es_index(const uint8_t* es, int64_t es_numel, const int64_t* es_off, const int64_t* cap,
-                           const int64_t* tile_prefix, int nseg, int64_t total_tiles, const int64_t* info,
-                           const int64_t* pes, int64_t max_pes, int64_t max_nal, int32_t* scratch, int32_t* nal,
-                           int32_t* au, int32_t* aframes, int64_t* sinfo, hipStream_t stream) {
-  if (nseg <= 0) return hipSuccess;
-  int32_t* tile_cnt = scratch;
-  int32_t* tile_pre = tile_cnt + total_tiles;
-  int32_t* pos = tile_pre + total_tiles;
+hipError_t launch_es_index(const EsIndexArgs& a) {
+  if (a.nseg <= 0) return hipSuccess;
+  const es::IndexScratch part = es::index_scratch(a.total_tiles, a.nseg, a.max_nal);
+  int32_t* tile_cnt = a.scratch + part.tile_cnt;
+  int32_t* tile_pre = a.scratch + part.tile_pre;
+  int32_t* pos = a.scratch + part.pos;
+  const dim3 tiles(static_cast<unsigned>(a.total_tiles));
   hipError_t e = hipSuccess;
-  if (total_tiles > 0) {
-    hipLaunchKernelGGL(es_count_kernel, dim3(static_cast<unsigned>(total_tiles)), dim3(kEsThreads), 0, stream, es,
-                       es_numel, es_off, cap, tile_prefix, nseg, info, tile_cnt);
+  if (a.total_tiles > 0) {
+    hipLaunchKernelGGL(es_count_kernel, tiles, dim3(kEsThreads), 0, a.stream, a.es, a.es_numel, a.es_off, a.cap,
+                       a.tile_prefix, a.nseg, a.info, tile_cnt);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(es_prefix_kernel, dim3(nseg), dim3(64), 0, stream, tile_prefix, tile_cnt, tile_pre, info, max_nal,
-                     sinfo);
+  hipLaunchKernelGGL(es_prefix_kernel, dim3(a.nseg), dim3(64), 0, a.stream, a.tile_prefix, tile_cnt, tile_pre, a.info,
+                     a.max_nal, a.sinfo);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (total_tiles > 0) {
-    hipLaunchKernelGGL(es_emit_kernel, dim3(static_cast<unsigned>(total_tiles)), dim3(kEsThreads), 0, stream, es,
-                       es_numel, es_off, cap, tile_prefix, nseg, info, tile_pre, max_nal, pos);
+  if (a.total_tiles > 0) {
+    hipLaunchKernelGGL(es_emit_kernel, tiles, dim3(kEsThreads), 0, a.stream, a.es, a.es_numel, a.es_off, a.cap,
+                       a.tile_prefix, a.nseg, a.info, tile_pre, a.max_nal, pos);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(es_finish_kernel, dim3(nseg), dim3(kEsThreads), 0, stream, es, es_off, cap, info, pes, max_pes,
-                     max_nal, pos, nal, au, aframes, sinfo);
+  hipLaunchKernelGGL(es_finish_kernel, dim3(a.nseg), dim3(kEsThreads), 0, a.stream, a.es, a.es_off, a.cap, a.info,
+                     a.pes, a.max_pes, a.max_nal, pos, a.nal, a.au, a.aframes, a.sinfo);
   return hipGetLastError();
 }
 

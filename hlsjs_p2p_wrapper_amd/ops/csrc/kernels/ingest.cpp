@@ -7,45 +7,16 @@
 //   per call; a round calls it once (CDN ingest) or twice (+ P2P verify).
 // * arena_views — the zero-copy uint8 views of the HBM arena handed to the loaders, made
 //   in one call (a Python slice costs ~1.5 us each, 64+ per round).
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-#include <pybind11/numpy.h>
-#include <pybind11/stl.h>
+#include <algorithm>
 
-#include <cstring>
-#include <vector>
-
-namespace hlsp2p {
-namespace dev {
-hipError_t launch_crc32_batch(const uint8_t*, const int64_t*, const int64_t*, const int64_t*, const int64_t*,
-                              const void*, const uint32_t*, uint32_t*, uint32_t*, const uint32_t*, uint8_t*,
-                              const int64_t*, uint32_t*, int64_t, int, int64_t, int, bool, hipStream_t,
-                              const int64_t*);
-}  // namespace dev
-}  // namespace hlsp2p
+#include "host_util.h"
 
 namespace {
 
 namespace py = pybind11;
+namespace crc = hlsp2p::crc;
 using torch::Tensor;
 using I64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
-
-int cus(int device) {
-  static int cached[64] = {0};
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int n = 0;
-  hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device);
-  if (n <= 0) n = 256;
-  if (device >= 0 && device < 64) cached[device] = n;
-  return n;
-}
-
-void put(std::vector<uint8_t>& blk, int64_t& off, const void* p, int64_t nbytes) {
-  off = static_cast<int64_t>(blk.size());
-  blk.resize(off + ((nbytes + 15) & ~int64_t(15)), 0);
-  if (nbytes) std::memcpy(blk.data() + off, p, static_cast<size_t>(nbytes));
-}
 
 // CRC-32 (zlib) of buf[offs[i] : offs[i] + lens[i]] (16-byte aligned offsets).  `expect`:
 // int32 device tensor of expected values -> also returns ok (uint8, 1 = match).  `scatter_to`
@@ -62,7 +33,8 @@ py::tuple crc32_launch(Tensor buf, I64 offs, I64 lens, Tensor wfrag, Tensor tabl
   TORCH_CHECK_VALUE(lens.size() == B, "crc32_launch: offs / lens sizes differ");
   const bool fp4 = wfrag.scalar_type() == torch::kUInt8;
   TORCH_CHECK_VALUE(wfrag.is_cuda() && wfrag.numel() >= (fp4 ? 32 * 64 * 16 : 64 * 64 * 16), "wfrag");
-  TORCH_CHECK_VALUE(tables.is_cuda() && tables.scalar_type() == torch::kInt32 && tables.numel() >= 48 * 1024, "tables");
+  TORCH_CHECK_VALUE(tables.is_cuda() && tables.scalar_type() == torch::kInt32 && tables.numel() >= crc::kShiftTableWords,
+                    "tables");
   const int device = buf.get_device();
   const auto dev_opts = torch::TensorOptions().device(torch::kCUDA, device);
   if (B == 0)
@@ -76,44 +48,35 @@ py::tuple crc32_launch(Tensor buf, I64 offs, I64 lens, Tensor wfrag, Tensor tabl
   for (int64_t i = 0; i < B; ++i) {
     TORCH_CHECK_VALUE(o[i] >= 0 && n[i] >= 0 && o[i] + n[i] <= cap, "crc32_launch: range out of bounds");
     TORCH_CHECK_VALUE(o[i] % 16 == 0, "crc32_launch: offsets must be 16-byte aligned");
-    const int64_t groups = (n[i] + 255) / 256;
     res_off[i] = groups_total;
-    groups_total += groups;
-    tile_prefix[i + 1] = tile_prefix[i] + (groups + 31) / 32;
+    groups_total += crc::groups(n[i]);
+    tile_prefix[i + 1] = tile_prefix[i] + crc::tiles(n[i]);
   }
-  const uint32_t* ex = nullptr;
-  if (expect.has_value()) {
+  const bool verify = expect.has_value();
+  if (verify)
     TORCH_CHECK_VALUE(expect->is_cuda() && expect->scalar_type() == torch::kInt32 && expect->numel() >= B &&
                     expect->is_contiguous(),
                 "expect: int32 GPU tensor of B values");
-    ex = static_cast<const uint32_t*>(expect->data_ptr());
-  }
   TORCH_CHECK_VALUE(scatter_to.has_value() == scatter_idx.has_value(), "scatter_to and scatter_idx go together");
-  std::vector<uint8_t> blk;
-  int64_t d_o, d_n, d_tp, d_ro, d_si = -1, d_k = -1;
-  put(blk, d_o, o, B * 8);
-  put(blk, d_n, n, B * 8);
-  put(blk, d_tp, tile_prefix.data(), (B + 1) * 8);
-  put(blk, d_ro, res_off.data(), B * 8);
-  uint32_t* sout = nullptr;
-  int64_t sn = 0;
+  hlsp2p::host::Staging blk;
+  const int64_t d_o = blk.add(o, B * 8), d_n = blk.add(n, B * 8), d_tp = blk.add(tile_prefix), d_ro = blk.add(res_off);
+  int64_t d_si = -1, d_k = -1;  // -1: absent
   if (scatter_to.has_value()) {
     TORCH_CHECK_VALUE(scatter_to->is_cuda() && scatter_to->scalar_type() == torch::kInt32 && scatter_to->is_contiguous(),
                 "scatter_to: int32 GPU tensor");
     const I64& si = *scatter_idx;
     TORCH_CHECK_VALUE(si.size() == B, "scatter_idx size");
-    sn = scatter_to->numel();
+    const int64_t sn = scatter_to->numel();
     for (int64_t i = 0; i < B; ++i) TORCH_CHECK_VALUE(si.data()[i] >= 0 && si.data()[i] < sn, "scatter index out of range");
-    put(blk, d_si, si.data(), B * 8);
-    sout = static_cast<uint32_t*>(scatter_to->data_ptr());
+    d_si = blk.add(si.data(), B * 8);
   }
   if (keys.has_value()) {
     TORCH_CHECK_VALUE(keys->size() == 4 * B, "keys: int64[B, 4]");
-    put(blk, d_k, keys->data(), B * 32);
+    d_k = blk.add(keys->data(), B * 32);
   }
-  const int64_t nbytes = static_cast<int64_t>(blk.size());
-  Tensor host = torch::empty({nbytes}, torch::TensorOptions().dtype(torch::kUInt8).pinned_memory(true));
-  std::memcpy(host.data_ptr<uint8_t>(), blk.data(), blk.size());
+  const int64_t nbytes = blk.size();
+  Tensor host = hlsp2p::host::pinned_bytes(nbytes);
+  blk.copy_to(host);
   // one device block: descriptors | residues | crc | ok
   const int64_t res_words = std::max<int64_t>(1, groups_total);
   const int64_t d_res = (nbytes + 255) / 256 * 256;
@@ -122,17 +85,23 @@ py::tuple crc32_launch(Tensor buf, I64 offs, I64 lens, Tensor wfrag, Tensor tabl
   Tensor dblk = torch::empty({d_ok + B}, dev_opts.dtype(torch::kUInt8));
   dblk.narrow(0, 0, nbytes).copy_(host, /*non_blocking=*/true);
   uint8_t* base = dblk.data_ptr<uint8_t>();
-  auto at = [&](int64_t off) { return reinterpret_cast<int64_t*>(base + off); };
+  auto u32t = [](const Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
+  auto at = [&](int64_t off) { return off >= 0 ? reinterpret_cast<int64_t*>(base + off) : nullptr; };
+  auto u32 = [&](int64_t off) { return reinterpret_cast<uint32_t*>(base + off); };
   Tensor crc = dblk.narrow(0, d_crc, B * 4).view(torch::kInt32);
   Tensor ok = dblk.narrow(0, d_ok, B);
-  hipStream_t st = c10::hip::getCurrentHIPStream(device).stream();
-  const hipError_t e = hlsp2p::dev::launch_crc32_batch(
-      static_cast<const uint8_t*>(buf.data_ptr()), at(d_o), at(d_n), at(d_tp), at(d_ro), wfrag.data_ptr(),
-      static_cast<const uint32_t*>(tables.data_ptr()), reinterpret_cast<uint32_t*>(base + d_res),
-      reinterpret_cast<uint32_t*>(base + d_crc), ex, ex ? base + d_ok : nullptr, d_si >= 0 ? at(d_si) : nullptr, sout,
-      sn, static_cast<int>(B), tile_prefix[B], cus(device), fp4, st, d_k >= 0 ? at(d_k) : nullptr);
-  TORCH_CHECK(e == hipSuccess, "crc32 launch failed: ", hipGetErrorString(e));
-  return py::make_tuple(crc, ex ? py::cast(ok) : py::none());
+  hlsp2p::host::hip_ok(
+      hlsp2p::dev::launch_crc32_batch(
+          {.buf = buf.data_ptr<uint8_t>(), .seg_off = at(d_o), .seg_len = at(d_n), .tile_prefix = at(d_tp),
+           .res_off = at(d_ro), .wfrag = wfrag.data_ptr(), .fp4 = fp4, .tables = u32t(tables), .residues = u32(d_res),
+           .out = {.crc_out = u32(d_crc), .expect = verify ? u32t(*expect) : nullptr,
+                   .ok_out = verify ? base + d_ok : nullptr, .scatter_idx = at(d_si),
+                   .scatter_out = d_si >= 0 ? u32t(*scatter_to) : nullptr,
+                   .scatter_n = d_si >= 0 ? scatter_to->numel() : 0},
+           .keys = at(d_k), .nseg = static_cast<int>(B), .total_tiles = tile_prefix[B],
+           .num_cu = hlsp2p::host::num_cus(device), .stream = c10::hip::getCurrentHIPStream(device).stream()}),
+      "crc32 launch");
+  return py::make_tuple(crc, verify ? py::cast(ok) : py::none());
 }
 
 // 1-D uint8 views arena[offs[i] : offs[i] + lens[i]] (shared storage, no copy).

@@ -1,0 +1,123 @@
+// Host side of every kernel launch: one argument struct and one declaration per launcher, included
+// by the defining .hip file and by every caller.  Device pointers; optional groups default to off.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+
+#include "layout.hpp"
+
+namespace hlsp2p {
+namespace dev {
+
+// Packet-header records: the decrypt writes ts::header_records(n) per segment, the demux scan reads them.
+struct HeaderRecords {
+  const int64_t* off = nullptr;  // [nseg] the segment's first record
+  void* rec = nullptr;
+};
+
+// What a CRC combine writes: crc_out[nseg], ok_out = (expect == crc), scatter_out[scatter_idx] = crc.
+struct CrcResults {
+  uint32_t* crc_out;
+  const uint32_t* expect = nullptr;
+  uint8_t* ok_out = nullptr;
+  const int64_t* scatter_idx = nullptr;
+  uint32_t* scatter_out = nullptr;
+  int64_t scatter_n = 0;
+};
+
+struct AesDecryptArgs {
+  const uint8_t* src;
+  uint8_t* dst;
+  const int64_t *src_off, *dst_off, *blk_prefix, *chunk_prefix;
+  const uint32_t *drk, *iv, *td0;
+  const uint8_t* isb;
+  int64_t* out_len;
+  int nseg;
+  int64_t total_chunks;
+  int num_cu;
+  hipStream_t stream;
+  struct FusedCrc {  // CRC-32 of the ciphertext; mask_off == nullptr: off
+    const int64_t* mask_off = nullptr;
+    const void* wfrag = nullptr;
+    uint32_t* masks = nullptr;
+  } crc;
+  HeaderRecords hdr;
+};
+int aes_chunk_blocks();
+hipError_t launch_aes128_cbc_decrypt(const AesDecryptArgs& a);
+
+struct Crc32BatchArgs {
+  const uint8_t* buf;
+  const int64_t *seg_off, *seg_len, *tile_prefix, *res_off;
+  const void* wfrag;
+  bool fp4;
+  const uint32_t* tables;  // [crc::kShiftTableWords]
+  uint32_t* residues;
+  CrcResults out;
+  const int64_t* keys = nullptr;  // [nseg][4]: expect / scatter values are bound to the key
+  int nseg;
+  int64_t total_tiles;
+  int num_cu;
+  hipStream_t stream;
+};
+hipError_t launch_crc32_batch(const Crc32BatchArgs& a);
+
+struct Crc32FromMasksArgs {  // second level of the CRC fused into the decrypt
+  const uint32_t* masks;
+  const void* wfold;
+  const int64_t *chunk_off, *seg_len;
+  const uint32_t* tables;  // [crc::kShiftTableWords]
+  uint32_t* chunk_res;
+  CrcResults out;
+  int nseg;
+  hipStream_t stream;
+};
+hipError_t launch_crc32_from_masks(const Crc32FromMasksArgs& a);
+
+struct TsDemuxArgs {
+  const uint8_t* buf;
+  const int64_t *seg_off, *seg_len, *blk_prefix;
+  int nseg;
+  int64_t total_blocks;
+  uint32_t* meta;  // meta, pts_dts, aux: ts::demux_workspace(total_blocks, nseg)
+  int64_t* pts_dts;
+  int32_t* aux;
+  uint8_t* es;
+  const int64_t* es_off;
+  int64_t* pes;
+  int64_t max_pes;
+  int64_t* info;
+  hipStream_t stream;
+  HeaderRecords hdr;
+};
+hipError_t launch_ts_demux(const TsDemuxArgs& a);
+
+struct EsIndexArgs {
+  const uint8_t* es;
+  int64_t es_numel;
+  const int64_t *es_off, *cap, *tile_prefix;
+  int nseg;
+  int64_t total_tiles;
+  const int64_t *info, *pes;
+  int64_t max_pes, max_nal;
+  int32_t* scratch;  // es::index_scratch(total_tiles, nseg, max_nal)
+  int32_t *nal, *au, *aframes;
+  int64_t* sinfo;
+  hipStream_t stream;
+};
+int es_index_tile_bytes();
+hipError_t launch_es_index(const EsIndexArgs& a);
+
+struct SegmentCopyArgs {
+  const uint8_t* src;
+  uint8_t* dst;
+  const int64_t *src_off, *dst_off, *len, *chunk_prefix;
+  int ncopy;
+  int64_t total_chunks;
+  hipStream_t stream;
+};
+hipError_t launch_segment_copy(const SegmentCopyArgs& a);
+
+}  // namespace dev
+}  // namespace hlsp2p

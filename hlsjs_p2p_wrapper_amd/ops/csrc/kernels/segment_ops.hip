@@ -11,6 +11,7 @@
 // no consumer (a launch + D2H sync costs more than the host bisects it would replace) and
 // were removed.
 #include "common.h"
+#include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -60,12 +61,10 @@ __global__ __launch_bounds__(kCopyThreads) void segment_copy_kernel(
 }
 
 // ------------------------------------------------------------------ launchers
-hipError_t launch_segment_copy(const uint8_t* src, uint8_t* dst, const int64_t* src_off, const int64_t* dst_off,
-                               const int64_t* len, const int64_t* chunk_prefix, int ncopy, int64_t total_chunks,
-                               hipStream_t stream) {
-  if (ncopy <= 0 || total_chunks <= 0) return hipSuccess;
-  hipLaunchKernelGGL(segment_copy_kernel, dim3(static_cast<unsigned>(total_chunks)), dim3(kCopyThreads), 0, stream,
-                     src, dst, src_off, dst_off, len, chunk_prefix, ncopy);
+hipError_t launch_segment_copy(const SegmentCopyArgs& a) {
+  if (a.ncopy <= 0 || a.total_chunks <= 0) return hipSuccess;
+  hipLaunchKernelGGL(segment_copy_kernel, dim3(static_cast<unsigned>(a.total_chunks)), dim3(kCopyThreads), 0, a.stream,
+                     a.src, a.dst, a.src_off, a.dst_off, a.len, a.chunk_prefix, a.ncopy);
   return hipGetLastError();
 }
 

@@ -9,34 +9,12 @@
 // packs, argument checks, six pybind launches, two pinned allocations) cost ~0.2 ms of host
 // time per 64-segment batch -- the host path bounds the per-GPU segment rate once peers
 // share the CDN work (N > 1); here it is tens of microseconds.
-#include <c10/hip/HIPStream.h>
-#include <hip/hip_runtime_api.h>
-#include <torch/extension.h>
-#include <pybind11/numpy.h>
-#include <pybind11/stl.h>
-
 #include <algorithm>
 #include <array>
 #include <chrono>
 #include <cstdlib>
-#include <cstring>
-#include <vector>
 
-namespace hlsp2p {
-namespace dev {
-int aes_chunk_blocks();
-hipError_t launch_aes128_cbc_decrypt(const uint8_t*, uint8_t*, const int64_t*, const int64_t*, const int64_t*,
-                                     const int64_t*, const uint32_t*, const uint32_t*, const uint32_t*,
-                                     const uint8_t*, int64_t*, int, int64_t, int, hipStream_t, const int64_t*,
-                                     const void*, uint32_t*, const int64_t*, void*);
-hipError_t launch_ts_demux(const uint8_t*, const int64_t*, const int64_t*, const int64_t*, int, int64_t, uint32_t*,
-                           int64_t*, int32_t*, uint8_t*, const int64_t*, int64_t*, int64_t, int64_t*, hipStream_t,
-                           const void*, const int64_t*);
-hipError_t launch_crc32_from_masks(const uint32_t*, const void*, const int64_t*, const int64_t*, const uint32_t*, uint32_t*, uint32_t*,
-                                   const uint32_t*, uint8_t*, const int64_t*, uint32_t*, int64_t, int, int64_t, int,
-                                   hipStream_t);
-}  // namespace dev
-}  // namespace hlsp2p
+#include "host_util.h"
 
 namespace {
 
@@ -44,11 +22,21 @@ namespace py = pybind11;
 using torch::Tensor;
 using I64 = py::array_t<int64_t, py::array::c_style | py::array::forcecast>;
 
-constexpr int64_t kAlign = 256;   // segment start alignment in the decrypt / ES buffers
-constexpr int64_t kPacket = 188;  // MPEG-TS packet
-constexpr int64_t kInfo = 24;     // int64 words per segment info row (ops/tsdemux.py INFO_WORDS)
+namespace D = hlsp2p::dev;
+namespace ts = hlsp2p::ts;
+namespace crc = hlsp2p::crc;
+using hlsp2p::host::hip_ok;
+
+constexpr int64_t kAlign = 256;  // segment start alignment in the decrypt / ES buffers
+constexpr int64_t kInfo = ts::kInfoWords;
 
 int64_t align_up(int64_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
+
+I64 to_numpy(const std::vector<int64_t>& v) {
+  I64 a(static_cast<py::ssize_t>(v.size()));
+  std::memcpy(a.mutable_data(), v.data(), v.size() * 8);
+  return a;
+}
 
 // host time of transmux_launch by stage (transmux_launch_profile): checks + plans,
 // descriptor upload, result allocations, decrypt (+ fused CRC) launches, demux launches + D2H
@@ -68,42 +56,6 @@ struct StageClock {
   }
 };
 
-// Host staging of many small arrays, 16-byte aligned, copied to the device in one H2D.
-class Desc {
- public:
-  int64_t add(const void* p, int64_t nbytes) {
-    const int64_t off = static_cast<int64_t>(buf_.size());
-    buf_.resize(off + ((nbytes + 15) & ~int64_t(15)), 0);
-    if (nbytes) std::memcpy(buf_.data() + off, p, static_cast<size_t>(nbytes));
-    return off;
-  }
-  template <typename T>
-  int64_t add(const std::vector<T>& v) { return add(v.data(), static_cast<int64_t>(v.size() * sizeof(T))); }
-  // pinned block from the caching host allocator (recorded on the copy's stream, so reuse
-  // waits for the copy), one non-blocking H2D on the current stream
-  Tensor upload(int device, StageClock& clk) {
-    const int64_t n = std::max<int64_t>(16, static_cast<int64_t>(buf_.size()));
-    clk.lap(kStDesc);
-    Tensor host = torch::empty({n}, torch::TensorOptions().dtype(torch::kUInt8).pinned_memory(true));
-    clk.lap(kStDescPin);
-    std::memcpy(host.data_ptr<uint8_t>(), buf_.data(), buf_.size());
-    clk.lap(kStDescCopy);
-    Tensor d = torch::empty({n}, torch::TensorOptions().dtype(torch::kUInt8).device(torch::kCUDA, device));
-    clk.lap(kStDescDev);
-    d.copy_(host, /*non_blocking=*/true);
-    clk.lap(kStDescH2D);
-    dev_ = d;
-    return d;
-  }
-  template <typename T>
-  T* at(int64_t off) const { return reinterpret_cast<T*>(static_cast<uint8_t*>(dev_.data_ptr()) + off); }
-  Tensor device() const { return dev_; }
-
- private:
-  std::vector<uint8_t> buf_;
-  Tensor dev_;
-};
-
 struct DemuxPlan {
   std::vector<int64_t> idx, off, len, cap, es_off, es_cap, blk_prefix;
   int64_t es_bytes = 0, total_blocks = 0;
@@ -120,21 +72,10 @@ void plan_demux(DemuxPlan& p) {
     p.es_off[i] = pos;
     p.es_cap[i] = align_up(std::max<int64_t>(p.cap[i], 1));
     pos += p.es_cap[i];
-    const int64_t blocks = ((p.cap[i] + kPacket - 1) / kPacket + 255) / 256;  // 256-packet demux blocks
-    p.blk_prefix[i + 1] = p.blk_prefix[i] + blocks;
+    p.blk_prefix[i + 1] = p.blk_prefix[i] + ts::demux_blocks(p.cap[i]);
   }
   p.es_bytes = pos + kAlign;
   p.total_blocks = p.blk_prefix[B];
-}
-
-int cus(int device) {
-  static int cached[64] = {0};
-  if (device >= 0 && device < 64 && cached[device]) return cached[device];
-  int n = 0;
-  hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device);
-  if (n <= 0) n = 256;
-  if (device >= 0 && device < 64) cached[device] = n;
-  return n;
 }
 
 // CUs the persistent decrypt grid leaves free (set_cu_reserve): with a live RCCL data plane
@@ -152,18 +93,16 @@ int decrypt_cus(int device) {
     const char* v = std::getenv("HLSP2P_DECRYPT_CUS");
     g_decrypt_cap = v != nullptr ? std::max(0, std::atoi(v)) : 0;
   }
-  int n = cus(device) - g_cu_reserve;
+  int n = hlsp2p::host::num_cus(device) - g_cu_reserve;
   if (g_decrypt_cap > 0) n = std::min(n, g_decrypt_cap);
   return std::max(8, n);
 }
-
-void hip_ok(hipError_t e, const char* what) { TORCH_CHECK(e == hipSuccess, what, " failed: ", hipGetErrorString(e)); }
 
 // src: uint8 device buffer holding every payload at src_off[i] (16-byte aligned) with
 // nbytes[i] bytes; enc[i] != 0 -> AES-128-CBC with round keys drk[i] (44 little-endian
 // words, equivalent inverse cipher) and IV iv[i]; encrypted sizes must be positive
 // multiples of 16 (the caller rejects others).  Returns, per group (encrypted, then clear):
-// (indices into the batch, info [B,24] device, pes device, es buffer, es offsets,
+// (indices into the batch, info [B, ts::kInfoWords] device, pes device, es buffer, es offsets,
 // info rows in pinned host memory, plaintext lengths in pinned host memory (enc) or a
 // host array (clear)); plus the decrypt buffer to keep alive until the batch completes.
 py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8_t, py::array::c_style> enc,
@@ -212,8 +151,10 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
     if (!any) v_exp.clear();
     else
       TORCH_CHECK_VALUE(crc_w.has_value() && crc_tables.has_value() && crc_w->is_cuda() &&
-                            crc_w->numel() * crc_w->element_size() >= (8 + 32) * 64 * 16 && crc_tables->is_cuda() &&
-                            crc_tables->numel() >= (40 + 12) * 1024,
+                            crc_w->numel() * crc_w->element_size() >=
+                                (crc::kFusedAesSteps + crc::kFusedFoldSteps) * 64 * 16 &&
+                            crc_tables->is_cuda() &&
+                            crc_tables->numel() >= crc::kShiftTableWords,
                         "fused CRC verify needs the chunk weights and shift tables on the device");
   }
 
@@ -233,7 +174,7 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
   std::vector<uint32_t> a_drk;
   std::vector<uint8_t> a_iv;
   DemuxPlan pe, pc;
-  const int64_t chunk = hlsp2p::dev::aes_chunk_blocks();
+  const int64_t chunk = D::aes_chunk_blocks();
   int64_t dec_pos = 0;
   for (int64_t i = 0; i < B; ++i) {
     if (en[i]) {
@@ -247,11 +188,11 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
       a_bp.push_back(a_bp.back() + blocks);
       a_cp.push_back(a_cp.back() + (blocks + chunk - 1) / chunk);
       a_ho.push_back(hdr_pos);
-      hdr_pos += nb[i] / kPacket + 2;
+      hdr_pos += ts::header_records(nb[i]);
       if (!v_exp.empty()) {
         const int64_t nch = (blocks + chunk - 1) / chunk;  // one 4096-byte CRC chunk per decrypt chunk
         if (v_exp[i] >= 0) {
-          a_mo.push_back(64 * v_chunks);  // crc_host.hpp kFusedMaskDwords
+          a_mo.push_back(crc::kFusedMaskDwords * v_chunks);
           v_idx.push_back(i);
           v_coff.push_back(v_chunks);
           v_len.push_back(nb[i]);
@@ -276,7 +217,7 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
 
   clk.lap(kStPlan);
   // ---- every descriptor of the batch in one staging block, one H2D
-  Desc desc;
+  hlsp2p::host::Staging desc;
   int64_t d_so = -1, d_do = -1, d_bp = -1, d_cp = -1, d_drk = -1, d_iv = -1, d_mo = -1, d_vco = -1, d_vl = -1,
           d_vx = -1, d_ho = -1;
   const int64_t nv = static_cast<int64_t>(v_idx.size());
@@ -305,7 +246,21 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
     pc.d_bp = desc.add(pc.blk_prefix);
     pc.d_eo = desc.add(pc.es_off);
   }
-  desc.upload(device, clk);
+  // one pinned block from the caching host allocator, one non-blocking H2D on the current stream
+  const int64_t desc_n = std::max<int64_t>(16, desc.size());
+  clk.lap(kStDesc);
+  Tensor desc_host = hlsp2p::host::pinned_bytes(desc_n);
+  clk.lap(kStDescPin);
+  desc.copy_to(desc_host);
+  clk.lap(kStDescCopy);
+  Tensor desc_dev = torch::empty({desc_n}, dev_opts.dtype(torch::kUInt8));
+  clk.lap(kStDescDev);
+  desc_dev.copy_(desc_host, /*non_blocking=*/true);
+  clk.lap(kStDescH2D);
+  uint8_t* const desc_base = desc_dev.data_ptr<uint8_t>();
+  auto at64 = [&](int64_t off) { return reinterpret_cast<int64_t*>(desc_base + off); };
+  auto at32 = [&](int64_t off) { return reinterpret_cast<uint32_t*>(desc_base + off); };
+  auto u32 = [](const Tensor& t) { return reinterpret_cast<uint32_t*>(t.data_ptr<int32_t>()); };
 
   // ---- host results block: info rows (enc group, then clear group) | enc plaintext lengths
   Tensor host = torch::empty({(ne + nc) * kInfo + ne + 1}, torch::TensorOptions().dtype(torch::kInt64).pinned_memory(true));
@@ -313,7 +268,7 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
   if (ne) out_len = torch::empty({ne}, dev_opts.dtype(torch::kInt64));
   Tensor masks, chunk_res, v_crc, v_ok, v_ok_host;
   if (nv) {
-    masks = torch::empty({64 * v_chunks}, dev_opts.dtype(torch::kInt32));
+    masks = torch::empty({crc::kFusedMaskDwords * v_chunks}, dev_opts.dtype(torch::kInt32));
     chunk_res = torch::empty({std::max<int64_t>(1, v_chunks)}, dev_opts.dtype(torch::kInt32));
     v_crc = torch::empty({nv}, dev_opts.dtype(torch::kInt32));
     v_ok = torch::empty({nv}, dev_opts.dtype(torch::kUInt8));
@@ -322,25 +277,26 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
   if (ne && hdr_on) hdr_rec = torch::empty({std::max<int64_t>(1, hdr_pos) * 16}, dev_opts.dtype(torch::kUInt8));
   if (ne) dec = torch::empty({dec_pos + kAlign}, dev_opts.dtype(torch::kUInt8));
   clk.lap(kStAlloc);
+  D::HeaderRecords hdr;  // written by the decrypt, read by the encrypted group's demux scan
+  if (ne && hdr_on) hdr = {.off = at64(d_ho), .rec = hdr_rec.data_ptr()};
   if (ne) {
-    hip_ok(hlsp2p::dev::launch_aes128_cbc_decrypt(
-               static_cast<const uint8_t*>(src.data_ptr()), static_cast<uint8_t*>(dec.data_ptr()),
-               desc.at<int64_t>(d_so), desc.at<int64_t>(d_do), desc.at<int64_t>(d_bp), desc.at<int64_t>(d_cp),
-               desc.at<uint32_t>(d_drk), desc.at<uint32_t>(d_iv), static_cast<const uint32_t*>(td0.data_ptr()),
-               static_cast<const uint8_t*>(isb.data_ptr()), out_len.data_ptr<int64_t>(), static_cast<int>(ne),
-               a_cp.back(), decrypt_cus(device), st, nv ? desc.at<int64_t>(d_mo) : nullptr,
-               nv ? crc_w->data_ptr() : nullptr, nv ? reinterpret_cast<uint32_t*>(masks.data_ptr<int32_t>()) : nullptr,
-               hdr_on ? desc.at<int64_t>(d_ho) : nullptr, hdr_on ? hdr_rec.data_ptr() : nullptr),
-           "aes128_cbc_decrypt");
+    D::AesDecryptArgs a{.src = src.data_ptr<uint8_t>(), .dst = dec.data_ptr<uint8_t>(), .src_off = at64(d_so),
+                        .dst_off = at64(d_do), .blk_prefix = at64(d_bp), .chunk_prefix = at64(d_cp),
+                        .drk = at32(d_drk), .iv = at32(d_iv), .td0 = static_cast<const uint32_t*>(td0.data_ptr()),
+                        .isb = static_cast<const uint8_t*>(isb.data_ptr()), .out_len = out_len.data_ptr<int64_t>(),
+                        .nseg = static_cast<int>(ne), .total_chunks = a_cp.back(), .num_cu = decrypt_cus(device),
+                        .stream = st, .hdr = hdr};
+    if (nv) a.crc = {.mask_off = at64(d_mo), .wfrag = crc_w->data_ptr(), .masks = u32(masks)};
+    hip_ok(D::launch_aes128_cbc_decrypt(a), "aes128_cbc_decrypt");
   }
   if (nv) {  // fold the decrypt's CRC masks per chunk, combine per segment, compare
-    hip_ok(hlsp2p::dev::launch_crc32_from_masks(
-               reinterpret_cast<const uint32_t*>(masks.data_ptr<int32_t>()),
-               static_cast<const uint8_t*>(crc_w->data_ptr()) + 8 * 64 * 16, desc.at<int64_t>(d_vco),
-               desc.at<int64_t>(d_vl), static_cast<const uint32_t*>(crc_tables->data_ptr()),
-               reinterpret_cast<uint32_t*>(chunk_res.data_ptr<int32_t>()),
-               reinterpret_cast<uint32_t*>(v_crc.data_ptr<int32_t>()), desc.at<uint32_t>(d_vx),
-               v_ok.data_ptr<uint8_t>(), nullptr, nullptr, 0, static_cast<int>(nv), v_chunks, cus(device), st),
+    hip_ok(D::launch_crc32_from_masks(
+               {.masks = u32(masks),
+                .wfold = static_cast<const uint8_t*>(crc_w->data_ptr()) + crc::kFusedAesSteps * 64 * 16,
+                .chunk_off = at64(d_vco), .seg_len = at64(d_vl),
+                .tables = static_cast<const uint32_t*>(crc_tables->data_ptr()), .chunk_res = u32(chunk_res),
+                .out = {.crc_out = u32(v_crc), .expect = at32(d_vx), .ok_out = v_ok.data_ptr<uint8_t>()},
+                .nseg = static_cast<int>(nv), .stream = st}),
            "crc32_from_masks");
     v_ok_host = torch::empty({nv}, torch::TensorOptions().dtype(torch::kUInt8).pinned_memory(true));
     v_ok_host.copy_(v_ok, /*non_blocking=*/true);
@@ -353,24 +309,22 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
     DemuxPlan& p = g == 0 ? pe : pc;
     const int64_t n = static_cast<int64_t>(p.idx.size());
     if (!n) continue;
-    const uint8_t* buf = g == 1 ? static_cast<const uint8_t*>(src.data_ptr())
-                         : dec.defined() ? static_cast<const uint8_t*>(dec.data_ptr()) : nullptr;
-    const int64_t* lens = g == 0 ? out_len.data_ptr<int64_t>() : desc.at<int64_t>(p.d_len);
+    const uint8_t* buf = (g == 1 ? src : dec).data_ptr<uint8_t>();  // group 0 exists only with a decrypt buffer
+    const int64_t* lens = g == 0 ? out_len.data_ptr<int64_t>() : at64(p.d_len);
     const int64_t nb_blocks = std::max<int64_t>(1, p.total_blocks);
     Tensor es = torch::empty({p.es_bytes}, dev_opts.dtype(torch::kUInt8));
     Tensor info = torch::empty({n, kInfo}, dev_opts.dtype(torch::kInt64));
-    Tensor pes = torch::empty({n, 3, max_pes, 3}, dev_opts.dtype(torch::kInt64));
-    Tensor meta = torch::empty({nb_blocks * 256}, dev_opts.dtype(torch::kInt32));
-    Tensor pts = torch::empty({nb_blocks * 256 * 2}, dev_opts.dtype(torch::kInt64));
-    Tensor aux = torch::empty({nb_blocks * 12 + n * 7}, dev_opts.dtype(torch::kInt32));
-    hip_ok(hlsp2p::dev::launch_ts_demux(buf, desc.at<int64_t>(p.d_off), lens, desc.at<int64_t>(p.d_bp),
-                                        static_cast<int>(n), p.total_blocks,
-                                        reinterpret_cast<uint32_t*>(meta.data_ptr<int32_t>()),
-                                        pts.data_ptr<int64_t>(), aux.data_ptr<int32_t>(), es.data_ptr<uint8_t>(),
-                                        desc.at<int64_t>(p.d_eo), pes.data_ptr<int64_t>(), max_pes,
-                                        info.data_ptr<int64_t>(), st,
-                                        g == 0 && hdr_on ? hdr_rec.data_ptr() : nullptr,
-                                        g == 0 && hdr_on ? desc.at<int64_t>(d_ho) : nullptr),
+    Tensor pes = torch::empty({n, ts::kClasses, max_pes, 3}, dev_opts.dtype(torch::kInt64));
+    const auto ws = ts::demux_workspace(nb_blocks, n);
+    Tensor meta = torch::empty({ws.meta}, dev_opts.dtype(torch::kInt32));
+    Tensor pts = torch::empty({ws.pts_dts}, dev_opts.dtype(torch::kInt64));
+    Tensor aux = torch::empty({ws.aux}, dev_opts.dtype(torch::kInt32));
+    hip_ok(D::launch_ts_demux({.buf = buf, .seg_off = at64(p.d_off), .seg_len = lens, .blk_prefix = at64(p.d_bp),
+                               .nseg = static_cast<int>(n), .total_blocks = p.total_blocks, .meta = u32(meta),
+                               .pts_dts = pts.data_ptr<int64_t>(), .aux = aux.data_ptr<int32_t>(),
+                               .es = es.data_ptr<uint8_t>(), .es_off = at64(p.d_eo), .pes = pes.data_ptr<int64_t>(),
+                               .max_pes = max_pes, .info = info.data_ptr<int64_t>(), .stream = st,
+                               .hdr = g == 0 ? hdr : D::HeaderRecords{}}),
            "ts_demux");
     keep.append(py::make_tuple(meta, pts, aux));
     // D2H through torch's copy so the caching host allocator records the use of the pinned
@@ -384,26 +338,19 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
       hl.copy_(out_len, /*non_blocking=*/true);
       hlens = py::cast(hl);
     } else {
-      I64 l(static_cast<py::ssize_t>(n));
-      std::memcpy(l.mutable_data(), p.len.data(), static_cast<size_t>(n * 8));
-      hlens = l;
+      hlens = to_numpy(p.len);
     }
-    I64 idx(static_cast<py::ssize_t>(n)), eo(static_cast<py::ssize_t>(n));
-    std::memcpy(idx.mutable_data(), p.idx.data(), static_cast<size_t>(n * 8));
-    std::memcpy(eo.mutable_data(), p.es_off.data(), static_cast<size_t>(n * 8));
-    groups.append(py::make_tuple(idx, info, pes, es, eo, hinfo, hlens));
+    groups.append(py::make_tuple(to_numpy(p.idx), info, pes, es, to_numpy(p.es_off), hinfo, hlens));
     row0 += n;
   }
   clk.lap(kStDemux);
   keep.append(dec.defined() ? py::cast(dec) : py::none());
-  keep.append(desc.device());
+  keep.append(desc_dev);
   if (hdr_rec.defined()) keep.append(hdr_rec);
   py::object verify = py::none();
   if (nv) {
     keep.append(py::make_tuple(masks, chunk_res, v_crc, v_ok));
-    I64 vi(static_cast<py::ssize_t>(nv));
-    std::memcpy(vi.mutable_data(), v_idx.data(), static_cast<size_t>(nv * 8));
-    verify = py::make_tuple(vi, v_ok_host);  // batch indices of the verified segments, ok flags (pinned)
+    verify = py::make_tuple(to_numpy(v_idx), v_ok_host);  // batch indices of the verified segments, ok flags (pinned)
   }
   auto out = py::make_tuple(groups, keep, host, verify);
   clk.lap(kStResult);

@@ -19,25 +19,15 @@
 //                          iteration with dword-aligned stores (v_alignbyte funnel for the
 //                          unaligned LDS source).
 #include "common.h"
+#include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
 
-constexpr int kPkt = 188;
-constexpr int kTsThreads = 256;
-constexpr int kClasses = 3;
-constexpr int kInfo = 24;
-constexpr int kPsiScan = 64;
-// info slots / status bits (must match runtime/ts.hpp)
-constexpr int kStatus = 0, kPmtPid = 1, kVideoPid = 2, kNumPackets = 5, kBytes0 = 6, kPes0 = 9, kVideoType = 12,
-              kAudioType = 13, kPayloadBytes = 14, kFirstPts = 16, kLastPts = 19, kAudioEsOffset = 22,
-              kId3EsOffset = 23;
-constexpr int64_t kBadSync = 1, kNoPat = 2, kNoPmt = 4, kPesOverflow = 8, kPesHeaderError = 16, kBadLength = 32;
+using namespace ts;  // info slots, status bits, packet / block geometry (shared/layout.hpp)
 
-__device__ __forceinline__ int64_t read_pts(const uint8_t* p) {
-  return (int64_t((p[0] >> 1) & 0x07) << 30) | (int64_t(p[1]) << 22) | (int64_t(p[2] >> 1) << 15) |
-         (int64_t(p[3]) << 7) | int64_t(p[4] >> 1);
-}
+constexpr int kTsThreads = 256;
+static_assert(kTsThreads == kBlockPackets, "a demux block is one packet per lane of the scan / gather workgroup");
 
 __device__ __forceinline__ int64_t seg_length(const int64_t* len_dev, int seg) {
   const int64_t n = len_dev[seg];
@@ -50,29 +40,29 @@ __global__ __launch_bounds__(64) void ts_psi_kernel(const uint8_t* __restrict__ 
                                                     int64_t* __restrict__ pes, int64_t max_pes) {
   const int seg = blockIdx.x;
   const int lane = threadIdx.x;
-  int64_t* inf = info + static_cast<int64_t>(seg) * kInfo;
+  int64_t* inf = info + static_cast<int64_t>(seg) * kInfoWords;
   int64_t* pe = pes + static_cast<int64_t>(seg) * kClasses * max_pes * 3;
   for (int64_t i = lane; i < static_cast<int64_t>(kClasses) * max_pes * 3; i += 64) pe[i] = -1;
   if (lane != 0) return;
   const int64_t raw_len = seg_len[seg];
   const int64_t n = raw_len < 0 ? 0 : raw_len;
   const uint8_t* d = buf + seg_off[seg];
-  const int64_t np = n / kPkt;
-  int64_t status = (raw_len < 0 || n % kPkt) ? kBadLength : 0;
+  const int64_t np = n / kPacket;
+  int64_t status = (raw_len < 0 || n % kPacket) ? kBadLength : 0;
   int pmt_pid = -1, vpid = -1, apid = -1, ipid = -1, vtype = 0, atype = 0;
-  const int64_t scan = np < kPsiScan ? np : kPsiScan;
+  const int64_t scan = np < kPsiScanPackets ? np : kPsiScanPackets;
   for (int64_t i = 0; i < scan && pmt_pid < 0; ++i) {
-    const uint8_t* p = d + i * kPkt;
+    const uint8_t* p = d + i * kPacket;
     if (p[0] != 0x47) continue;
     const int pid = ((p[1] & 0x1f) << 8) | p[2];
     if (pid != 0 || !(p[1] & 0x40)) continue;
     const int afc = (p[3] >> 4) & 3;
     int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPkt) continue;
+    if (!(afc & 1) || ps >= kPacket) continue;
     ps += 1 + p[ps];
-    if (ps + 8 > kPkt || p[ps] != 0x00) continue;
+    if (ps + 8 > kPacket || p[ps] != 0x00) continue;
     const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    const int end = ps + 3 + slen - 4 < kPkt ? ps + 3 + slen - 4 : kPkt;
+    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
     for (int q = ps + 8; q + 4 <= end; q += 4) {
       const int prog = (p[q] << 8) | p[q + 1];
       if (prog != 0) {
@@ -84,18 +74,18 @@ __global__ __launch_bounds__(64) void ts_psi_kernel(const uint8_t* __restrict__ 
   if (pmt_pid < 0) status |= kNoPat;
   bool pmt_found = false;
   for (int64_t i = 0; i < scan && pmt_pid >= 0 && !pmt_found; ++i) {
-    const uint8_t* p = d + i * kPkt;
+    const uint8_t* p = d + i * kPacket;
     if (p[0] != 0x47) continue;
     const int pid = ((p[1] & 0x1f) << 8) | p[2];
     if (pid != pmt_pid || !(p[1] & 0x40)) continue;
     const int afc = (p[3] >> 4) & 3;
     int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPkt) continue;
+    if (!(afc & 1) || ps >= kPacket) continue;
     ps += 1 + p[ps];
-    if (ps + 12 > kPkt || p[ps] != 0x02) continue;
+    if (ps + 12 > kPacket || p[ps] != 0x02) continue;
     pmt_found = true;
     const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    const int end = ps + 3 + slen - 4 < kPkt ? ps + 3 + slen - 4 : kPkt;
+    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
     const int pil = ((p[ps + 10] & 0x0f) << 8) | p[ps + 11];
     for (int q = ps + 12 + pil; q + 5 <= end;) {
       const int type = p[q];
@@ -114,7 +104,7 @@ __global__ __launch_bounds__(64) void ts_psi_kernel(const uint8_t* __restrict__ 
     }
   }
   if (pmt_pid >= 0 && !pmt_found) status |= kNoPmt;
-  for (int k = 0; k < kInfo; ++k) inf[k] = 0;
+  for (int k = 0; k < kInfoWords; ++k) inf[k] = 0;
   inf[kStatus] = status;
   inf[kPmtPid] = pmt_pid;
   inf[kVideoPid] = vpid;
@@ -137,25 +127,9 @@ __device__ __forceinline__ uint32_t pack_meta(int c, int ps, int len, int pes) {
 }
 
 // ---------------------------------------------------------------- 2. scan
-// Inclusive prefix sum over the wave64 in six DPP-modified moves and adds, no LDS traffic
-// (a __shfl_up ladder is six ds_bpermute round trips): row_shr:1/2/4/8 scan each 16-lane row
-// (bound_ctrl fills 0 past the row start), row_bcast:15 adds row 0's / row 2's total to rows 1
-// and 3, row_bcast:31 adds rows 0-1's total to rows 2 and 3.
-__device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t v) {
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x111, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x112, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x114, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x118, 0xf, 0xf, true));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x142, 0xa, 0xf, false));
-  v += static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(v), 0x143, 0xc, 0xf, false));
-  return v;
-}
 // the wave's total (lane 63 of the inclusive scan), wave-uniform
 __device__ __forceinline__ uint32_t wave_sum_dpp(uint32_t v) {
   return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(wave_scan_dpp(v)), 63));
-}
-__device__ __forceinline__ int wave_incl_scan(int v, int /*lane*/) {
-  return static_cast<int>(wave_scan_dpp(static_cast<uint32_t>(v)));
 }
 
 // hdr_rec / hdr_off (optional, from the decrypt: aes_cbc.hip AesHdr): record p of a segment is
@@ -179,7 +153,7 @@ __device__ __forceinline__ ScanPkt scan_load(const uint8_t* __restrict__ p, cons
   r.b4 = -1;
   if (rec != nullptr) {
     const uint4 v = *rec;
-    const int o = static_cast<int>((pk * kPkt) & 15);  // 0, 4, 8 or 12
+    const int o = static_cast<int>((pk * kPacket) & 15);  // 0, 4, 8 or 12
     r.hdr = o == 0 ? v.x : o == 4 ? v.y : o == 8 ? v.z : v.w;
     if (o < 12) r.b4 = static_cast<int>((o == 0 ? v.y : o == 4 ? v.z : v.w) & 0xff);
   } else {
@@ -215,11 +189,11 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
         seg = __builtin_amdgcn_readfirstlane(advance_seg(blk_prefix, seg, gb0 + u));
         segs[u] = seg;
       }
-      const int64_t np = seg_length(seg_len, seg) / kPkt;
+      const int64_t np = seg_length(seg_len, seg) / kPacket;
       const int64_t pk = (gb0 + u - blk_prefix[seg]) * kTsThreads + tid;
       if (pk < np) {
         pks[u] = pk;
-        pp[u] = buf + seg_off[seg] + pk * kPkt;
+        pp[u] = buf + seg_off[seg] + pk * kPacket;
         pkt[u] = scan_load(pp[u], hdr_rec != nullptr ? hdr_rec + hdr_off[seg] + pk : nullptr, pk);
       }
     }
@@ -248,10 +222,10 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
       const uint32_t hdr = pkt[u].hdr;
       const int afc = (hdr >> 28) & 3, b1 = (hdr >> 8) & 0xff;
       const int s0 = 4 + ((afc & 2) ? 1 + b4v[u] : 0);
-      if ((hdr & 0xff) == 0x47 && (b1 & 0x40) && (afc & 1) && s0 + 9 <= kPkt) {
+      if ((hdr & 0xff) == 0x47 && (b1 & 0x40) && (afc & 1) && s0 + 9 <= kPacket) {
         const uint8_t* h = pp[u] + s0;
         const uint32_t* w = reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(h) & ~uintptr_t(3));
-        const uint32_t* wend = reinterpret_cast<const uint32_t*>(pp[u] + kPkt);  // packets are 4-byte aligned
+        const uint32_t* wend = reinterpret_cast<const uint32_t*>(pp[u] + kPacket);  // packets are 4-byte aligned
         uint32_t d[6];
 #pragma unroll
         for (int k = 0; k < 6; ++k) d[k] = w + k < wend ? w[k] : 0u;
@@ -268,7 +242,7 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
     if (u >= nb) break;
     if (segs[u] != cur) {
       cur = segs[u];
-      const int64_t* inf = info + static_cast<int64_t>(cur) * kInfo;
+      const int64_t* inf = info + static_cast<int64_t>(cur) * kInfoWords;
       cpid0 = static_cast<int>(inf[kVideoPid]);
       cpid1 = static_cast<int>(inf[kVideoPid + 1]);
       cpid2 = static_cast<int>(inf[kVideoPid + 2]);
@@ -288,10 +262,10 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
         const int afc = (b3 >> 4) & 3;
         if (cls < 3 && (afc & 1)) {
           int s = 4 + ((afc & 2) ? 1 + b4v[u] : 0);
-          if (s > kPkt) {
+          if (s > kPacket) {
             err |= static_cast<int>(kBadLength);
           } else {
-            int l = kPkt - s;
+            int l = kPacket - s;
             bool ok = true;
             if (b1 & 0x40) {
 #define HB(i) static_cast<int>((hw[u][(i) >> 2] >> (8 * ((i) & 3))) & 0xffu)
@@ -346,7 +320,7 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
   if (tid == 0) {
     for (int u = 0; u < nb; ++u)
       if (s_err[u])
-        atomicOr(reinterpret_cast<unsigned long long*>(info + static_cast<int64_t>(segs[u]) * kInfo + kStatus),
+        atomicOr(reinterpret_cast<unsigned long long*>(info + static_cast<int64_t>(segs[u]) * kInfoWords + kStatus),
                  static_cast<unsigned long long>(s_err[u]));
   }
 }
@@ -373,7 +347,7 @@ __global__ __launch_bounds__(64) void ts_prefix_kernel(const int64_t* __restrict
     for (int k = 0; k < 2 * kClasses; ++k) v[k] = b < nblk ? blk_sums[(b0 + b) * 2 * kClasses + k] : 0;
 #pragma unroll
     for (int k = 0; k < 2 * kClasses; ++k) {
-      const int inc = wave_incl_scan(v[k], lane);
+      const int inc = static_cast<int>(wave_scan_dpp(static_cast<uint32_t>(v[k])));
       if (b < nblk) blk_pre[(b0 + b) * 2 * kClasses + k] = carry[k] + inc - v[k];
       carry[k] += __shfl(inc, 63);
     }
@@ -381,11 +355,11 @@ __global__ __launch_bounds__(64) void ts_prefix_kernel(const int64_t* __restrict
   if (lane == 0) {  // carry[] is wave-uniform
 #pragma unroll
     for (int k = 0; k < 2 * kClasses; ++k) seg_tot[seg * 2 * kClasses + k] = carry[k];
-    int64_t* inf = info + static_cast<int64_t>(seg) * kInfo;
+    int64_t* inf = info + static_cast<int64_t>(seg) * kInfoWords;
     int64_t over = 0;
     for (int k = 0; k < kClasses; ++k) {
-      inf[kBytes0 + k] = carry[2 * k];
-      inf[kPes0 + k] = carry[2 * k + 1];
+      inf[kVideoBytes + k] = carry[2 * k];
+      inf[kNumVideoPes + k] = carry[2 * k + 1];
       if (carry[2 * k + 1] > max_pes) over = kPesOverflow;
     }
     inf[kPayloadBytes] = static_cast<int64_t>(carry[0]) + carry[2] + carry[4];
@@ -403,7 +377,7 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
     uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, int64_t* __restrict__ pes, int64_t max_pes,
     int64_t* __restrict__ info) {
   // this block's 256 packets (47 KiB), rounded up to whole 16-byte-per-lane LDS-DMA waves
-  constexpr int kStageVec = (kTsThreads * kPkt + 16 * kTsThreads - 1) / (16 * kTsThreads);  // 12
+  constexpr int kStageVec = (kTsThreads * kPacket + 16 * kTsThreads - 1) / (16 * kTsThreads);  // 12
   __shared__ __attribute__((aligned(16))) uint32_t s_pk[kStageVec * kTsThreads * 4];
   __shared__ uint32_t s_wave[4][3];      // per-wave packed scan totals
   __shared__ uint8_t s_order[4][64];      // per wave: active-packet rank -> lane
@@ -416,11 +390,11 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
   // (A register-staged loop compiled to load / vmcnt(0) / ds_write per 16 B: ~12 serialised
   // HBM round trips per block.)
   {
-    const int64_t np = seg_length(seg_len, seg) / kPkt;
+    const int64_t np = seg_length(seg_len, seg) / kPacket;
     const int64_t first = blk * kTsThreads;
     const int64_t npk = np - first < kTsThreads ? (np - first > 0 ? np - first : 0) : kTsThreads;
-    const int nvec = static_cast<int>((npk * kPkt + 15) / 16);
-    const uint8_t* g = buf + seg_off[seg] + first * kPkt;
+    const int nvec = static_cast<int>((npk * kPacket + 15) / 16);
+    const uint8_t* g = buf + seg_off[seg] + first * kPacket;
     const int last = nvec - 1;
 #pragma unroll
     for (int k = 0; k < kStageVec; ++k) {
@@ -479,7 +453,7 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
     pes_idx = static_cast<int64_t>(pre[2 * c + 1]) + inc_p - pes_flag;
     if (pes_flag) {
       const int64_t tot_pes = tot[2 * c + 1];
-      int64_t* infc = info + static_cast<int64_t>(seg) * kInfo;
+      int64_t* infc = info + static_cast<int64_t>(seg) * kInfoWords;
       if (pes_idx == 0) infc[kFirstPts + c] = pts_dts[2 * gpk];
       if (pes_idx == tot_pes - 1) infc[kLastPts + c] = pts_dts[2 * gpk];
       if (pes_idx < max_pes) {
@@ -523,7 +497,7 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
     const int jps = __shfl(ps, j);
     const int jdst = __shfl(dst32, j);
     const int jlen = valid ? jlen_all : 0;
-    const int s = (wave * 64 + j) * kPkt + jps;  // LDS byte offset of the payload
+    const int s = (wave * 64 + j) * kPacket + jps;  // LDS byte offset of the payload
     uint8_t* d = ebase + jdst;
     const int mis = static_cast<int>((4 - (reinterpret_cast<uintptr_t>(d) & 3)) & 3);
     const int head = mis < jlen ? mis : jlen;
@@ -553,32 +527,30 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
 }
 
 
-hipError_t launch_ts_demux(const uint8_t* buf, const int64_t* seg_off, const int64_t* seg_len,
-                           const int64_t* blk_prefix, int nseg, int64_t total_blocks, uint32_t* meta,
-                           int64_t* pts_dts, int32_t* aux, uint8_t* es, const int64_t* es_off, int64_t* pes,
-                           int64_t max_pes, int64_t* info, hipStream_t stream, const void* hdr_rec,
-                           const int64_t* hdr_off) {
-  if (nseg <= 0) return hipSuccess;
-  // aux (int32): [blk_sums: blocks x 6 | blk_pre: blocks x 6 | seg_tot: nseg x 6 | spare: nseg]
-  int32_t* blk_sums = aux;
-  int32_t* blk_pre = blk_sums + total_blocks * 2 * kClasses;
-  int32_t* seg_tot = blk_pre + total_blocks * 2 * kClasses;
-  hipLaunchKernelGGL(ts_psi_kernel, dim3(nseg), dim3(64), 0, stream, buf, seg_off, seg_len, info, pes, max_pes);
+hipError_t launch_ts_demux(const TsDemuxArgs& a) {
+  if (a.nseg <= 0) return hipSuccess;
+  const DemuxAux part = demux_aux(a.total_blocks, a.nseg);
+  int32_t* blk_sums = a.aux + part.blk_sums;
+  int32_t* blk_pre = a.aux + part.blk_pre;
+  int32_t* seg_tot = a.aux + part.seg_tot;
+  hipLaunchKernelGGL(ts_psi_kernel, dim3(a.nseg), dim3(64), 0, a.stream, a.buf, a.seg_off, a.seg_len, a.info, a.pes,
+                     a.max_pes);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || total_blocks <= 0) return e;
-  hipLaunchKernelGGL(ts_scan_kernel, dim3(static_cast<unsigned>((total_blocks + kScanBlocks - 1) / kScanBlocks)),
-                     dim3(kTsThreads), 0, stream, buf, seg_off, seg_len, blk_prefix, nseg, total_blocks, info, meta,
-                     pts_dts, blk_sums,
-                     reinterpret_cast<const uint4*>(hdr_rec), hdr_rec != nullptr ? hdr_off : nullptr);
+  if (e != hipSuccess || a.total_blocks <= 0) return e;
+  const bool hdr = a.hdr.rec != nullptr;
+  hipLaunchKernelGGL(ts_scan_kernel, dim3(static_cast<unsigned>((a.total_blocks + kScanBlocks - 1) / kScanBlocks)),
+                     dim3(kTsThreads), 0, a.stream, a.buf, a.seg_off, a.seg_len, a.blk_prefix, a.nseg, a.total_blocks,
+                     a.info, a.meta, a.pts_dts, blk_sums, reinterpret_cast<const uint4*>(a.hdr.rec),
+                     hdr ? a.hdr.off : nullptr);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ts_prefix_kernel, dim3(nseg), dim3(64), 0, stream, blk_prefix, blk_sums, blk_pre, seg_tot, info,
-                     max_pes);
+  hipLaunchKernelGGL(ts_prefix_kernel, dim3(a.nseg), dim3(64), 0, a.stream, a.blk_prefix, blk_sums, blk_pre, seg_tot,
+                     a.info, a.max_pes);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ts_gather_kernel, dim3(static_cast<unsigned>(total_blocks)), dim3(kTsThreads), 0, stream, buf,
-                     seg_off, seg_len, blk_prefix, nseg, meta, pts_dts, blk_pre, seg_tot, es, es_off, pes, max_pes,
-                     info);
+  hipLaunchKernelGGL(ts_gather_kernel, dim3(static_cast<unsigned>(a.total_blocks)), dim3(kTsThreads), 0, a.stream,
+                     a.buf, a.seg_off, a.seg_len, a.blk_prefix, a.nseg, a.meta, a.pts_dts, blk_pre, seg_tot, a.es,
+                     a.es_off, a.pes, a.max_pes, a.info);
   return hipGetLastError();
 }
 

@@ -302,6 +302,35 @@ PYBIND11_MODULE(_runtime, m) {
   m.def("mpeg_crc32", [](Arr<uint8_t> data) { return ts::mpeg_crc32(data.data(), static_cast<size_t>(data.size())); });
   m.attr("TS_INFO_WORDS") = ts::kInfoWords;
   m.attr("TS_CLASSES") = ts::kClasses;
+  m.attr("TS_PACKET") = ts::kPacket;
+  {  // the info row and status bits by name (shared/layout.hpp)
+    py::dict d, st;
+    d["status"] = int(ts::kStatus);
+    d["pmt_pid"] = int(ts::kPmtPid);
+    d["n_packets"] = int(ts::kNumPackets);
+    const char* cls[ts::kClasses] = {"video", "audio", "id3"};
+    for (int c = 0; c < ts::kClasses; ++c) {  // the per-class families: base slot + class
+      const std::string n = cls[c];
+      d[py::str(n + "_pid")] = ts::kVideoPid + c;
+      d[py::str(n + "_bytes")] = ts::kVideoBytes + c;
+      d[py::str("n_" + n + "_pes")] = ts::kNumVideoPes + c;
+      d[py::str(n + "_first_pts")] = ts::kFirstPts + c;
+      d[py::str(n + "_last_pts")] = ts::kLastPts + c;
+    }
+    d["video_type"] = int(ts::kVideoType);
+    d["audio_type"] = int(ts::kAudioType);
+    d["payload_bytes"] = int(ts::kPayloadBytes);
+    d["audio_es_offset"] = int(ts::kAudioEsOffset);
+    d["id3_es_offset"] = int(ts::kId3EsOffset);
+    m.attr("TS_INFO") = d;
+    st["bad_sync"] = int64_t(ts::kBadSync);
+    st["no_pat"] = int64_t(ts::kNoPat);
+    st["no_pmt"] = int64_t(ts::kNoPmt);
+    st["pes_overflow"] = int64_t(ts::kPesOverflow);
+    st["pes_header_error"] = int64_t(ts::kPesHeaderError);
+    st["bad_length"] = int64_t(ts::kBadLength);
+    m.attr("TS_STATUS") = st;
+  }
   // Batched CPU sample index with the device kernels' layout (docs/ESINDEX.md).
   //   es: flat uint8 (segment b's ES at es_off[b], cap[b] bytes readable); info / pes: demux_batch's
   //   nal: int32[B, max_nal, 4]; au: int32[B, max_pes, 4]; aframes: int32[B, max_pes, 2]; sinfo: int64[B, 8]
@@ -336,6 +365,27 @@ PYBIND11_MODULE(_runtime, m) {
   });
   m.attr("ES_SINFO_WORDS") = es::kSinfoWords;
   m.attr("ES_DEFAULT_MAX_NAL") = es::kDefaultMaxNal;
+  {
+    py::dict d, st, fl;
+    d["status"] = int(es::kStatus);
+    d["n_nal"] = int(es::kNumNal);
+    d["n_au"] = int(es::kNumAu);
+    d["n_keyframe_aus"] = int(es::kNumKeyframeAus);
+    d["first_keyframe_au"] = int(es::kFirstKeyframeAu);
+    d["n_adts_frames"] = int(es::kNumAdtsFrames);
+    d["audio_sample_rate"] = int(es::kAudioSampleRate);
+    d["audio_channels"] = int(es::kAudioChannels);
+    m.attr("ES_SINFO") = d;
+    st["nal_overflow"] = int64_t(es::kNalOverflow);
+    st["adts_error"] = int64_t(es::kAdtsError);
+    st["unsupported_video"] = int64_t(es::kUnsupportedVideo);
+    m.attr("ES_STATUS") = st;
+    fl["keyframe"] = int(es::kAuKeyframe);
+    fl["sps"] = int(es::kAuSps);
+    fl["pps"] = int(es::kAuPps);
+    fl["aud"] = int(es::kAuAud);
+    m.attr("ES_AU_FLAGS") = fl;
+  }
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

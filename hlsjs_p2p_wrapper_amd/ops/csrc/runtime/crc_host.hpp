@@ -17,15 +17,13 @@
 #include <cstdint>
 #include <vector>
 
+#include "layout.hpp"
+
 namespace hlsp2p {
 namespace crc {
 
 constexpr uint32_t kPoly = 0xEDB88320u;
-constexpr int kGroupBytes = 256;      // data bytes per MFMA output row
-constexpr int kNumP = 40;             // P_b tables, b = 0..39  (shift up to 2^39 bytes)
-constexpr int kNumQ = 12;             // Q_b tables, b = 0..11  (undo pad < 4096 bytes)
-constexpr int kChunkBytes = 4096;     // data bytes per fused decrypt + CRC chunk (aes_cbc.hip)
-constexpr int kSliceWords = 4 * 256;  // one byte-slice table set (4 KiB)
+// group / tile / chunk geometry and the table counts: shared/layout.hpp
 
 uint32_t crc32(const uint8_t* data, size_t n, uint32_t crc = 0);  // zlib-compatible update
 
@@ -60,9 +58,6 @@ std::vector<uint32_t> shift_tables();
 //    A fragments [s = 0..31][lane][16 bytes] (row = CRC bit, k half hh reads mask dword
 //    s + 32 hh of the chunk).
 // Returns the decrypt fragments followed by the fold fragments.
-constexpr int kFusedAesSteps = 8;
-constexpr int kFusedFoldSteps = 32;
-constexpr int kFusedMaskDwords = 64;  // mask dwords per 4096-byte chunk
 std::vector<uint8_t> mfma_chunk_weights_fp4();
 // Raw (zero-init) CRC of [FF FF FF FF 00 ...] of `nbytes` bytes: zlib's init value folded into
 // the first group's residue.

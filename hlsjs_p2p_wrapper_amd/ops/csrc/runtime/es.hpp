@@ -8,34 +8,12 @@
 #pragma once
 #include <cstdint>
 
+#include "layout.hpp"
+
 namespace hlsp2p {
 namespace es {
 
-constexpr int kSinfoWords = 8;
-constexpr int64_t kDefaultMaxNal = 2048;
-
-// sinfo[] layout (int64), identical on host and device
-enum Sinfo : int {
-  kStatus = 0,
-  kNumNal = 1,  // true total, also when the table overflowed
-  kNumAu = 2,
-  kNumKeyframeAus = 3,
-  kFirstKeyframeAu = 4,  // -1: none
-  kNumAdtsFrames = 5,
-  kAudioSampleRate = 6,
-  kAudioChannels = 7,
-};
-enum Status : int64_t {
-  kNalOverflow = 1,
-  kAdtsError = 2,
-  kUnsupportedVideo = 4,
-};
-enum AuFlags : int {
-  kAuKeyframe = 1,
-  kAuSps = 2,
-  kAuPps = 4,
-  kAuAud = 8,
-};
+// sinfo[] row layout, status bits and access-unit flags: shared/layout.hpp
 
 // Index one segment.
 //   es:      the segment's [video ES | audio ES | id3 ES]; `cap` bytes are readable

@@ -11,42 +11,12 @@
 #include <cstdint>
 #include <vector>
 
+#include "layout.hpp"
+
 namespace hlsp2p {
 namespace ts {
 
-constexpr int kPacket = 188;
-constexpr int kPsiScanPackets = 64;  // PAT/PMT must appear within the first 64 packets
-constexpr int kClasses = 3;          // 0 video, 1 audio, 2 id3/metadata
-constexpr int kInfoWords = 24;
-
-// info[] layout (int64), identical on host and device
-enum Info : int {
-  kStatus = 0,
-  kPmtPid = 1,
-  kVideoPid = 2,
-  kAudioPid = 3,
-  kId3Pid = 4,
-  kNumPackets = 5,
-  kVideoBytes = 6,   // kVideoBytes + class
-  kNumVideoPes = 9,  // kNumVideoPes + class
-  kVideoType = 12,
-  kAudioType = 13,
-  kPayloadBytes = 14,  // total ES bytes (video+audio+id3)
-  kFirstPts = 16,      // kFirstPts + class: PTS of the class's first PES (-1 if none)
-  kLastPts = 19,       // kLastPts + class: PTS of the class's last PES
-  kAudioEsOffset = 22,  // byte offset of the audio ES from the segment's ES start (video at 0)
-  kId3EsOffset = 23,    // byte offset of the id3 ES (the host and the split kernels pack
-                        // [video | audio | id3]; the fused kernel uses fixed per-class regions)
-};
-// status bits
-enum Status : int64_t {
-  kBadSync = 1,
-  kNoPat = 2,
-  kNoPmt = 4,
-  kPesOverflow = 8,
-  kPesHeaderError = 16,
-  kBadLength = 32,
-};
+// packet size, class count, info[] row layout and status bits: shared/layout.hpp
 
 struct MuxConfig {
   double duration = 4.0;

@@ -9,19 +9,10 @@ allocator, which records the stream use, so reuse is safe without a sync.
 """
 from __future__ import annotations
 
-from typing import Dict, List, Tuple
+from typing import Dict
 
 import numpy as np
 import torch
-
-_DT = {
-    np.dtype(np.int64): torch.int64,
-    np.dtype(np.int32): torch.int32,
-    np.dtype(np.uint8): torch.uint8,
-    np.dtype(np.int8): torch.int8,
-    np.dtype(np.float64): torch.float64,
-    np.dtype(np.uint32): torch.int32,
-}
 
 
 def check_ranges(op: str, what: str, offs: np.ndarray, lens: np.ndarray, numel: int) -> None:
@@ -48,27 +39,7 @@ def pack_to_device(arrays: Dict[str, np.ndarray], device: torch.device) -> Dict[
 
         idx = device.index if device.index is not None else torch.cuda.current_device()
         return dict(zip(arrays.keys(), _dev().pack_h2d(list(arrays.values()), idx)))
-    layout: List[Tuple[str, int, np.ndarray]] = []
-    off = 0
-    for name, a in arrays.items():
-        a = np.ascontiguousarray(a)
-        if a.dtype == np.uint32:
-            a = a.view(np.int32)
-        layout.append((name, off, a))
-        off += (a.nbytes + 15) & ~15
-    total = max(off, 16)
-    if device.type == "cpu":
-        out = {}
-        for name, _, a in layout:
-            out[name] = torch.from_numpy(a.copy())
-        return out
-    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-    hv = host.numpy()
-    for name, o, a in layout:
-        hv[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
-    dev = host.to(device, non_blocking=True)
-    out = {}
-    for name, o, a in layout:
-        t = dev[o:o + a.nbytes].view(_DT[a.dtype])
-        out[name] = t
-    return out
+    if device.type != "cpu":
+        raise ValueError(f"pack_to_device: unsupported device {device}")
+    host = {name: np.ascontiguousarray(a) for name, a in arrays.items()}
+    return {k: torch.from_numpy((a.view(np.int32) if a.dtype == np.uint32 else a).copy()) for k, a in host.items()}

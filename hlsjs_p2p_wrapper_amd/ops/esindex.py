@@ -89,7 +89,7 @@ def index_batch(res: DemuxResult, caps: Sequence[int], max_nal: int = DEFAULT_MA
     np.cumsum(tiles, out=tile_prefix[1:])
     total_tiles = int(tile_prefix[-1])
     d = pack_to_device({"eo": eo, "cap": cap, "tp": tile_prefix}, dev)
-    scratch = torch.empty(2 * total_tiles + B * (max_nal + 1), dtype=torch.int32, device=dev)
+    scratch = torch.empty(_dev().es_index_scratch_words(total_tiles, B, max_nal), dtype=torch.int32, device=dev)
     nal = torch.empty((B, max_nal, 4), dtype=torch.int32, device=dev)
     au = torch.empty((B, max_pes, 4), dtype=torch.int32, device=dev)
     aframes = torch.empty((B, max_pes, 2), dtype=torch.int32, device=dev)

@@ -86,7 +86,7 @@ def demux_batch(buf: torch.Tensor, offs: Sequence[int], lens: Union[Sequence[int
         return DemuxResult(torch.from_numpy(info), torch.from_numpy(pes), es, eo)
     if np.any(o % 16):
         raise ValueError("demux_batch: offsets must be 16-byte aligned on device")
-    blocks = ((cap + PACKET - 1) // PACKET + 255) // 256
+    blocks = _dev().ts_demux_blocks(cap)
     blk_prefix = np.zeros(B + 1, dtype=np.int64)
     np.cumsum(blocks, out=blk_prefix[1:])
     arrays = {"o": o, "bp": blk_prefix, "eo": eo}
@@ -95,10 +95,10 @@ def demux_batch(buf: torch.Tensor, offs: Sequence[int], lens: Union[Sequence[int
     d = pack_to_device(arrays, dev)
     n_dev = lens if isinstance(lens, torch.Tensor) else d["n"]
     total_blocks = int(blk_prefix[-1])
-    nb = max(1, total_blocks)
-    meta = torch.empty(nb * 256, dtype=torch.int32, device=dev)
-    pts_dts = torch.empty(nb * 256 * 2, dtype=torch.int64, device=dev)
-    blk_sums = torch.empty(nb * 12 + B * 7, dtype=torch.int32, device=dev)  # sums|prefixes|totals|counters
+    n_meta, n_pts, n_aux = _dev().ts_demux_workspace(max(1, total_blocks), B)
+    meta = torch.empty(n_meta, dtype=torch.int32, device=dev)
+    pts_dts = torch.empty(n_pts, dtype=torch.int64, device=dev)
+    blk_sums = torch.empty(n_aux, dtype=torch.int32, device=dev)
     info = torch.empty((B, INFO_WORDS), dtype=torch.int64, device=dev)
     pes = torch.empty((B, 3, max_pes, 3), dtype=torch.int64, device=dev)
     _dev().ts_demux(buf, d["o"], n_dev, d["bp"], total_blocks, meta, pts_dts, blk_sums, es, d["eo"], pes, max_pes, info)
