@@ -27,7 +27,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 RUNTIME_SRC = CSRC / "runtime"
 KERNEL_SRC = CSRC / "kernels"
-SHARED_SRC = CSRC / "shared"  # layouts and sizes both builds include (layout.hpp)
+SHARED_SRC = CSRC / "shared"  # layouts, sizes and byte rules both builds include (layout.hpp, grammar.hpp)
 REPO = HERE.parent.parent
 BUILD = REPO / "build" / "native"
 EXT_SUFFIX = sysconfig.get_config_var("EXT_SUFFIX") or ".so"

@@ -23,7 +23,10 @@
 //                         unit (NAL range, flags), then wave 0 counts the keyframe units and
 //                         walks the ADTS frames with a lane per audio PES.
 // No workgroup waits for another one: the order comes from the launches alone.
+// The codec, NAL-type and ADTS byte rules are shared/grammar.hpp (namespace es), the same
+// functions runtime/es.cpp calls.
 #include "common.h"
+#include "grammar.hpp"
 #include "launch.h"
 
 namespace hlsp2p {
@@ -35,15 +38,9 @@ constexpr int kEsIterBytes = kEsThreads * 16;
 constexpr int kEsTile = kEsIters * kEsIterBytes;  // 16 KiB
 int es_index_tile_bytes() { return kEsTile; }
 
-__device__ __forceinline__ int64_t es_clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-__device__ __forceinline__ bool es_video_supported(const int64_t* __restrict__ inf) {
-  return inf[ts::kVideoType] == 0x1B || inf[ts::kVideoType] == 0x24;
-}
-
 // bytes of video ES to index: 0 for an unsupported codec, never beyond the host cap
 __device__ __forceinline__ int64_t es_video_len(const int64_t* __restrict__ inf, int64_t cap) {
-  return es_video_supported(inf) ? es_clamp(inf[ts::kVideoBytes], 0, cap) : 0;
+  return es::video_supported(inf[ts::kVideoType]) ? clamp(inf[ts::kVideoBytes], 0, cap) : 0;
 }
 
 // 0x80 in every byte of x that is zero (exact: no carry leaves a byte)
@@ -139,10 +136,10 @@ __global__ __launch_bounds__(64) void es_prefix_kernel(const int64_t* __restrict
   if (lane == 0) {  // carry is wave-uniform
     int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
     const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
-    int64_t status = es_video_supported(inf) ? 0 : es::kUnsupportedVideo;
+    int64_t status = es::video_supported(inf[ts::kVideoType]) ? 0 : es::kUnsupportedVideo;
     if (static_cast<int64_t>(carry) > max_nal) status |= es::kNalOverflow;
-    si[0] = status;
-    si[1] = carry;
+    si[es::kStatus] = status;
+    si[es::kNumNal] = carry;
   }
 }
 
@@ -190,15 +187,6 @@ __device__ __forceinline__ int es_first_nal_at(const int32_t* __restrict__ pos, 
   return lo;
 }
 
-__device__ __forceinline__ int es_adts_rate(int idx) {
-  switch (idx) {
-    case 0: return 96000; case 1: return 88200; case 2: return 64000; case 3: return 48000;
-    case 4: return 44100; case 5: return 32000; case 6: return 24000; case 7: return 22050;
-    case 8: return 16000; case 9: return 12000; case 10: return 11025; case 11: return 8000;
-    case 12: return 7350; default: return 0;
-  }
-}
-
 __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
     const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
     const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
@@ -211,10 +199,10 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   const int64_t room = cap[seg];
   const uint8_t* V = es + es_off[seg];
   const int64_t n = es_video_len(inf, room);
-  const int64_t n_nal = si[1];
+  const int64_t n_nal = si[es::kNumNal];
   const int nn = static_cast<int>(n_nal < max_nal ? n_nal : max_nal);
-  const bool hevc = inf[ts::kVideoType] == 0x24;
-  const int m = es_video_supported(inf) ? static_cast<int>(es_clamp(inf[ts::kNumVideoPes], 0, max_pes)) : 0;
+  const bool hevc = es::is_hevc(inf[ts::kVideoType]);
+  const int m = es::video_supported(inf[ts::kVideoType]) ? static_cast<int>(clamp(inf[ts::kNumVideoPes], 0, max_pes)) : 0;
   const int64_t* vp = pes + static_cast<int64_t>(seg) * 3 * max_pes * 3;  // class 0
   const int64_t* ap = vp + max_pes * 3;                                      // class 1
   const int32_t* pos = pos_all + static_cast<int64_t>(seg) * (max_nal + 1);
@@ -241,7 +229,7 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
       }
       r0 = static_cast<int32_t>(s);
       r1 = static_cast<int32_t>(e - s);
-      r2 = e == s ? -1 : hevc ? (hb >> 1) & 0x3f : hb & 0x1f;
+      r2 = e == s ? -1 : es::nal_type(hevc, hb);
       r3 = a_lo - 1;
     }
     nal[4 * k] = r0;
@@ -260,16 +248,7 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
       const int first = es_first_nal_at(pos, nn, o);
       const int end = a + 1 < m ? es_first_nal_at(pos, nn, o_next) : nn;
       int flags = 0;
-      for (int k = first; k < end; ++k) {
-        const int ty = nal[4 * k + 2];
-        if (hevc) {
-          flags |= (ty >= 16 && ty <= 21 ? es::kAuKeyframe : 0) | (ty == 33 ? es::kAuSps : 0) |
-                   (ty == 34 ? es::kAuPps : 0) | (ty == 35 ? es::kAuAud : 0);
-        } else {
-          flags |= (ty == 5 ? es::kAuKeyframe : 0) | (ty == 7 ? es::kAuSps : 0) | (ty == 8 ? es::kAuPps : 0) |
-                   (ty == 9 ? es::kAuAud : 0);
-        }
-      }
+      for (int k = first; k < end; ++k) flags |= es::nal_flags(hevc, nal[4 * k + 2]);
       r1 = end > first ? end - first : 0;
       r0 = r1 > 0 ? first : -1;
       r2 = flags;
@@ -292,39 +271,20 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
       if (a < first_key) first_key = a;
     }
   }
-  const bool adts = inf[ts::kAudioType] == 0x0F;
-  const int64_t a_off = es_clamp(inf[ts::kAudioEsOffset], 0, room);
-  const int64_t a_len = es_clamp(inf[ts::kAudioBytes], 0, room - a_off);
+  const int64_t a_off = clamp(inf[ts::kAudioEsOffset], 0, room);
+  const int64_t a_len = clamp(inf[ts::kAudioBytes], 0, room - a_off);
   const uint8_t* A = V + a_off;
-  const int ma = adts ? static_cast<int>(es_clamp(inf[ts::kNumAudioPes], 0, max_pes)) : 0;
+  const int ma = es::is_adts(inf[ts::kAudioType]) ? static_cast<int>(clamp(inf[ts::kNumAudioPes], 0, max_pes)) : 0;
   int n_frames = 0, err = 0, rate = 0, chans = 0;
   for (int64_t k = lane; k < max_pes; k += 64) {
     int32_t frames = -1, used = -1;
     if (k < ma) {
-      const int64_t start = es_clamp(ap[3 * k], 0, a_len);
-      const int64_t end = k + 1 < ma ? es_clamp(ap[3 * (k + 1)], start, a_len) : a_len;
-      int64_t q = start;
-      frames = 0;
-      while (q != end) {
-        if (q + 7 > end || A[q] != 0xFF || (A[q + 1] & 0xF6) != 0xF0) {
-          err = 1;
-          break;
-        }
-        const int64_t len = (static_cast<int64_t>(A[q + 3] & 3) << 11) | (static_cast<int64_t>(A[q + 4]) << 3) |
-                            (A[q + 5] >> 5);
-        const int hdr = (A[q + 1] & 1) ? 7 : 9;
-        if (len < hdr || q + len > end) {
-          err = 1;
-          break;
-        }
-        if (k == 0 && frames == 0) {
-          rate = es_adts_rate((A[q + 2] >> 2) & 15);
-          chans = ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6);
-        }
-        ++frames;
-        q += len;
-      }
-      used = static_cast<int32_t>(q - start);
+      const int64_t start = clamp(ap[3 * k], 0, a_len);
+      const int64_t end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
+      const es::AdtsWalk w = es::adts_walk(A, start, end, k == 0, rate, chans);
+      frames = w.frames;
+      used = w.used;
+      err |= w.error;
       n_frames += frames;
     }
     af[2 * k] = frames;
@@ -338,13 +298,13 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
     first_key = other < first_key ? other : first_key;
   }
   if (lane == 0) {  // rate / chans: lane 0 walked audio PES 0
-    si[0] |= any_err ? es::kAdtsError : 0;
-    si[2] = m;
-    si[3] = n_key;
-    si[4] = n_key > 0 ? first_key : -1;
-    si[5] = n_frames;
-    si[6] = rate;
-    si[7] = chans;
+    si[es::kStatus] |= any_err ? es::kAdtsError : 0;
+    si[es::kNumAu] = m;
+    si[es::kNumKeyframeAus] = n_key;
+    si[es::kFirstKeyframeAu] = n_key > 0 ? first_key : -1;
+    si[es::kNumAdtsFrames] = n_frames;
+    si[es::kAudioSampleRate] = rate;
+    si[es::kAudioChannels] = chans;
   }
 }
 

@@ -1,6 +1,10 @@
 // MPEG-TS demux of a batch of decrypted segments — CDNA4 / gfx950.
 //
-// Output contract (identical to the CPU oracle runtime/ts.cpp demux_segment):
+// The PSI and per-packet byte rules are shared/grammar.hpp (ts::parse_psi, ts::parse_packet), the
+// same functions the CPU oracle runtime/ts.cpp demux_segment calls; this file holds the loads,
+// the sums and the stores around them.
+//
+// Output contract (identical to the CPU oracle):
 //   es:   per segment, [video ES | audio ES | id3 ES] written at es_off[seg]
 //   pes:  int64[seg][3 classes][max_pes][3] = (ES byte offset, PTS, DTS)  (-1 = absent)
 //   info: int64[seg][16] (status bits, PIDs, packet count, per-class bytes / PES counts)
@@ -19,12 +23,13 @@
 //                          iteration with dword-aligned stores (v_alignbyte funnel for the
 //                          unaligned LDS source).
 #include "common.h"
+#include "grammar.hpp"
 #include "launch.h"
 
 namespace hlsp2p {
 namespace dev {
 
-using namespace ts;  // info slots, status bits, packet / block geometry (shared/layout.hpp)
+using namespace ts;  // info slots, status bits, geometry (shared/layout.hpp), byte rules (shared/grammar.hpp)
 
 constexpr int kTsThreads = 256;
 static_assert(kTsThreads == kBlockPackets, "a demux block is one packet per lane of the scan / gather workgroup");
@@ -48,72 +53,15 @@ __global__ __launch_bounds__(64) void ts_psi_kernel(const uint8_t* __restrict__ 
   const int64_t n = raw_len < 0 ? 0 : raw_len;
   const uint8_t* d = buf + seg_off[seg];
   const int64_t np = n / kPacket;
-  int64_t status = (raw_len < 0 || n % kPacket) ? kBadLength : 0;
-  int pmt_pid = -1, vpid = -1, apid = -1, ipid = -1, vtype = 0, atype = 0;
-  const int64_t scan = np < kPsiScanPackets ? np : kPsiScanPackets;
-  for (int64_t i = 0; i < scan && pmt_pid < 0; ++i) {
-    const uint8_t* p = d + i * kPacket;
-    if (p[0] != 0x47) continue;
-    const int pid = ((p[1] & 0x1f) << 8) | p[2];
-    if (pid != 0 || !(p[1] & 0x40)) continue;
-    const int afc = (p[3] >> 4) & 3;
-    int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPacket) continue;
-    ps += 1 + p[ps];
-    if (ps + 8 > kPacket || p[ps] != 0x00) continue;
-    const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
-    for (int q = ps + 8; q + 4 <= end; q += 4) {
-      const int prog = (p[q] << 8) | p[q + 1];
-      if (prog != 0) {
-        pmt_pid = ((p[q + 2] & 0x1f) << 8) | p[q + 3];
-        break;
-      }
-    }
-  }
-  if (pmt_pid < 0) status |= kNoPat;
-  bool pmt_found = false;
-  for (int64_t i = 0; i < scan && pmt_pid >= 0 && !pmt_found; ++i) {
-    const uint8_t* p = d + i * kPacket;
-    if (p[0] != 0x47) continue;
-    const int pid = ((p[1] & 0x1f) << 8) | p[2];
-    if (pid != pmt_pid || !(p[1] & 0x40)) continue;
-    const int afc = (p[3] >> 4) & 3;
-    int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPacket) continue;
-    ps += 1 + p[ps];
-    if (ps + 12 > kPacket || p[ps] != 0x02) continue;
-    pmt_found = true;
-    const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
-    const int pil = ((p[ps + 10] & 0x0f) << 8) | p[ps + 11];
-    for (int q = ps + 12 + pil; q + 5 <= end;) {
-      const int type = p[q];
-      const int epid = ((p[q + 1] & 0x1f) << 8) | p[q + 2];
-      const int eil = ((p[q + 3] & 0x0f) << 8) | p[q + 4];
-      if ((type == 0x1B || type == 0x24) && vpid < 0) {
-        vpid = epid;
-        vtype = type;
-      } else if ((type == 0x0F || type == 0x03 || type == 0x04) && apid < 0) {
-        apid = epid;
-        atype = type;
-      } else if (type == 0x15 && ipid < 0) {
-        ipid = epid;
-      }
-      q += 5 + eil;
-    }
-  }
-  if (pmt_pid >= 0 && !pmt_found) status |= kNoPmt;
+  const Psi psi = parse_psi(d, np);
   for (int k = 0; k < kInfoWords; ++k) inf[k] = 0;
-  inf[kStatus] = status;
-  inf[kPmtPid] = pmt_pid;
-  inf[kVideoPid] = vpid;
-  inf[kVideoPid + 1] = apid;
-  inf[kVideoPid + 2] = ipid;
+  inf[kStatus] = psi.status | ((raw_len < 0 || n % kPacket) ? kBadLength : 0);
+  inf[kPmtPid] = psi.pmt_pid;
   inf[kNumPackets] = np;
-  inf[kVideoType] = vtype;
-  inf[kAudioType] = atype;
+  inf[kVideoType] = psi.video_type;
+  inf[kAudioType] = psi.audio_type;
   for (int c = 0; c < kClasses; ++c) {
+    inf[kVideoPid + c] = psi.pid[c];
     inf[kFirstPts + c] = -1;
     inf[kLastPts + c] = -1;
   }
@@ -207,11 +155,8 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
 #pragma unroll
   for (int u = 0; u < kScanBlocks; ++u) {
     b4v[u] = 0;
-    if (pks[u] >= 0) {
-      const uint32_t hdr = pkt[u].hdr;
-      const int afc = (hdr >> 28) & 3;
-      b4v[u] = pkt[u].b4 >= 0 ? pkt[u].b4 : ((afc & 2) ? static_cast<int>(pp[u][4]) : 0);
-    }
+    if (pks[u] >= 0)
+      b4v[u] = pkt[u].b4 >= 0 ? pkt[u].b4 : (has_adaptation(pkt[u].hdr >> 24) ? static_cast<int>(pp[u][4]) : 0);
   }
   uint32_t hw[kScanBlocks][5];
 #pragma unroll
@@ -220,9 +165,8 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
     for (int k = 0; k < 5; ++k) hw[u][k] = 0;
     if (pks[u] >= 0) {
       const uint32_t hdr = pkt[u].hdr;
-      const int afc = (hdr >> 28) & 3, b1 = (hdr >> 8) & 0xff;
-      const int s0 = 4 + ((afc & 2) ? 1 + b4v[u] : 0);
-      if ((hdr & 0xff) == 0x47 && (b1 & 0x40) && (afc & 1) && s0 + 9 <= kPacket) {
+      const int s0 = pes_header_start(hdr & 0xff, (hdr >> 8) & 0xff, hdr >> 24, b4v[u]);
+      if (s0 >= 0) {
         const uint8_t* h = pp[u] + s0;
         const uint32_t* w = reinterpret_cast<const uint32_t*>(reinterpret_cast<uintptr_t>(h) & ~uintptr_t(3));
         const uint32_t* wend = reinterpret_cast<const uint32_t*>(pp[u] + kPacket);  // packets are 4-byte aligned
@@ -244,59 +188,25 @@ __global__ __launch_bounds__(kTsThreads) void ts_scan_kernel(
       cur = segs[u];
       const int64_t* inf = info + static_cast<int64_t>(cur) * kInfoWords;
       cpid0 = static_cast<int>(inf[kVideoPid]);
-      cpid1 = static_cast<int>(inf[kVideoPid + 1]);
-      cpid2 = static_cast<int>(inf[kVideoPid + 2]);
+      cpid1 = static_cast<int>(inf[kAudioPid]);
+      cpid2 = static_cast<int>(inf[kId3Pid]);
     }
     const int64_t gpk = (gb0 + u) * kTsThreads + tid;  // global packet slot (meta index)
-    int c = 3, ps = 0, len = 0, pes = 0;
+    int c = kClasses, ps = 0, len = 0, pes = 0;
     int err = 0;
     if (pks[u] >= 0) {
       const uint32_t hdr = pkt[u].hdr;
-      const int sync = hdr & 0xff;
-      const int b1 = (hdr >> 8) & 0xff, b2 = (hdr >> 16) & 0xff, b3 = hdr >> 24;
-      if (sync != 0x47) {
-        err |= static_cast<int>(kBadSync);
-      } else {
-        const int pid = ((b1 & 0x1f) << 8) | b2;
-        const int cls = (cpid0 >= 0 && pid == cpid0) ? 0 : (cpid1 >= 0 && pid == cpid1) ? 1 : (cpid2 >= 0 && pid == cpid2) ? 2 : 3;
-        const int afc = (b3 >> 4) & 3;
-        if (cls < 3 && (afc & 1)) {
-          int s = 4 + ((afc & 2) ? 1 + b4v[u] : 0);
-          if (s > kPacket) {
-            err |= static_cast<int>(kBadLength);
-          } else {
-            int l = kPacket - s;
-            bool ok = true;
-            if (b1 & 0x40) {
-#define HB(i) static_cast<int>((hw[u][(i) >> 2] >> (8 * ((i) & 3))) & 0xffu)
-              if (l < 9 || HB(0) != 0 || HB(1) != 0 || HB(2) != 1 || 9 + HB(8) > l) {
-                err |= static_cast<int>(kPesHeaderError);
-                ok = false;
-              } else {
-                const int f7 = HB(7);
-                const int64_t pts = ((f7 & 0x80) && l >= 14)
-                                        ? (int64_t((HB(9) >> 1) & 0x07) << 30) | (int64_t(HB(10)) << 22) |
-                                              (int64_t(HB(11) >> 1) << 15) | (int64_t(HB(12)) << 7) | int64_t(HB(13) >> 1)
-                                        : -1;
-                const int64_t dts = ((f7 & 0xC0) == 0xC0 && l >= 19)
-                                        ? (int64_t((HB(14) >> 1) & 0x07) << 30) | (int64_t(HB(15)) << 22) |
-                                              (int64_t(HB(16) >> 1) << 15) | (int64_t(HB(17)) << 7) | int64_t(HB(18) >> 1)
-                                        : -1;
-                pts_dts[2 * gpk] = pts;
-                pts_dts[2 * gpk + 1] = dts;
-                pes = 1;
-                s += 9 + HB(8);
-                l -= 9 + HB(8);
-              }
-#undef HB
-            }
-            if (ok) {
-              c = cls;
-              ps = s;
-              len = l;
-            }
-          }
-        }
+      const uint32_t* w = hw[u];  // the realigned PES header dwords
+      const Packet r = parse_packet(hdr & 0xff, (hdr >> 8) & 0xff, (hdr >> 16) & 0xff, hdr >> 24, b4v[u], cpid0, cpid1,
+                                    cpid2, [w](int i) { return static_cast<int>((w[i >> 2] >> (8 * (i & 3))) & 0xffu); });
+      c = r.cls;
+      ps = r.start;
+      len = r.len;
+      pes = r.pes;
+      err = r.err;
+      if (pes) {
+        pts_dts[2 * gpk] = r.pts;
+        pts_dts[2 * gpk + 1] = r.dts;
       }
     }
     meta[gpk] = pack_meta(c, ps, len, pes);

@@ -1,28 +1,15 @@
+// Host sample index: the serial loops that fill the rows.  The codec, NAL-type and ADTS byte
+// rules are shared/grammar.hpp (namespace es), the same functions kernels/es_index.hip calls.
 #include "es.hpp"
 
 #include <algorithm>
 #include <vector>
 
+#include "grammar.hpp"
 #include "ts.hpp"
 
 namespace hlsp2p {
 namespace es {
-
-namespace {
-
-int64_t clamp(int64_t v, int64_t lo, int64_t hi) { return std::min(std::max(v, lo), hi); }
-
-const int kAdtsRates[13] = {96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350};
-
-int nal_flags(bool hevc, int type) {
-  if (hevc)
-    return (type >= 16 && type <= 21 ? kAuKeyframe : 0) | (type == 33 ? kAuSps : 0) | (type == 34 ? kAuPps : 0) |
-           (type == 35 ? kAuAud : 0);
-  return (type == 5 ? kAuKeyframe : 0) | (type == 7 ? kAuSps : 0) | (type == 8 ? kAuPps : 0) |
-         (type == 9 ? kAuAud : 0);
-}
-
-}  // namespace
 
 void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const int64_t* pes, int64_t max_pes,
                    int64_t max_nal, int32_t* nal, int32_t* au, int32_t* aframes, int64_t* sinfo) {
@@ -33,8 +20,8 @@ void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const in
   sinfo[kFirstKeyframeAu] = -1;
   cap = std::max<int64_t>(cap, 0);
   const int64_t vtype = info[ts::kVideoType];
-  const bool supported = vtype == 0x1B || vtype == 0x24;
-  const bool hevc = vtype == 0x24;
+  const bool supported = video_supported(vtype);
+  const bool hevc = is_hevc(vtype);
   int64_t status = supported ? 0 : kUnsupportedVideo;
   const uint8_t* V = es;
   const int64_t n = supported ? clamp(info[ts::kVideoBytes], 0, cap) : 0;
@@ -69,7 +56,7 @@ void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const in
     while (a + 1 < m && vp[3 * (a + 1)] <= s) ++a;
     nal[4 * k] = static_cast<int32_t>(s);
     nal[4 * k + 1] = static_cast<int32_t>(e - s);
-    nal[4 * k + 2] = e == s ? -1 : hevc ? (V[s] >> 1) & 0x3f : V[s] & 0x1f;
+    nal[4 * k + 2] = e == s ? -1 : nal_type(hevc, V[s]);
     nal[4 * k + 3] = static_cast<int32_t>(a);
   }
 
@@ -96,40 +83,22 @@ void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const in
   }
 
   // ---- ADTS frames, one walk per audio PES
-  int64_t n_frames = 0, rate = 0, chans = 0;
-  if (info[ts::kAudioType] == 0x0F) {
+  int64_t n_frames = 0;
+  int rate = 0, chans = 0;
+  if (is_adts(info[ts::kAudioType])) {
     const int64_t a_off = clamp(info[ts::kAudioEsOffset], 0, cap);
-    const int64_t a_len = clamp(info[ts::kVideoBytes + 1], 0, cap - a_off);
+    const int64_t a_len = clamp(info[ts::kAudioBytes], 0, cap - a_off);
     const uint8_t* A = es + a_off;
-    const int64_t ma = clamp(info[ts::kNumVideoPes + 1], 0, max_pes);
+    const int64_t ma = clamp(info[ts::kNumAudioPes], 0, max_pes);
     const int64_t* ap = pes + max_pes * 3;  // class 1
     for (int64_t k = 0; k < ma; ++k) {
       const int64_t start = clamp(ap[3 * k], 0, a_len);
       const int64_t end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
-      int64_t q = start;
-      int32_t frames = 0;
-      while (q != end) {
-        if (q + 7 > end || A[q] != 0xFF || (A[q + 1] & 0xF6) != 0xF0) {
-          status |= kAdtsError;
-          break;
-        }
-        const int64_t len = (int64_t(A[q + 3] & 3) << 11) | (int64_t(A[q + 4]) << 3) | (A[q + 5] >> 5);
-        const int64_t hdr = (A[q + 1] & 1) ? 7 : 9;
-        if (len < hdr || q + len > end) {
-          status |= kAdtsError;
-          break;
-        }
-        if (k == 0 && frames == 0) {
-          const int idx = (A[q + 2] >> 2) & 15;
-          rate = idx < 13 ? kAdtsRates[idx] : 0;
-          chans = ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6);
-        }
-        ++frames;
-        q += len;
-      }
-      aframes[2 * k] = frames;
-      aframes[2 * k + 1] = static_cast<int32_t>(q - start);
-      n_frames += frames;
+      const AdtsWalk w = adts_walk(A, start, end, k == 0, rate, chans);
+      if (w.error) status |= kAdtsError;
+      aframes[2 * k] = w.frames;
+      aframes[2 * k + 1] = w.used;
+      n_frames += w.frames;
     }
   }
 

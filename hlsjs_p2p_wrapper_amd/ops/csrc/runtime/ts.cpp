@@ -1,8 +1,13 @@
+// Synthetic muxer (mux_segment) and the host demux oracle (demux_segment).  The demux is the
+// serial two-pass loop around shared/grammar.hpp (ts::parse_psi, ts::parse_packet), the same byte
+// rules kernels/ts_demux.hip calls; only the muxer's writers spell TS bytes out here.
 #include "ts.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+
+#include "grammar.hpp"
 
 namespace hlsp2p {
 namespace ts {
@@ -186,11 +191,6 @@ std::vector<uint8_t> pmt_section(bool with_id3) {
   return s;
 }
 
-inline int64_t read_pts(const uint8_t* p) {
-  return (int64_t((p[0] >> 1) & 0x07) << 30) | (int64_t(p[1]) << 22) | (int64_t(p[2] >> 1) << 15) |
-         (int64_t(p[3]) << 7) | int64_t(p[4] >> 1);
-}
-
 }  // namespace
 
 uint32_t mpeg_crc32(const uint8_t* p, size_t n) {
@@ -303,60 +303,13 @@ std::vector<uint8_t> mux_segment(const MuxConfig& cfg, MuxStats* stats) {
 void demux_segment(const uint8_t* data, int64_t n, uint8_t* es_out, int64_t* pes_out, int64_t max_pes, int64_t* info) {
   std::fill(info, info + kInfoWords, 0);
   for (int64_t i = 0; i < int64_t(kClasses) * max_pes * 3; ++i) pes_out[i] = -1;
-  int64_t status = 0;
   const int64_t np = n / kPacket;
-  if (n % kPacket) status |= kBadLength;
+  const Psi psi = parse_psi(data, np);
+  int64_t status = psi.status | (n % kPacket ? kBadLength : 0);
   info[kNumPackets] = np;
-  // --- PSI: PAT then PMT within the first kPsiScanPackets packets
-  int pmt_pid = -1, vpid = -1, apid = -1, ipid = -1, vtype = 0, atype = 0;
-  const int64_t scan = std::min<int64_t>(np, kPsiScanPackets);
-  for (int64_t i = 0; i < scan && pmt_pid < 0; ++i) {
-    const uint8_t* p = data + i * kPacket;
-    if (p[0] != 0x47) continue;
-    int pid = ((p[1] & 0x1f) << 8) | p[2];
-    if (pid != 0 || !(p[1] & 0x40)) continue;
-    int afc = (p[3] >> 4) & 3;
-    int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPacket) continue;
-    ps += 1 + p[ps];  // pointer field
-    if (ps + 8 > kPacket || p[ps] != 0x00) continue;
-    int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    int end = std::min(ps + 3 + slen - 4, kPacket);
-    for (int q = ps + 8; q + 4 <= end; q += 4) {
-      int prog = (p[q] << 8) | p[q + 1];
-      if (prog != 0) { pmt_pid = ((p[q + 2] & 0x1f) << 8) | p[q + 3]; break; }
-    }
-  }
-  if (pmt_pid < 0) status |= kNoPat;
-  bool pmt_found = false;
-  for (int64_t i = 0; i < scan && pmt_pid >= 0 && !pmt_found; ++i) {
-    const uint8_t* p = data + i * kPacket;
-    if (p[0] != 0x47) continue;
-    int pid = ((p[1] & 0x1f) << 8) | p[2];
-    if (pid != pmt_pid || !(p[1] & 0x40)) continue;
-    int afc = (p[3] >> 4) & 3;
-    int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-    if (!(afc & 1) || ps >= kPacket) continue;
-    ps += 1 + p[ps];
-    if (ps + 12 > kPacket || p[ps] != 0x02) continue;
-    pmt_found = true;
-    int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
-    int end = std::min(ps + 3 + slen - 4, kPacket);
-    int pil = ((p[ps + 10] & 0x0f) << 8) | p[ps + 11];
-    for (int q = ps + 12 + pil; q + 5 <= end;) {
-      int type = p[q];
-      int epid = ((p[q + 1] & 0x1f) << 8) | p[q + 2];
-      int eil = ((p[q + 3] & 0x0f) << 8) | p[q + 4];
-      if ((type == 0x1B || type == 0x24) && vpid < 0) { vpid = epid; vtype = type; }
-      else if ((type == 0x0F || type == 0x03 || type == 0x04) && apid < 0) { apid = epid; atype = type; }
-      else if (type == 0x15 && ipid < 0) { ipid = epid; }
-      q += 5 + eil;
-    }
-  }
-  if (pmt_pid >= 0 && !pmt_found) status |= kNoPmt;
-  info[kPmtPid] = pmt_pid; info[kVideoPid] = vpid; info[kAudioPid] = apid; info[kId3Pid] = ipid;
-  info[kVideoType] = vtype; info[kAudioType] = atype;
-  const int cls_pid[3] = {vpid, apid, ipid};
+  info[kPmtPid] = psi.pmt_pid;
+  for (int k = 0; k < kClasses; ++k) info[kVideoPid + k] = psi.pid[k];
+  info[kVideoType] = psi.video_type; info[kAudioType] = psi.audio_type;
   // --- two passes: sizes, then copy
   int64_t bytes[kClasses] = {0, 0, 0};
   int64_t npes[kClasses] = {0, 0, 0};
@@ -368,40 +321,25 @@ void demux_segment(const uint8_t* data, int64_t n, uint8_t* es_out, int64_t* pes
     int64_t cnt[kClasses] = {0, 0, 0};
     for (int64_t i = 0; i < np; ++i) {
       const uint8_t* p = data + i * kPacket;
-      if (p[0] != 0x47) { if (pass == 0) status |= kBadSync; continue; }
-      int pid = ((p[1] & 0x1f) << 8) | p[2];
-      int c = -1;
-      for (int k = 0; k < kClasses; ++k) if (cls_pid[k] >= 0 && pid == cls_pid[k]) { c = k; break; }
-      if (c < 0) continue;
-      int afc = (p[3] >> 4) & 3;
-      if (!(afc & 1)) continue;
-      int ps = 4 + ((afc & 2) ? 1 + p[4] : 0);
-      if (ps > kPacket) { if (pass == 0) status |= kBadLength; continue; }
-      int len = kPacket - ps;
-      if (p[1] & 0x40) {
-        const uint8_t* h = p + ps;
-        if (len < 9 || h[0] != 0 || h[1] != 0 || h[2] != 1 || 9 + h[8] > len) {
-          if (pass == 0) status |= kPesHeaderError;
-          continue;
-        }
-        int64_t pts = -1, dts = -1;
-        if ((h[7] & 0x80) && len >= 14) pts = read_pts(h + 9);
-        if ((h[7] & 0xC0) == 0xC0 && len >= 19) dts = read_pts(h + 14);
+      const int s0 = payload_start(p[3], p[4]);
+      const Packet pk = parse_packet(p[0], p[1], p[2], p[3], p[4], psi.pid[0], psi.pid[1], psi.pid[2],
+                                     [p, s0](int j) { return int(p[s0 + j]); });
+      if (pass == 0) status |= pk.err;
+      const int c = pk.cls;
+      if (c == kClasses) continue;
+      if (pk.pes) {
         if (pass == 1) {
-          if (cnt[c] == 0) first_pts[c] = pts;
-          last_pts[c] = pts;
+          if (cnt[c] == 0) first_pts[c] = pk.pts;
+          last_pts[c] = pk.pts;
           if (cnt[c] < max_pes) {
             int64_t* r = pes_out + (int64_t(c) * max_pes + cnt[c]) * 3;
-            r[0] = cur[c]; r[1] = pts; r[2] = dts;
+            r[0] = cur[c]; r[1] = pk.pts; r[2] = pk.dts;
           }
         }
         cnt[c] += 1;
-        int skip = 9 + h[8];
-        ps += skip;
-        len -= skip;
       }
-      if (pass == 1 && len > 0) std::memcpy(es_out + base[c] + cur[c], p + ps, len);
-      cur[c] += len;
+      if (pass == 1 && pk.len > 0) std::memcpy(es_out + base[c] + cur[c], p + pk.start, pk.len);
+      cur[c] += pk.len;
     }
     if (pass == 0) { for (int k = 0; k < kClasses; ++k) { bytes[k] = cur[k]; npes[k] = cnt[k]; } }
   }

@@ -1,0 +1,214 @@
+// The MPEG-TS / PES / NAL / ADTS byte rules that fill the rows of layout.hpp: the only definition
+// of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp) and by the gfx950 kernels
+// (kernels/ts_demux.hip, kernels/es_index.hip).  Plain inline functions over <cstdint> and
+// layout.hpp: no containers, no statics, no tables in memory.
+#pragma once
+#include <cstdint>
+
+#include "layout.hpp"
+
+#if defined(__HIPCC__)
+#define HLSP2P_RULE __host__ __device__ __forceinline__
+#else
+#define HLSP2P_RULE inline
+#endif
+
+namespace hlsp2p {
+
+HLSP2P_RULE int64_t clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+// ---------------------------------------------------------------- MPEG-TS demux
+namespace ts {
+constexpr int kSync = 0x47;
+constexpr int kPusi = 0x40;  // payload_unit_start_indicator, in header byte 1
+enum StreamType : int { kMpeg1Audio = 0x03, kMpeg2Audio = 0x04, kAdtsAac = 0x0F, kId3 = 0x15, kAvc = 0x1B, kHevc = 0x24 };
+
+HLSP2P_RULE int packet_pid(int b1, int b2) { return ((b1 & 0x1f) << 8) | b2; }
+HLSP2P_RULE bool has_adaptation(int b3) { return (b3 & 0x20) != 0; }
+HLSP2P_RULE bool has_payload(int b3) { return (b3 & 0x10) != 0; }
+// first payload byte; b4 (adaptation_field_length) counts only where has_adaptation(b3).
+// Past kPacket when the adaptation field is too long.
+HLSP2P_RULE int payload_start(int b3, int b4) { return 4 + (has_adaptation(b3) ? 1 + b4 : 0); }
+
+// Offset of the PES header in a packet that starts a payload unit and has room for the header's
+// 9 fixed bytes, else -1: the packets whose payload parse_packet reads through hb.
+HLSP2P_RULE int pes_header_start(int b0, int b1, int b3, int b4) {
+  const int s = payload_start(b3, b4);
+  return (b0 == kSync && (b1 & kPusi) && has_payload(b3) && s + 9 <= kPacket) ? s : -1;
+}
+
+// Offset of the table_id byte of a section that starts in the 188-byte packet p on `pid`, with at
+// least min_bytes of the section inside the packet, else -1.
+HLSP2P_RULE int find_section(const uint8_t* p, int pid, int table_id, int min_bytes) {
+  if (p[0] != kSync || packet_pid(p[1], p[2]) != pid || !(p[1] & kPusi)) return -1;
+  int ps = payload_start(p[3], p[4]);
+  if (!has_payload(p[3]) || ps >= kPacket) return -1;
+  ps += 1 + p[ps];  // pointer field
+  if (ps + min_bytes > kPacket || p[ps] != table_id) return -1;
+  return ps;
+}
+
+struct Psi {
+  int64_t status;  // kNoPat / kNoPmt
+  int pmt_pid;     // -1: none
+  int pid[kClasses];
+  int video_type, audio_type;
+};
+
+// PAT -> PMT PID, PMT -> the first ES PID of each class, both within the first kPsiScanPackets
+// packets; sections are read as far as they lie inside their first packet.
+HLSP2P_RULE Psi parse_psi(const uint8_t* data, int64_t n_packets) {
+  Psi r = {0, -1, {-1, -1, -1}, 0, 0};
+  const int64_t scan = n_packets < kPsiScanPackets ? n_packets : kPsiScanPackets;
+  for (int64_t i = 0; i < scan && r.pmt_pid < 0; ++i) {
+    const uint8_t* p = data + i * kPacket;
+    const int ps = find_section(p, 0, 0x00, 8);
+    if (ps < 0) continue;
+    const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
+    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
+    for (int q = ps + 8; q + 4 <= end; q += 4) {
+      if (((p[q] << 8) | p[q + 1]) != 0) {  // program 0 is the network PID
+        r.pmt_pid = packet_pid(p[q + 2], p[q + 3]);
+        break;
+      }
+    }
+  }
+  if (r.pmt_pid < 0) r.status |= kNoPat;
+  bool pmt_found = false;
+  for (int64_t i = 0; i < scan && r.pmt_pid >= 0 && !pmt_found; ++i) {
+    const uint8_t* p = data + i * kPacket;
+    const int ps = find_section(p, r.pmt_pid, 0x02, 12);
+    if (ps < 0) continue;
+    pmt_found = true;
+    const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
+    const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
+    const int pil = ((p[ps + 10] & 0x0f) << 8) | p[ps + 11];
+    for (int q = ps + 12 + pil; q + 5 <= end;) {
+      const int type = p[q];
+      const int epid = packet_pid(p[q + 1], p[q + 2]);
+      const int eil = ((p[q + 3] & 0x0f) << 8) | p[q + 4];
+      if ((type == kAvc || type == kHevc) && r.pid[0] < 0) {
+        r.pid[0] = epid;
+        r.video_type = type;
+      } else if ((type == kAdtsAac || type == kMpeg1Audio || type == kMpeg2Audio) && r.pid[1] < 0) {
+        r.pid[1] = epid;
+        r.audio_type = type;
+      } else if (type == kId3 && r.pid[2] < 0) {
+        r.pid[2] = epid;
+      }
+      q += 5 + eil;
+    }
+  }
+  if (r.pmt_pid >= 0 && !pmt_found) r.status |= kNoPmt;
+  return r;
+}
+
+// the 33-bit PTS / DTS whose 5 bytes start at byte i of hb
+template <class HB>
+HLSP2P_RULE int64_t read_ts33(HB hb, int i) {
+  return (int64_t((hb(i) >> 1) & 0x07) << 30) | (int64_t(hb(i + 1)) << 22) | (int64_t(hb(i + 2) >> 1) << 15) |
+         (int64_t(hb(i + 3)) << 7) | int64_t(hb(i + 4) >> 1);
+}
+
+struct Packet {
+  int cls;         // kClasses: the packet carries no ES bytes
+  int start, len;  // ES bytes inside the packet
+  int pes;         // 1: the packet starts a PES with these stamps (-1 = absent)
+  int64_t pts, dts;
+  int err;  // kBadSync / kBadLength / kPesHeaderError: counted in the status, the packet is dropped
+};
+
+// One packet from its first five bytes (b4 counts only with an adaptation field), the ES PIDs of
+// the three classes (-1 = none) and hb(i), byte i of the payload, which is asked only for
+// i < min(payload length, 19).
+template <class HB>
+HLSP2P_RULE Packet parse_packet(int b0, int b1, int b2, int b3, int b4, int vpid, int apid, int ipid, HB hb) {
+  Packet r = {kClasses, 0, 0, 0, -1, -1, 0};
+  if (b0 != kSync) {
+    r.err = static_cast<int>(kBadSync);
+    return r;
+  }
+  const int pid = packet_pid(b1, b2);
+  const int cls = (vpid >= 0 && pid == vpid) ? 0 : (apid >= 0 && pid == apid) ? 1 : (ipid >= 0 && pid == ipid) ? 2 : kClasses;
+  if (cls == kClasses || !has_payload(b3)) return r;
+  int s = payload_start(b3, b4);
+  if (s > kPacket) {
+    r.err = static_cast<int>(kBadLength);
+    return r;
+  }
+  int l = kPacket - s;
+  if (b1 & kPusi) {
+    if (l < 9 || hb(0) != 0 || hb(1) != 0 || hb(2) != 1 || 9 + hb(8) > l) {
+      r.err = static_cast<int>(kPesHeaderError);
+      return r;
+    }
+    const int flags = hb(7);
+    if ((flags & 0x80) && l >= 14) r.pts = read_ts33(hb, 9);
+    if ((flags & 0xC0) == 0xC0 && l >= 19) r.dts = read_ts33(hb, 14);
+    r.pes = 1;
+    s += 9 + hb(8);
+    l -= 9 + hb(8);
+  }
+  r.cls = cls;
+  r.start = s;
+  r.len = l;
+  return r;
+}
+}  // namespace ts
+
+// ---------------------------------------------------------------- sample index
+namespace es {
+HLSP2P_RULE bool video_supported(int64_t vtype) { return vtype == ts::kAvc || vtype == ts::kHevc; }
+HLSP2P_RULE bool is_hevc(int64_t vtype) { return vtype == ts::kHevc; }
+HLSP2P_RULE bool is_adts(int64_t atype) { return atype == ts::kAdtsAac; }
+HLSP2P_RULE int nal_type(bool hevc, int byte) { return hevc ? (byte >> 1) & 0x3f : byte & 0x1f; }
+
+HLSP2P_RULE int nal_flags(bool hevc, int type) {
+  if (hevc)
+    return (type >= 16 && type <= 21 ? kAuKeyframe : 0) | (type == 33 ? kAuSps : 0) | (type == 34 ? kAuPps : 0) |
+           (type == 35 ? kAuAud : 0);
+  return (type == 5 ? kAuKeyframe : 0) | (type == 7 ? kAuSps : 0) | (type == 8 ? kAuPps : 0) | (type == 9 ? kAuAud : 0);
+}
+
+HLSP2P_RULE int adts_rate(int idx) {
+  switch (idx) {
+    case 0: return 96000; case 1: return 88200; case 2: return 64000; case 3: return 48000;
+    case 4: return 44100; case 5: return 32000; case 6: return 24000; case 7: return 22050;
+    case 8: return 16000; case 9: return 12000; case 10: return 11025; case 11: return 8000;
+    case 12: return 7350; default: return 0;
+  }
+}
+
+struct AdtsWalk {
+  int32_t frames, used;  // whole frames, and their bytes
+  bool error;            // the walk stopped at bytes that are no frame inside [start, end)
+};
+
+// The ADTS frames of one audio PES, bytes [start, end) of the audio ES A.  The first frame of the
+// segment's first PES gives the sample rate and the channel configuration.
+HLSP2P_RULE AdtsWalk adts_walk(const uint8_t* A, int64_t start, int64_t end, bool first_pes, int& rate, int& chans) {
+  AdtsWalk r = {0, 0, false};
+  int64_t q = start;
+  while (q != end) {
+    if (q + 7 > end || A[q] != 0xFF || (A[q + 1] & 0xF6) != 0xF0) {
+      r.error = true;
+      break;
+    }
+    const int64_t len = (int64_t(A[q + 3] & 3) << 11) | (int64_t(A[q + 4]) << 3) | (A[q + 5] >> 5);
+    const int hdr = (A[q + 1] & 1) ? 7 : 9;
+    if (len < hdr || q + len > end) {
+      r.error = true;
+      break;
+    }
+    if (first_pes && r.frames == 0) {
+      rate = adts_rate((A[q + 2] >> 2) & 15);
+      chans = ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6);
+    }
+    ++r.frames;
+    q += len;
+  }
+  r.used = static_cast<int32_t>(q - start);
+  return r;
+}
+}  // namespace es
+}  // namespace hlsp2p
