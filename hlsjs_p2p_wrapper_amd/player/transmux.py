@@ -8,6 +8,14 @@ by ONE demux launch sequence, then a single small device->host copy of the per-s
 node's HBM arena are consumed in place (no copy); host payloads (default CDN loader) are
 staged with one H2D copy.
 
+A batch has one internal form, columns (:class:`_Columns`: source buffer, offsets, sizes,
+encrypted flags, IVs, keys, expected CRCs), and one launch core, ``_launch_core``: it rejects
+encrypted fragments that are not whole AES blocks, gives every fragment that asked for a CRC
+check exactly one, and calls the backend (one native ``transmux_launch`` on the GPU, the host
+kernels on CPU).  ``launch()`` (jobs submitted one by one) and ``launch_columns()`` (a fleet
+rank's arrays) are adapters over it, and ``_rows`` gathers a completed batch's result rows
+for ``complete()``, ``complete_arrays()`` and ``complete_columns()`` alike.
+
 The batching point is per (thread, device): the peer threads of an in-process swarm each
 get their own pipeline.
 """
@@ -23,9 +31,9 @@ import torch
 
 from ..net.event_loop import get_event_loop
 from ..ops import aes as _aes
+from ..ops import crc as _crc
 from ..ops import tsdemux as _ts
 from ..ops._native import device as _native_device
-from ..ops._native import runtime as _rt
 from ..utils.trace import PhaseTimer
 
 ALIGN = 256
@@ -73,6 +81,51 @@ def _align(n: int) -> int:
     return (n + ALIGN - 1) // ALIGN * ALIGN
 
 
+def _layout(caps: np.ndarray) -> Tuple[np.ndarray, int]:
+    """ALIGN-ed offsets of consecutive buffers of ``caps`` bytes, and their total size."""
+    sizes = (caps + (ALIGN - 1)) // ALIGN * ALIGN
+    ends = np.cumsum(sizes)
+    return ends - sizes, int(ends[-1])
+
+
+def _np(x) -> np.ndarray:
+    return x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _to_host(t: torch.Tensor):
+    """A small device tensor on its way into pinned host memory (async, on the current
+    stream: readable after the batch's event); a CPU tensor as numpy."""
+    if t.device.type == "cpu":
+        return t.numpy()
+    h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    h.copy_(t, non_blocking=True)
+    return h
+
+
+class _Columns:
+    """A batch in its one internal form.  Fragment ``i`` is ``src[offs[i] : offs[i] + nb[i]]``
+    (16-byte aligned offsets); ``enc[i]``: AES-128-CBC with ``iv[i]`` and, for the device,
+    round keys ``drk[i]`` (``ops.aes.round_keys_le``) or, for the host, the raw key
+    ``keys[i]``; ``expect`` (``None``: no checks) holds the CRC-32 fragment i's bytes must
+    have, ``-1`` for no check; ``index`` (``None``: nobody) marks the fragments whose samples
+    are to be indexed."""
+
+    __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index")
+
+    def __init__(self, src: torch.Tensor, offs: np.ndarray, nb: np.ndarray, enc: np.ndarray, iv: np.ndarray,
+                 drk: Optional[np.ndarray] = None, keys: Any = None, expect: Optional[np.ndarray] = None,
+                 index: Optional[np.ndarray] = None) -> None:
+        self.src = src      # uint8 tensor on the pipeline's device
+        self.offs = offs    # int64[n]
+        self.nb = nb        # int64[n]
+        self.enc = enc      # bool[n]
+        self.iv = iv        # uint8[n, 16]
+        self.drk = drk      # uint32[n, 44]
+        self.keys = keys    # n raw 16-byte keys (a list or uint8[n, 16]); read only where enc is set
+        self.expect = expect  # int64[n]
+        self.index = index  # bool[n]
+
+
 class MediaPipeline:
     def __init__(self, device: torch.device, loop=None) -> None:
         self.device = torch.device(device)
@@ -108,9 +161,11 @@ class MediaPipeline:
         if not jobs:
             return None
         try:
-            return self._launch(jobs)
+            b = self._launch_core(self._job_columns(jobs))
         except Exception as e:  # deliver the failure to every job of the batch
-            return _Batch(jobs, error=e)
+            return _Batch(jobs, infos=[], host=[], error=e, n=len(jobs))
+        b.jobs = jobs
+        return b
 
     def complete(self, batch: Optional["_Batch"]) -> None:
         """Wait for a launched batch and run the per-fragment callbacks."""
@@ -179,268 +234,170 @@ class MediaPipeline:
             buf[o:o + t.numel()].copy_(t, non_blocking=True)
         return buf, offs
 
-    def _launch(self, jobs: List[TransmuxJob]) -> "_Batch":
-        dev = self.device
+    def _job_columns(self, jobs: List[TransmuxJob]) -> _Columns:
+        """The submitted jobs as columns: payloads staged into one source buffer; one key per
+        stream (the usual case) is expanded once."""
+        t0 = time.perf_counter()
+        cuda = self.device.type == "cuda"
         tensors = [_as_tensor(j.payload) for j in jobs]
         sizes = [t.numel() for t in tensors]
-        self.segments += len(jobs)
-        self.bytes_in += sum(sizes)
-        self.batches += 1
-        tm = self.timer
-        t0 = time.perf_counter()
         src, src_offs = self._stage(tensors, sizes)
-        t1 = time.perf_counter()
-        tm.add("stage", t1 - t0)
-        enc = [i for i, j in enumerate(jobs) if j.key is not None]
-        clear = [i for i, j in enumerate(jobs) if j.key is None]
-        results: List[Optional[Dict[str, Any]]] = [None] * len(jobs)
-        groups = []
-        if enc:
-            bad = [i for i in enc if sizes[i] == 0 or sizes[i] % 16]
-            for i in bad:
-                results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1}
-            if bad:
-                enc = [i for i in enc if i not in bad]
-        vjobs = [i for i, j in enumerate(jobs) if j.verify is not None]
-        if dev.type == "cuda":
-            return self._launch_native(jobs, src, src_offs, sizes, enc, clear, results, t1, vjobs)
-        host_verify = None
-        if vjobs:  # CPU: a host CRC of the received bytes (the GPU fuses it into the decrypt)
-            vi = np.asarray(vjobs, dtype=np.int64)
-            got = _rt().crc32_batch(src.numpy(), np.asarray([src_offs[i] for i in vjobs], dtype=np.int64),
-                                    np.asarray([sizes[i] for i in vjobs], dtype=np.int64))
-            exp = np.asarray([jobs[i].verify.expect for i in vjobs], dtype=np.int64)
-            host_verify = [(vi, (got.astype(np.int64) & 0xFFFFFFFF) == (exp & 0xFFFFFFFF))]
-        if enc:
-            dec_offs, pos = [], 0
-            for i in enc:
-                dec_offs.append(pos)
-                pos += _align(sizes[i])
-            dec = torch.empty(pos + ALIGN, dtype=torch.uint8, device=dev)
-            out_len = _aes.cbc_decrypt_batch(src, [src_offs[i] for i in enc], [sizes[i] for i in enc],
-                                             [jobs[i].key for i in enc], [jobs[i].iv for i in enc], dec, dec_offs)
-            groups.append((enc, dec, dec_offs, out_len, [sizes[i] for i in enc]))
-        if clear:
-            groups.append((clear, src, [src_offs[i] for i in clear], [sizes[i] for i in clear],
-                           [sizes[i] for i in clear]))
-        t2 = time.perf_counter()
-        tm.add("decrypt_launch", t2 - t1)
-        infos = []
-        index = []
-        for idx, buf, offs, lens, caps in groups:
-            es_offs, pos = [], 0
-            for c in caps:
-                es_offs.append(pos)
-                pos += _align(c)
-            es = torch.empty(pos + ALIGN, dtype=torch.uint8, device=dev)
-            res = _ts.demux_batch(buf, offs, lens, es, es_offs, caps=caps)
-            infos.append((idx, res, es_offs, lens))
-            index.append(self._index(jobs, idx, res, caps))
-        # async D2H of the small per-segment info rows (+ plaintext lengths) into pinned
-        # host memory, then one event: completing the batch is the stage's only sync
-        host = []
-        for _, r, _, lens in infos:
-            if dev.type == "cpu":
-                host.append((r.info.numpy(), lens.numpy() if isinstance(lens, torch.Tensor) else np.asarray(lens)))
-                continue
-            hi = torch.empty(r.info.shape, dtype=torch.int64, pin_memory=True)
-            hi.copy_(r.info, non_blocking=True)
-            if isinstance(lens, torch.Tensor):
-                hl = torch.empty(lens.shape, dtype=torch.int64, pin_memory=True)
-                hl.copy_(lens, non_blocking=True)
-            else:
-                hl = np.asarray(lens)
-            host.append((hi, hl))
-        ev = None
-        if dev.type != "cpu":
-            ev = self._event()
-        tm.add("demux_launch", time.perf_counter() - t2)
-        return _Batch(jobs, infos=infos, host=host, event=ev, results=results, verify=host_verify,
-                      expect_mask=_mask(len(jobs), vjobs), index=index if any(index) else None)
-
-    def _index(self, jobs, idx, res: "_ts.DemuxResult", caps):
-        """The sample index of one demuxed group when any of its jobs asked for it: one
-        ``index_batch`` call on the group's stream, its ``sinfo`` rows on their way to pinned
-        host memory before the batch's event.  Returns ``(EsIndex, host sinfo)`` or None."""
-        if not any(jobs[i].index for i in idx):
-            return None
-        from ..ops import esindex as _esx
-
-        ix = _esx.index_batch(res, caps)
-        if ix.sinfo.device.type == "cpu":
-            return ix, ix.sinfo.numpy()
-        hs = torch.empty(ix.sinfo.shape, dtype=torch.int64, pin_memory=True)
-        hs.copy_(ix.sinfo, non_blocking=True)
-        return ix, hs
-
-    def _launch_native(self, jobs, src, src_offs, sizes, enc, clear, results, t1, vjobs=()) -> "_Batch":
-        """GPU batch in ONE native call (``kernels/transmux.cpp``): descriptor math, one
-        staging H2D, AES-CBC decrypt (with the receive CRC of ``vjobs`` fused in), demux per
-        group, D2H of the info rows.  Received segments the decrypt does not read (clear
-        ones, rejected ones) are checked by the CRC kernel."""
-        tm = self.timer
-        idx = enc + clear
-        n = len(idx)
-        verify = []
-        ex = cw = ctab = None
-        if vjobs:
-            in_dec = set(enc)
-            side = [i for i in vjobs if i not in in_dec]
-            if side:
-                from ..ops import crc as _crc
-
-                _, okd = _crc.crc32_batch(src, [src_offs[i] for i in side], [sizes[i] for i in side],
-                                          expect=[jobs[i].verify.expect & 0xFFFFFFFF for i in side])
-                okh = torch.empty(len(side), dtype=torch.uint8, pin_memory=True)
-                okh.copy_(okd, non_blocking=True)
-                verify.append((np.asarray(side, dtype=np.int64), okh))
-            if len(side) < len(vjobs):
-                from ..ops import crc as _crc
-
-                ex = np.full(n, -1, dtype=np.int64)
-                for r, i in enumerate(enc):
-                    if jobs[i].verify is not None:
-                        ex[r] = jobs[i].verify.expect & 0xFFFFFFFF
-                cw, ctab = _crc.fused_consts(self.device)
-        mask = _mask(len(jobs), vjobs)
-        if n == 0:  # every job was rejected above
-            return _Batch(jobs, infos=[], host=[], event=self._event() if verify else None, results=results,
-                          verify=verify or None, expect_mask=mask)
-        offs = np.fromiter((src_offs[i] for i in idx), dtype=np.int64, count=n)
-        nb = np.fromiter((sizes[i] for i in idx), dtype=np.int64, count=n)
-        flags = np.zeros(n, dtype=np.uint8)
-        flags[:len(enc)] = 1
-        drk = np.zeros((n, 44), dtype=np.uint32)
+        n = len(jobs)
+        e = [i for i, j in enumerate(jobs) if j.key is not None]
+        enc = np.zeros(n, dtype=bool)
         iv = np.zeros((n, 16), dtype=np.uint8)
-        if enc:
-            k0 = jobs[enc[0]].key
-            if all(jobs[i].key is k0 or jobs[i].key == k0 for i in enc):  # one key per stream
-                drk[:len(enc)] = _aes.round_keys_le(bytes(k0))
+        drk = np.zeros((n, 44), dtype=np.uint32) if cuda else None
+        if e:
+            enc[e] = True
+            iv[e] = np.frombuffer(b"".join(bytes(jobs[i].iv) for i in e), dtype=np.uint8).reshape(-1, 16)
+        if e and cuda:  # (the host decrypt expands the raw keys itself)
+            k0 = jobs[e[0]].key
+            if all(jobs[i].key is k0 or jobs[i].key == k0 for i in e):
+                drk[e] = _aes.round_keys_le(bytes(k0))
             else:
-                for r, i in enumerate(enc):
-                    drk[r] = _aes.round_keys_le(bytes(jobs[i].key))
-            iv[:len(enc)] = np.frombuffer(b"".join(bytes(jobs[i].iv) for i in enc), dtype=np.uint8).reshape(-1, 16)
-        td0, isb = _aes.device_tables(self.device)
-        t2 = time.perf_counter()
-        tm.add("decrypt_launch", t2 - t1)
-        ev0 = self._event()
-        groups, dec, host_block, fused = _native_device().transmux_launch(src, offs, nb, flags, drk, iv, td0, isb,
-                                                                          _ts.DEFAULT_MAX_PES, ex, cw, ctab)
-        infos, host = [], []
-        want_index = any(j.index for j in jobs)
-        index = []
-        for gidx, info, pes, es, es_offs, hinfo, hlens in groups:
-            batch_idx = [idx[k] for k in gidx.tolist()]
-            res = _ts.DemuxResult(info, pes, es, es_offs)
-            infos.append((batch_idx, res, es_offs, hlens))
-            host.append((hinfo, hlens))
-            if want_index:  # after the group's demux, on the same stream
-                index.append(self._index(jobs, batch_idx, res, [sizes[i] for i in batch_idx]))
-        if fused is not None:  # rows of the launch -> job indices
-            verify.append((np.asarray(idx, dtype=np.int64)[fused[0]], fused[1]))
-        ev = self._event()
-        tm.add("demux_launch", time.perf_counter() - t2)
-        return _Batch(jobs, infos=infos, host=host, event=ev, results=results, keep=(dec, host_block), start=ev0,
-                      verify=verify or None, expect_mask=mask, index=index if any(index) else None)
+                drk[e] = [_aes.round_keys_le(bytes(jobs[i].key)) for i in e]
+        expect = None
+        v = [i for i, j in enumerate(jobs) if j.verify is not None]
+        if v:
+            expect = np.full(n, -1, dtype=np.int64)
+            expect[v] = [jobs[i].verify.expect & 0xFFFFFFFF for i in v]
+        cols = _Columns(src, np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64), enc, iv, drk=drk,
+                        keys=None if cuda else [j.key for j in jobs], expect=expect,
+                        index=_mask(n, [i for i, j in enumerate(jobs) if j.index]))
+        self.timer.add("stage", time.perf_counter() - t0)
+        return cols
 
-    # ------------------------------------------------------------------ columnar batch
     def launch_columns(self, src: torch.Tensor, offs: np.ndarray, nbytes: np.ndarray, enc: np.ndarray,
                        drk: np.ndarray, iv: np.ndarray, tag: Any = None, keys: Optional[np.ndarray] = None,
                        expect: Optional[np.ndarray] = None) -> Optional["_Batch"]:
-        """A batch given as columns (a fleet rank: no job object per fragment).  Fragment
-        ``i`` is ``src[offs[i] : offs[i] + nbytes[i]]`` (the node's HBM arena, 16-byte aligned
-        offsets); ``enc[i]``: AES-128-CBC with round keys ``drk[i]`` (44 little-endian words,
-        ``ops.aes.round_keys_le``) and ``iv[i]``; ``keys[i]`` (raw 16-byte keys) is only read
-        by the CPU path.  ``expect[i] >= 0``: fragment i's bytes must have that CRC-32 (a
-        peer's trailer, verified here instead of by the node): an encrypted fragment is
-        checked by the decrypt itself (the CRC fused into ``aes_cbc.hip``), a clear one by the
-        CRC kernel; :meth:`complete_columns` reports the outcome.  ``tag`` comes back from
-        :meth:`complete_columns`."""
+        """A batch given as columns (a fleet rank: no job object per fragment), handed to the
+        launch core as it is.  Fragment ``i`` is ``src[offs[i] : offs[i] + nbytes[i]]`` (the
+        node's HBM arena, 16-byte aligned offsets); ``enc[i]``: AES-128-CBC with round keys
+        ``drk[i]`` (44 little-endian words, ``ops.aes.round_keys_le``) and ``iv[i]``; on CPU the
+        host decrypt reads the raw 16-byte ``keys[i]`` instead, and without ``keys`` every
+        fragment is taken as clear.  ``expect[i] >= 0``: fragment i's bytes must have that
+        CRC-32 (a peer's trailer, verified here instead of by the node); :meth:`complete_columns`
+        reports the outcome.  ``tag`` comes back from :meth:`complete_columns`.  No fragment is
+        indexed (``TransmuxJob.index`` is the job form's)."""
         n = len(offs)
         if n == 0:
             return None
-        offs = np.ascontiguousarray(offs, dtype=np.int64)
-        nb = np.ascontiguousarray(nbytes, dtype=np.int64)
+        cuda = self.device.type == "cuda"
         enc = np.asarray(enc, dtype=bool)
+        if not cuda and keys is None:
+            enc = np.zeros(n, dtype=bool)
         if expect is not None:
             expect = np.ascontiguousarray(expect, dtype=np.int64)
             if not (expect >= 0).any():
                 expect = None
-        self.segments += n
-        self.bytes_in += int(nb.sum())
-        self.batches += 1
+        col = np.ascontiguousarray
+        return self._launch_core(
+            _Columns(src, col(offs, dtype=np.int64), col(nbytes, dtype=np.int64), enc, col(iv, dtype=np.uint8),
+                     drk=col(drk, dtype=np.uint32) if cuda else None, keys=keys, expect=expect), tag)
+
+    # ------------------------------------------------------------------ the launch core
+    def _launch_core(self, c: _Columns, tag: Any = None) -> "_Batch":
+        """Enqueue one batch; every index of the returned batch is a row of ``c``.
+
+        * An encrypted row that is not a positive number of whole AES blocks is rejected: it
+          gets no decrypt or demux row.
+        * Every row with ``expect >= 0`` gets exactly one CRC check: on the GPU an accepted
+          encrypted row is checked by the decrypt that reads it (the CRC fused into
+          ``aes_cbc.hip``), every other row -- clear, rejected, and all of them on CPU -- by
+          ``ops.crc.crc32_batch``.  ``expect_mask`` records who asked, so :meth:`_verified`
+          fails a row no check covered.
+        * GPU: ONE native call (``kernels/transmux.cpp``): descriptor math, one staging H2D,
+          AES-CBC decrypt, demux per group (encrypted, then clear, each in row order), D2H of
+          the info rows.  CPU: the host kernels, the same groups."""
         t1 = time.perf_counter()
-        if self.device.type != "cuda":  # CPU mode: the job path (host kernels)
-            jobs = []
-            for i in range(n):
-                o, k = int(offs[i]), int(nb[i])
-                key = bytes(keys[i]) if (enc[i] and keys is not None) else None
-                jobs.append(TransmuxJob(src[o:o + k], key, bytes(iv[i]) if key is not None else None, None))
-            b = self.launch_jobs(jobs)
-            b.tag = tag
-            if expect is not None:  # host CRC of the same bytes
-                vi = np.flatnonzero(expect >= 0)
-                got = _rt().crc32_batch(src.numpy(), offs[vi], nb[vi])
-                b.verify = [(vi, (got.astype(np.int64) & 0xFFFFFFFF) == (expect[vi] & 0xFFFFFFFF))]
-                b.expect_mask = expect >= 0
-            return b
-        ok = ~(enc & ((nb <= 0) | (nb % 16 != 0)))  # encrypted payloads must be whole AES blocks
-        idx_ok = np.flatnonzero(ok)
-        verify = []
-        ex = None
-        if expect is not None:
-            # bytes with an expected CRC that no decrypt pass reads -- clear fragments, and
-            # encrypted ones rejected for their length -- go through the CRC kernel: every
-            # fragment that asked for a check gets one (complete_columns reports the rest False)
-            crc_v = np.flatnonzero((expect >= 0) & (~enc | ~ok))
-            if len(crc_v):
-                from ..ops import crc as _crc
-
-                _, okd = _crc.crc32_batch(src, offs[crc_v], nb[crc_v], expect=(expect[crc_v] & 0xFFFFFFFF).tolist())
-                okh = torch.empty(len(crc_v), dtype=torch.uint8, pin_memory=True)
-                okh.copy_(okd, non_blocking=True)
-                verify.append((crc_v, okh))
-            ex = np.where(enc, expect, -1)[ok] if (expect[enc & ok] >= 0).any() else None
-        if not len(idx_ok):  # nothing to decrypt or demux (the CRC checks above still run)
-            return _Batch(None, infos=[], host=[], event=self._event() if verify else None, tag=tag, n=n,
-                          verify=verify or None, expect_mask=None if expect is None else expect >= 0)
-        if not ok.all():
-            offs, nb, enc, drk, iv = offs[ok], nb[ok], enc[ok], drk[ok], iv[ok]
-        td0, isb = _aes.device_tables(self.device)
-        cw, ctab = (None, None)
-        if ex is not None:
-            from ..ops import crc as _crc
-
-            cw, ctab = _crc.fused_consts(self.device)
-        ev0 = self._event()
-        groups, dec, host_block, fused = _native_device().transmux_launch(
-            src, offs, nb, enc.astype(np.uint8), np.ascontiguousarray(drk, dtype=np.uint32),
-            np.ascontiguousarray(iv, dtype=np.uint8), td0, isb, _ts.DEFAULT_MAX_PES, ex, cw, ctab)
-        infos, host = [], []
-        for gidx, info, pes, es, es_offs, hinfo, hlens in groups:
-            infos.append((idx_ok[gidx], _ts.DemuxResult(info, pes, es, es_offs), es_offs, hlens))
+        cuda = self.device.type == "cuda"
+        n = len(c.offs)
+        self.segments += n
+        self.bytes_in += int(c.nb.sum())
+        self.batches += 1
+        ok = ~(c.enc & ((c.nb <= 0) | (c.nb % 16 != 0)))
+        rows = np.flatnonzero(ok)
+        verify: List[Any] = []
+        mask = ex = None
+        if c.expect is not None:
+            mask = c.expect >= 0
+            fuse = mask & c.enc & ok if cuda else np.zeros(n, dtype=bool)
+            side = np.flatnonzero(mask & ~fuse)
+            if len(side):
+                _, okd = _crc.crc32_batch(c.src, c.offs[side], c.nb[side],
+                                          expect=(c.expect[side] & 0xFFFFFFFF).tolist())
+                verify.append((side, _to_host(okd)))
+            if fuse.any():
+                ex = np.where(fuse, c.expect, -1)[rows]
+        groups: List[Any] = []
+        keep = ev0 = None
+        if not len(rows):  # nothing to decrypt or demux (the CRC checks above still run)
+            pass
+        elif cuda:
+            take = (lambda a: a) if len(rows) == n else (lambda a: a[rows])
+            td0, isb = _aes.device_tables(self.device)
+            cw, ctab = _crc.fused_consts(self.device) if ex is not None else (None, None)
+            ev0 = self._event()
+            out, dec, host_block, fused = _native_device().transmux_launch(
+                c.src, take(c.offs), take(c.nb), take(c.enc).astype(np.uint8), take(c.drk), take(c.iv), td0, isb,
+                _ts.DEFAULT_MAX_PES, ex, cw, ctab)
+            keep = (dec, host_block)
+            for gidx, info, pes, es, es_offs, hinfo, hlens in out:
+                groups.append((rows[gidx], _ts.DemuxResult(info, pes, es, es_offs), hinfo, hlens))
+            if fused is not None:  # rows of the launch -> rows of the batch
+                verify.append((rows[fused[0]], fused[1]))
+        else:
+            groups = self._host_groups(c, rows)
+        infos, host, index = [], [], []
+        for idx, res, hinfo, hlens in groups:
+            infos.append((idx, res, res.es_offs, hlens))
             host.append((hinfo, hlens))
-        if fused is not None:
-            verify.append((idx_ok[fused[0]], fused[1]))
-        ev = self._event()
-        self.timer.add("launch_columns", time.perf_counter() - t1)
-        return _Batch(None, infos=infos, host=host, event=ev, keep=(dec, host_block), tag=tag, n=n, start=ev0,
-                      verify=verify or None, expect_mask=None if expect is None else expect >= 0)
+            # the sample index of a group in which any row asked for it: one ``index_batch`` call
+            # after the group's demux on the same stream, its ``sinfo`` rows on their way to the
+            # host before the batch's event
+            ix = None
+            if c.index is not None and c.index[idx].any():
+                from ..ops import esindex as _esx
 
-    def launch_jobs(self, jobs: List[TransmuxJob]) -> "_Batch":
-        """:meth:`launch` for an explicit job list (the pipeline's own queue untouched)."""
-        try:
-            return self._launch(jobs)
-        except Exception as e:  # noqa: BLE001 - delivered to every job of the batch
-            return _Batch(jobs, error=e)
+                ix = _esx.index_batch(res, c.nb[idx])
+                ix = (ix, _to_host(ix.sinfo))
+            index.append(ix)
+        # completing the batch is the stage's only sync: one event after everything enqueued
+        ev = self._event() if cuda and (groups or verify) else None
+        self.timer.add("launch", time.perf_counter() - t1)
+        return _Batch(None, infos=infos, host=host, event=ev, keep=keep, tag=tag, n=n, start=ev0,
+                      verify=verify or None, expect_mask=mask, index=index if any(index) else None)
 
-    def complete_columns(self, batch: "_Batch"):
-        """Wait for a :meth:`launch_columns` batch: ``(tag, rows int64[n, INFO_WORDS], plain
-        int64[n], has_row bool[n], verified bool[n])`` aligned with the launch columns
-        (``verified[i]`` False: fragment i failed its ``expect`` CRC)."""
-        if batch.jobs is not None:  # CPU job path
-            _, rows, plain, has = self.complete_arrays(batch)
-            return batch.tag, rows, plain, has, self._verified(batch, len(batch.jobs))
+    def _host_groups(self, c: _Columns, rows: np.ndarray) -> List[Any]:
+        """The host backend: ``ops.aes.cbc_decrypt_batch`` over the encrypted rows, then
+        ``ops.tsdemux.demux_batch`` per group.  Returns ``(rows of the batch, DemuxResult, info
+        rows, plaintext lengths)`` per group, like the native call's groups."""
+        dev = self.device
+        work = []
+        e, cl = rows[c.enc[rows]], rows[~c.enc[rows]]
+        if len(e):
+            caps = c.nb[e]
+            dec_offs, size = _layout(caps)
+            dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+            out_len = _aes.cbc_decrypt_batch(c.src, c.offs[e], caps, [bytes(c.keys[i]) for i in e.tolist()], c.iv[e],
+                                             dec, dec_offs)
+            work.append((e, dec, dec_offs, out_len, caps))
+        if len(cl):
+            work.append((cl, c.src, c.offs[cl], c.nb[cl], c.nb[cl]))
+        groups = []
+        for idx, buf, offs, lens, caps in work:
+            es_offs, size = _layout(caps)
+            es = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+            res = _ts.demux_batch(buf, offs, lens, es, es_offs, caps=caps)
+            groups.append((idx, res, _to_host(res.info), _to_host(lens) if isinstance(lens, torch.Tensor) else lens))
+        return groups
+
+    # ------------------------------------------------------------------ completion
+    def _rows(self, batch: "_Batch") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Wait for a batch and gather its result rows: ``(rows int64[n, INFO_WORDS], plain
+        int64[n], has_row bool[n])`` aligned with the batch's fragments: the demux info rows,
+        the plaintext lengths, and whether the fragment has a row (False: rejected before
+        launch; its ``plain`` is -1)."""
         n = batch.n
         rows = np.zeros((n, _ts.INFO_WORDS), dtype=np.int64)
         plain = np.full(n, -1, dtype=np.int64)
@@ -450,10 +407,25 @@ class MediaPipeline:
         self.timer.add("wait_device", time.perf_counter() - t3)
         for (idx, _res, _es_offs, _lens), (hinfo, hlens) in zip(batch.infos, batch.host):
             k = len(idx)
-            rows[idx] = (hinfo.numpy() if isinstance(hinfo, torch.Tensor) else np.asarray(hinfo))[:k]
-            plain[idx] = (hlens.numpy() if isinstance(hlens, torch.Tensor) else np.asarray(hlens))[:k]
+            rows[idx] = _np(hinfo)[:k]
+            plain[idx] = _np(hlens)[:k]
             has[idx] = True
-        return batch.tag, rows, plain, has, self._verified(batch, n)
+        return rows, plain, has
+
+    def complete_arrays(self, batch: Optional["_Batch"]):
+        """Wait for a launched batch; return ``(jobs, rows, plain, has_row)``: :meth:`_rows`
+        aligned with ``jobs``.  The columnar form a fleet node ships to its players without a
+        Python object per word."""
+        if batch is None:
+            return [], None, None, None
+        return (batch.jobs,) + self._rows(batch)
+
+    def complete_columns(self, batch: "_Batch"):
+        """Wait for a :meth:`launch_columns` batch: ``(tag, rows int64[n, INFO_WORDS], plain
+        int64[n], has_row bool[n], verified bool[n])`` aligned with the launch columns
+        (``verified[i]`` False: fragment i failed its ``expect`` CRC)."""
+        rows, plain, has = self._rows(batch)
+        return batch.tag, rows, plain, has, self._verified(batch, batch.n)
 
     @staticmethod
     def _verified(batch: "_Batch", n: int) -> np.ndarray:
@@ -463,84 +435,38 @@ class MediaPipeline:
         if batch.expect_mask is not None:
             out[batch.expect_mask] = False
         for idx, ok in batch.verify or ():
-            out[idx] = (ok.numpy() if isinstance(ok, torch.Tensor) else np.asarray(ok)).astype(bool)
+            out[idx] = _np(ok).astype(bool)
         return out
-
-    def complete_rows(self, batch: Optional["_Batch"]) -> List[Tuple["TransmuxJob", Optional[list], int]]:
-        """Wait for a launched batch and return ``(job, info row, plaintext length)`` per job
-        without building the per-fragment result dicts or running callbacks (a fleet node
-        ships the rows to its player processes; ``row`` is None for a rejected job)."""
-        if batch is None:
-            return []
-        if batch.error is not None:
-            return [(j, None, -1) for j in batch.jobs]
-        t3 = time.perf_counter()
-        self._wait(batch)
-        self.timer.add("wait_device", time.perf_counter() - t3)
-        out: List[Any] = [None] * len(batch.jobs)
-        for (idx, _res, _es_offs, _lens), (hinfo, hlens) in zip(batch.infos, batch.host):
-            rows = (hinfo.numpy() if isinstance(hinfo, torch.Tensor) else hinfo).tolist()
-            plain = (hlens.numpy() if isinstance(hlens, torch.Tensor) else np.asarray(hlens)).tolist()
-            for k, i in enumerate(idx):
-                out[i] = (batch.jobs[i], rows[k], int(plain[k]))
-        for i, o in enumerate(out):
-            if o is None:  # rejected before launch (e.g. not a multiple of 16 bytes)
-                out[i] = (batch.jobs[i], None, -1)
-        return out
-
-    def complete_arrays(self, batch: Optional["_Batch"]):
-        """Wait for a launched batch; return ``(jobs, rows, plain, has_row)``: the info rows as
-        one int64 array ``[n, INFO_WORDS]`` aligned with ``jobs``, the plaintext lengths, and
-        whether each job has a row (False: rejected before launch; its ``plain`` is -1).  The
-        columnar form a fleet node ships to its players without a Python object per word."""
-        if batch is None:
-            return [], None, None, None
-        n = len(batch.jobs)
-        rows = np.zeros((n, _ts.INFO_WORDS), dtype=np.int64)
-        plain = np.full(n, -1, dtype=np.int64)
-        has = np.zeros(n, dtype=bool)
-        if batch.error is not None:
-            return batch.jobs, rows, plain, has
-        t3 = time.perf_counter()
-        self._wait(batch)
-        self.timer.add("wait_device", time.perf_counter() - t3)
-        for (idx, _res, _es_offs, _lens), (hinfo, hlens) in zip(batch.infos, batch.host):
-            k = len(idx)
-            rows[idx] = (hinfo.numpy() if isinstance(hinfo, torch.Tensor) else np.asarray(hinfo))[:k]
-            plain[idx] = (hlens.numpy() if isinstance(hlens, torch.Tensor) else np.asarray(hlens))[:k]
-            has[idx] = True
-        return batch.jobs, rows, plain, has
 
     def _complete(self, b: "_Batch") -> List[Dict[str, Any]]:
-        tm = self.timer
-        t3 = time.perf_counter()
-        self._wait(b)
+        """The per-fragment results of a job batch, built from :meth:`_rows`."""
+        rows, plain, has = self._rows(b)
         t4 = time.perf_counter()
-        tm.add("wait_device", t4 - t3)
-        results = b.results
-        for g, ((idx, res, es_offs, lens), (hinfo, hlens)) in enumerate(zip(b.infos, b.host)):
-            hinfo = hinfo.numpy() if isinstance(hinfo, torch.Tensor) else hinfo
-            plain_lens = hlens.numpy() if isinstance(hlens, torch.Tensor) else hlens
-            rows = hinfo.tolist()
+        rl, pl = rows.tolist(), plain.tolist()
+        results: List[Any] = [None] * b.n
+        for i in np.flatnonzero(~has).tolist():  # rejected before launch
+            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1}
+        for g, (idx, res, es_offs, _lens) in enumerate(b.infos):
             es = res.es
-            for k, i in enumerate(idx):
-                row = rows[k]
-                # ES views (per class, at the row's offsets from es_offs[k]) are built on first access: the
+            il = idx.tolist()
+            for k, (i, base) in enumerate(zip(il, es_offs.tolist())):
+                row = rl[i]
+                # ES views (per class, at the row's offsets from base) are built on first access: the
                 # buffer path only needs their byte counts, which the info row holds
-                r = _Result(status=row[0], info=InfoRow(row), plain_bytes=int(plain_lens[k]), demux=res, index=k)
-                r._es = (es, es_offs[k], row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
-                if plain_lens[k] < 0:
+                r = _Result(status=row[0], info=InfoRow(row), plain_bytes=pl[i], demux=res, index=k)
+                r._es = (es, base, row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
+                if pl[i] < 0:
                     r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
                 results[i] = r
             gi = b.index[g] if b.index is not None else None
             if gi is not None:  # the jobs of this group that asked for the sample index
                 ix, hs = gi
-                srows = (hs.numpy() if isinstance(hs, torch.Tensor) else hs).tolist()
-                for k, i in enumerate(idx):
+                srows = _np(hs).tolist()
+                for k, i in enumerate(il):
                     if b.jobs[i].index:
                         results[i]["samples"] = Samples(srows[k], ix, k)
-        tm.add("results", time.perf_counter() - t4)
-        return results  # type: ignore[return-value]
+        self.timer.add("results", time.perf_counter() - t4)
+        return results
 
 
 def _mask(n: int, idx) -> Optional[np.ndarray]:
@@ -673,11 +599,10 @@ class _Batch:
     infos: Any = None
     host: Any = None
     event: Any = None
-    results: Any = None
     error: Optional[BaseException] = None
     keep: Any = None  # device/pinned buffers the batch's in-flight work uses
     tag: Any = None  # launch_columns: the caller's columns, handed back by complete_columns
-    n: int = 0  # launch_columns: fragments in the batch
+    n: int = 0  # fragments in the batch
     start: Any = None  # timing event recorded before the batch's first launch
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)

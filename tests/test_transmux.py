@@ -257,3 +257,66 @@ def test_jobs_with_verify_tickets_are_checked_by_their_batch(device, request):
     for n in range(len(subs)):
         if n != 2:
             assert out[n].get("error") is None and not out[n].get("verify_failed"), (n, out[n])
+
+
+@pytest.mark.parametrize("device", ["cpu", pytest.param("cuda", marks=pytest.mark.gpu)])
+def test_job_form_and_column_form_give_the_same_batch(device, request):
+    """The two entry forms are adapters over one launch core: the same fragments submitted as
+    jobs and handed over as columns give equal ``rows``, ``plain`` and ``has`` arrays, and the
+    columns' ``verified`` is what the jobs' tickets are told.  The batch takes every check
+    route: a rejected encrypted fragment with a correct expected CRC (CRC kernel), a clear one
+    with a wrong CRC (CRC kernel), an accepted encrypted one with a wrong CRC and one with a
+    correct CRC (fused into the decrypt), and fragments that ask for no check."""
+    import zlib
+
+    import numpy as np
+
+    if device == "cuda":
+        request.getfixturevalue("cuda")
+    jobs, arena, views, offs = _arena_jobs(device)
+    key = bytes(range(16))
+    # (view, key, iv) per fragment: the arena's five, then 100 bytes of the first ciphertext (rejected)
+    frags = [(v, k, iv) for (_, _, k, iv), v in zip(jobs, views)] + [(views[0][:100], key, jobs[0][3])]
+    offs = offs + [offs[0]]
+    n = len(frags)
+    crcs = [zlib.crc32(bytes(v.cpu().numpy())) for v, _, _ in frags]
+    expect = np.full(n, -1, dtype=np.int64)
+    expect[0] = crcs[0]          # accepted encrypted, correct
+    expect[1] = crcs[1] ^ 0x10   # clear, wrong
+    expect[2] = crcs[2] ^ 1      # accepted encrypted, wrong
+    expect[n - 1] = crcs[n - 1]  # rejected, correct
+    assert frags[1][1] is None and frags[0][1] is not None and frags[2][1] is not None
+    want = np.ones(n, dtype=bool)
+    want[[1, 2]] = False
+
+    pipe = MediaPipeline(torch.device(device), new_event_loop("virtual"))
+    pipe.auto_flush = False
+
+    def submit_all():
+        tickets = [_Ticket(int(e)) if e >= 0 else None for e in expect]
+        for i, ((v, k, iv), t) in enumerate(zip(frags, tickets)):
+            pipe.submit(TransmuxJob(v, k, iv, lambda r: None, i, t))
+        return tickets
+
+    submit_all()
+    got_jobs, rows_j, plain_j, has_j = pipe.complete_arrays(pipe.launch())
+    assert [j.frag for j in got_jobs] == list(range(n))
+    tickets = submit_all()
+    pipe.complete(pipe.launch())
+    told = [None if t is None else t.got for t in tickets]
+
+    enc = np.array([k is not None for _, k, _ in frags])
+    drk = np.tile(aes.round_keys_le(key), (n, 1)).astype(np.uint32)
+    iv = np.stack([np.frombuffer(v if v is not None else bytes(16), dtype=np.uint8) for _, _, v in frags])
+    keys = np.tile(np.frombuffer(key, dtype=np.uint8), (n, 1))
+    nb = np.array([v.numel() for v, _, _ in frags], dtype=np.int64)
+    tag, rows_c, plain_c, has_c, verified = pipe.complete_columns(
+        pipe.launch_columns(arena, np.asarray(offs, dtype=np.int64), nb, enc, drk, iv, "t", keys=keys, expect=expect))
+    assert tag == "t"
+    assert rows_j.dtype == rows_c.dtype and np.array_equal(rows_j, rows_c)
+    assert plain_j.dtype == plain_c.dtype and np.array_equal(plain_j, plain_c)
+    assert has_j.dtype == has_c.dtype and np.array_equal(has_j, has_c)
+    assert has_c.tolist() == [True] * (n - 1) + [False] and plain_c[n - 1] == -1
+    assert verified.tolist() == want.tolist()
+    assert told == [bool(w) if e >= 0 else None for w, e in zip(want, expect)]
+    assert [bool(verified[i]) for i in range(n) if told[i] is not None] == [t for t in told if t is not None]
