@@ -136,6 +136,45 @@ void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t 
   hip_ok(D::launch_es_index(a), "es_index launch");
 }
 
+// Remux of a demuxed and indexed batch (remux.hip): the inputs of es_index, its four outputs, and
+// per segment a region of es::remux_out_bytes(cap, max_nal) bytes of `out` at out_off (the Python
+// wrapper has checked the regions against out); tile_prefix is the exclusive prefix of
+// ceil(region / remux_tile_bytes()).
+void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
+           int64_t max_pes, int64_t max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_aframes,
+           Tensor scratch, Tensor vsamples, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_nal > 0 && max_aframes > 0 && total_tiles >= 0,
+              "remux: max_pes / max_nal / max_aframes / total_tiles out of range");
+  const D::RemuxArgs a{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
+                       .es_off = check<int64_t>(es_off, "es_off"),
+                       .cap = check<int64_t>(cap, "cap", B),
+                       .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
+                       .nseg = static_cast<int>(B), .total_tiles = total_tiles,
+                       .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+                       .pes = check<int64_t>(pes, "pes", B * ts::kClasses * max_pes * 3),
+                       .max_pes = max_pes, .max_nal = max_nal,
+                       .nal = check<int32_t>(nal, "nal", B * max_nal * 4),
+                       .au = check<int32_t>(au, "au", B * max_pes * 4),
+                       .aframes = check<int32_t>(aframes, "aframes", B * max_pes * 2),
+                       .sinfo = check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords),
+                       .max_aframes = max_aframes,
+                       .scratch = check<int32_t>(scratch, "scratch",
+                                        es_::remux_scratch(B, max_nal, max_aframes).end),
+                       .vsamples = check<int32_t>(vsamples, "vsamples", B * max_pes * es_::kVsampleWords),
+                       .asamples = check<int32_t>(asamples, "asamples", B * max_aframes * es_::kAsampleWords),
+                       .rinfo = check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords),
+                       .out = check<uint8_t>(out, "out"),
+                       .out_off = check<int64_t>(out_off, "out_off", B),
+                       .stream = stream()};
+  TORCH_CHECK(es.device() == out.device() && es.device() == rinfo.device(), "tensors on different devices");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0,
+              "es / out must be 16-byte aligned");
+  TORCH_CHECK(es.data_ptr() != out.data_ptr(), "remux cannot run in place");
+  hip_ok(D::launch_remux(a), "remux launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -261,6 +300,10 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
         "int max_pes, int max_nal, Tensor(a!) scratch, Tensor(b!) nal, Tensor(c!) au, Tensor(d!) aframes, "
         "Tensor(e!) sinfo) -> ()");
+  m.def("remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
+        "int max_pes, int max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_aframes, "
+        "Tensor(a!) scratch, Tensor(b!) vsamples, Tensor(c!) asamples, Tensor(d!) rinfo, Tensor(e!) out, "
+        "Tensor out_off) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -270,6 +313,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("crc32_batch", &crc32_batch);
   m.impl("ts_demux", &ts_demux);
   m.impl("es_index", &es_index);
+  m.impl("remux", &remux);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -297,6 +341,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("es_index_scratch_words", [](int64_t total_tiles, int64_t nseg, int64_t max_nal) {
     return es_::index_scratch(total_tiles, nseg, max_nal).end;
   }, py::arg("total_tiles"), py::arg("nseg"), py::arg("max_nal"));
+  m.def("remux", &remux);
+  m.def("remux_tile_bytes", &D::remux_tile_bytes);
+  m.def("remux_out_bytes", py::vectorize(&es_::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
+  m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
+    return es_::remux_scratch(nseg, max_nal, max_aframes).end;
+  }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

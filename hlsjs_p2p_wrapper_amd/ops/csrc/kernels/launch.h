@@ -109,6 +109,27 @@ struct EsIndexArgs {
 int es_index_tile_bytes();
 hipError_t launch_es_index(const EsIndexArgs& a);
 
+struct RemuxArgs {
+  const uint8_t* es;
+  int64_t es_numel;
+  const int64_t *es_off, *cap, *tile_prefix;  // tiles of es::remux_out_bytes(cap, max_nal)
+  int nseg;
+  int64_t total_tiles;
+  const int64_t *info, *pes;
+  int64_t max_pes, max_nal;
+  const int32_t *nal, *au, *aframes;  // launch_es_index's outputs
+  const int64_t* sinfo;
+  int64_t max_aframes;
+  int32_t* scratch;  // es::remux_scratch(nseg, max_nal, max_aframes)
+  int32_t *vsamples, *asamples;
+  int64_t* rinfo;
+  uint8_t* out;
+  const int64_t* out_off;
+  hipStream_t stream;
+};
+int remux_tile_bytes();
+hipError_t launch_remux(const RemuxArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

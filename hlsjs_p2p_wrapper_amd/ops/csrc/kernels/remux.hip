@@ -1,0 +1,404 @@
+// Remux of demuxed and indexed segments to fMP4 samples and mdat boxes (docs/REMUX.md) — CDNA4 /
+// gfx950.
+//
+// Input: what ts_demux.hip and es_index.hip leave in HBM.  Output per segment, identical to the
+// host implementation runtime/remux.cpp remux_segment:
+//   vsamples: int32[seg][max_pes][5]     = (offset, size, duration, cts, flags)   (-1 rows beyond)
+//   asamples: int32[seg][max_aframes][2] = (offset, size)                         (-1 rows beyond)
+//   rinfo:    int64[seg][8]
+//   out:      at out_off[seg]: 'mdat' box of the video payload (4-byte length + NAL bytes per
+//             kept NAL), then at the next multiple of 16 the 'mdat' box of the ADTS frame bodies
+//
+// Two launches on the caller's stream, no host round trip (host caps size the tile space and
+// bound every access):
+//   1. remux_plan_kernel — one workgroup per segment: a lane per NAL row (kept or not, output
+//                          bytes; a workgroup scan with a carry gives every kept NAL its payload
+//                          offset, sample sizes add up with integer atomics), a lane per access
+//                          unit (timestamps, flags, then offsets by a second scan), a lane per
+//                          audio PES (two walks over its counted frames around a scan of the PES
+//                          totals), then rinfo and both box headers.  The payload offsets and
+//                          source offsets go to scratch for the copy.
+//   2. remux_copy_kernel — output-driven: one workgroup per 16 KiB tile of one segment's output
+//                          region, a lane per 16 aligned output bytes.  The lane finds the NAL
+//                          (or frame) that covers its bytes by binary search of the payload
+//                          offsets, narrowed to the rows the tile touches; 16 bytes inside one
+//                          body are funnelled out of five source dwords (v_alignbyte) and stored
+//                          as one vector, every other chunk goes byte by byte and stores only
+//                          payload bytes.  Tiles past the real output exit at once.
+// No workgroup waits for another one: the order comes from the launches alone.
+// The keep rule, the ADTS frame rule and the timestamp differences are shared/grammar.hpp
+// (namespace es), the same functions runtime/remux.cpp calls.
+#include "common.h"
+#include "grammar.hpp"
+#include "launch.h"
+
+namespace hlsp2p {
+namespace dev {
+
+constexpr int kRxThreads = 256;
+constexpr int kRxWaves = kRxThreads / 64;
+constexpr int kRxIterBytes = kRxThreads * 16;
+constexpr int kRxIters = es::kRemuxTile / kRxIterBytes;
+static_assert(kRxIters * kRxIterBytes == es::kRemuxTile, "the tile is a whole number of iterations");
+int remux_tile_bytes() { return es::kRemuxTile; }
+
+// Exclusive prefix sum over the workgroup (every thread calls it); total: the sum of all.
+__device__ __forceinline__ int64_t rx_block_scan(int64_t v, int64_t* s_w, int64_t& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int64_t inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int64_t t = __shfl_up(inc, d);
+    if (lane >= d) inc += t;
+  }
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  int64_t pre = 0;
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kRxWaves; ++w) {
+    if (w < wave) pre += s_w[w];
+    total += s_w[w];
+  }
+  __syncthreads();  // s_w is free again
+  return pre + inc - v;
+}
+
+__device__ __forceinline__ int32_t rx_sat32(int64_t v) { return v < 0x7fffffff ? static_cast<int32_t>(v) : 0x7fffffff; }
+
+// ---------------------------------------------------------------- 1. plan
+__global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
+    const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
+    const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
+    const int32_t* __restrict__ nal_all, const int32_t* __restrict__ au_all, const int32_t* __restrict__ af_all,
+    const int64_t* __restrict__ sinfo, int64_t max_aframes, int32_t* __restrict__ scratch,
+    int32_t* __restrict__ vs_all, int32_t* __restrict__ as_all, int64_t* __restrict__ rinfo, uint8_t* __restrict__ out,
+    const int64_t* __restrict__ out_off) {
+  __shared__ int64_t s_w[kRxWaves];
+  __shared__ unsigned long long s_first_unfit;  // payload offset of the first kept NAL without room
+  __shared__ int s_bad, s_nrec, s_q, s_aover;
+  const int seg = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
+  const int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
+  const int64_t room_es = clamp(cap[seg], 0, 0x7fffffff);
+  const uint8_t* V = es + es_off[seg];
+  const int64_t vtype = inf[ts::kVideoType];
+  const bool supported = es::video_supported(vtype);
+  const bool hevc = es::is_hevc(vtype);
+  const int64_t R = supported ? clamp(si[es::kNumNal], 0, max_nal) : 0;
+  const int64_t m = supported ? clamp(si[es::kNumAu], 0, max_pes) : 0;
+  const int64_t* vp = pes + static_cast<int64_t>(seg) * ts::kClasses * max_pes * 3;  // class 0
+  const int64_t* ap = vp + max_pes * 3;                                               // class 1
+  const int32_t* nal = nal_all + static_cast<int64_t>(seg) * max_nal * 4;
+  const int32_t* au = au_all + static_cast<int64_t>(seg) * max_pes * 4;
+  const int32_t* af = af_all + static_cast<int64_t>(seg) * max_pes * 2;
+  int32_t* vs = vs_all + static_cast<int64_t>(seg) * max_pes * es::kVsampleWords;
+  int32_t* as = as_all + static_cast<int64_t>(seg) * max_aframes * es::kAsampleWords;
+  const es::RemuxScratch part = es::remux_scratch(1, max_nal, max_aframes);
+  int32_t* sc = scratch + static_cast<int64_t>(seg) * part.stride;
+  int32_t* vstart = sc + part.vstart;
+  int32_t* vsrc = sc + part.vsrc;
+  int32_t* astart = sc + part.astart;
+  int32_t* asrc = sc + part.asrc;
+  uint8_t* o = out + out_off[seg];
+  const int64_t region = es::remux_out_bytes(room_es, max_nal);
+  const int64_t v_limit = es::remux_video_limit(room_es, max_nal);
+  if (tid == 0) {
+    s_first_unfit = ~0ull;
+    s_bad = 0;
+    s_nrec = 0;
+    s_q = 0;
+    s_aover = 0;
+  }
+
+  // ---- a lane per sample row: timestamps and flags, size 0 for the atomics below
+  bool bad = false;
+  for (int64_t a = tid; a < max_pes; a += kRxThreads) {
+    int32_t r0 = -1, r1 = -1, r2 = -1, r3 = -1, r4 = -1;
+    if (a < m) {
+      es::Delta32 dur = {0, true};
+      if (a + 1 < m) dur = es::delta32(vp[3 * (a + 1) + 2], vp[3 * a + 2], true);
+      else if (m > 1) dur = es::delta32(vp[3 * a + 2], vp[3 * (a - 1) + 2], true);
+      const es::Delta32 cts = es::delta32(vp[3 * a + 1], vp[3 * a + 2], false);
+      bad |= !dur.fits || !cts.fits;
+      r0 = 0;
+      r1 = 0;
+      r2 = dur.v;
+      r3 = cts.v;
+      r4 = (au[4 * a + 2] & es::kAuKeyframe) ? es::kSampleSync : es::kSampleNonSync;
+    }
+    int32_t* row = vs + a * es::kVsampleWords;
+    row[0] = r0;
+    row[1] = r1;
+    row[2] = r2;
+    row[3] = r3;
+    row[4] = r4;
+  }
+  for (int64_t f = tid; f < max_aframes; f += kRxThreads) {
+    as[2 * f] = -1;
+    as[2 * f + 1] = -1;
+  }
+  __syncthreads();  // rows and the shared words are set
+  if (bad) atomicOr(&s_bad, 1);
+
+  // ---- a lane per NAL row, a carry across rounds of the workgroup
+  int64_t carry = 0;
+  for (int64_t kb = 0; kb < R; kb += kRxThreads) {  // R is workgroup-uniform
+    const int64_t k = kb + tid;
+    int64_t ob = 0, s = 0, a = -1;
+    if (k < R) {
+      s = clamp(nal[4 * k], 0, room_es);
+      const int64_t len = clamp(nal[4 * k + 1], 0, room_es - s);
+      a = nal[4 * k + 3];
+      if (a >= 0 && a < m && len > 0 && es::nal_kept(hevc, nal[4 * k + 2])) ob = 4 + len;
+    }
+    int64_t total;
+    const int64_t d = carry + rx_block_scan(ob, s_w, total);
+    carry += total;
+    if (k < R) {
+      vstart[k] = rx_sat32(d);
+      vsrc[k] = static_cast<int32_t>(s);
+      if (ob > 0) {
+        if (d + ob <= v_limit) atomicAdd(&vs[a * es::kVsampleWords + 1], static_cast<int32_t>(ob));
+        else atomicMin(&s_first_unfit, static_cast<unsigned long long>(d));
+      }
+    }
+  }
+  __syncthreads();  // sizes and s_first_unfit are complete
+  const bool v_cut = s_first_unfit != ~0ull;
+  const int64_t P = v_cut ? static_cast<int64_t>(s_first_unfit) : carry;
+  if (tid == 0) vstart[R] = rx_sat32(carry);
+
+  // ---- sample offsets
+  int64_t acarry = 0;
+  for (int64_t ab = 0; ab < m; ab += kRxThreads) {
+    const int64_t a = ab + tid;
+    const int64_t sz = a < m ? vs[a * es::kVsampleWords + 1] : 0;
+    int64_t total;
+    const int64_t off = acarry + rx_block_scan(sz, s_w, total);
+    acarry += total;
+    if (a < m) vs[a * es::kVsampleWords] = static_cast<int32_t>(off);
+  }
+
+  // ---- audio: a lane per PES walks its counted frames, twice around the scan of the totals
+  const int64_t A0 = (8 + P + 15) & ~int64_t(15);
+  const int64_t a_room = region - (A0 + 8);
+  const int64_t ma_all = clamp(inf[ts::kNumAudioPes], 0, max_pes);
+  const int64_t ma = es::is_adts(inf[ts::kAudioType]) ? ma_all : 0;
+  const int64_t a_off = clamp(inf[ts::kAudioEsOffset], 0, room_es);
+  const int64_t a_len = clamp(inf[ts::kAudioBytes], 0, room_es - a_off);
+  const uint8_t* A = V + a_off;
+  int64_t fcarry = 0, bcarry = 0;
+  for (int64_t kb = 0; kb < ma; kb += kRxThreads) {
+    const int64_t k = kb + tid;
+    int64_t start = 0, end = 0, want = 0, cnt = 0, bytes = 0;
+    if (k < ma) {
+      start = clamp(ap[3 * k], 0, a_len);
+      end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
+      want = af[2 * k];
+      int64_t q = start;
+      for (; cnt < want; ++cnt) {
+        const es::AdtsFrame f = es::adts_frame_at(A, q, end);
+        if (f.len == 0) break;
+        bytes += f.len - f.hdr;
+        q += f.len;
+      }
+    }
+    int64_t ftotal, btotal;
+    int64_t fi = fcarry + rx_block_scan(cnt, s_w, ftotal);
+    int64_t bo = bcarry + rx_block_scan(bytes, s_w, btotal);
+    fcarry += ftotal;
+    bcarry += btotal;
+    int nrec = 0, qsum = 0;
+    bool over = false;
+    int64_t q = start;
+    for (int64_t j = 0; j < cnt; ++j, ++fi) {
+      const es::AdtsFrame f = es::adts_frame_at(A, q, end);
+      const int64_t size = f.len - f.hdr;
+      if (fi < max_aframes && bo + size <= a_room) {  // a prefix of the frames: both sides only grow
+        as[2 * fi] = static_cast<int32_t>(bo);
+        as[2 * fi + 1] = static_cast<int32_t>(size);
+        astart[fi] = static_cast<int32_t>(bo);
+        asrc[fi] = static_cast<int32_t>(a_off + q + f.hdr);
+        ++nrec;
+        qsum += static_cast<int>(size);
+      } else {
+        over = true;
+      }
+      bo += size;
+      q += f.len;
+    }
+    if (nrec) {
+      atomicAdd(&s_nrec, nrec);
+      atomicAdd(&s_q, qsum);
+    }
+    if (over) atomicOr(&s_aover, 1);
+  }
+  __syncthreads();
+  const int64_t n_rec = s_nrec, Q = s_q;
+
+  // ---- totals and the two box headers
+  if (tid < 16) {
+    const bool second = tid >= 8;
+    const int b = tid & 7;
+    const uint32_t size = static_cast<uint32_t>(8 + (second ? Q : P));
+    const uint32_t word = b < 4 ? size : 0x6d646174u;  // 'mdat'
+    o[(second ? A0 : 0) + b] = static_cast<uint8_t>(word >> (8 * (3 - (b & 3))));
+  }
+  if (tid == 0) {
+    astart[n_rec] = static_cast<int32_t>(Q);
+    sc[0] = static_cast<int32_t>(R);
+    sc[1] = static_cast<int32_t>(n_rec);
+    int64_t status = supported ? 0 : es::kRemuxUnsupportedVideo;
+    if ((si[es::kStatus] & es::kNalOverflow) || v_cut) status |= es::kTruncated;
+    if (s_aover) status |= es::kAframeOverflow;
+    if (s_bad) status |= es::kBadTimestamps;
+    int64_t* ri = rinfo + static_cast<int64_t>(seg) * es::kRinfoWords;
+    ri[es::kRStatus] = status;
+    ri[es::kVideoPayloadBytes] = P;
+    ri[es::kNumVsamples] = m;
+    ri[es::kAudioBoxOffset] = A0;
+    ri[es::kAudioPayloadBytes] = Q;
+    ri[es::kNumAframes] = fcarry;
+    ri[es::kVideoBaseDts] = m > 0 ? vp[2] : -1;
+    ri[es::kAudioBasePts] = ma_all > 0 ? ap[1] : -1;
+  }
+}
+
+// ---------------------------------------------------------------- 2. copy
+// last j in [lo, hi] with t[j] <= y, given t[lo] <= y (t ascends)
+__device__ __forceinline__ int rx_last_le(const int32_t* __restrict__ t, int lo, int hi, int y) {
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (t[mid] <= y) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// The same for a workgroup-uniform y with all 64 lanes of the wave active, over rows [0, cnt): each
+// lane tests one row and a ballot counts the rows <= y, so the lookup costs one global round trip
+// per 64-way level (two up to 4096 rows) instead of log2(cnt) dependent loads at the head of
+// every workgroup (find_seg_wave's scheme, on int32 rows).
+__device__ __forceinline__ int rx_last_le_wave(const int32_t* __restrict__ t, int cnt, int y) {
+  const int lane = static_cast<int>(threadIdx.x & 63);
+  const int n = cnt;
+  int lo = 0;
+  while (cnt > 64) {
+    const int stride = (cnt + 63) >> 6;
+    const int idx = lo + lane * stride;
+    const bool le = idx < lo + cnt && t[idx] <= y;
+    lo += (__popcll(__ballot(le)) - 1) * stride;
+    cnt = stride < n - lo ? stride : n - lo;
+  }
+  const bool le = lane < cnt && t[lo + lane] <= y;
+  return __builtin_amdgcn_readfirstlane(lo + __popcll(__ballot(le)) - 1);
+}
+
+// One payload inside one tile.  Output bytes [lo, hi) of the region hold the payload: row j of
+// `cnt` rows starts at payload offset start[j] (start[0] == 0, start[cnt] >= hi - lo) with kPrefix
+// bytes of big-endian length, then the bytes of the segment's ES from src[j] on.  Every thread
+// of the workgroup calls it.  The loads of the four iterations are issued together, phase by
+// phase (rows, then source dwords), so a lane waits for two round trips, not eight.
+template <int kPrefix>
+__device__ __forceinline__ void rx_copy_stream(__amdgpu_buffer_rsrc_t rsrc, const uint8_t* __restrict__ V,
+                                               uint8_t* __restrict__ o, int b0, int lo, int hi,
+                                               const int32_t* __restrict__ start, const int32_t* __restrict__ src,
+                                               int cnt) {
+  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+  const int t_lo = lo > b0 ? lo : b0;
+  const int t_hi = hi < b0 + es::kRemuxTile ? hi : b0 + es::kRemuxTile;
+  if (t_lo >= t_hi || cnt <= 0) return;  // workgroup-uniform
+  const int j_lo = rx_last_le_wave(start, cnt, t_lo - lo);  // uniform: the rows this tile touches
+  const int j_hi = rx_last_le_wave(start, cnt, t_hi - 1 - lo);
+  int c_lo[kRxIters], c_hi[kRxIters], j[kRxIters], e[kRxIters], nxt[kRxIters], sj[kRxIters];
+#pragma unroll
+  for (int it = 0; it < kRxIters; ++it) {
+    const int x0 = b0 + it * kRxIterBytes + static_cast<int>(threadIdx.x) * 16;
+    c_lo[it] = x0 > t_lo ? x0 : t_lo;
+    c_hi[it] = x0 + 16 < t_hi ? x0 + 16 : t_hi;
+    j[it] = c_lo[it] < c_hi[it] ? rx_last_le(start, j_lo, j_hi, c_lo[it] - lo) : j_lo;
+  }
+#pragma unroll
+  for (int it = 0; it < kRxIters; ++it) {  // rows in range also for idle lanes: unconditional loads
+    e[it] = start[j[it]];
+    nxt[it] = start[j[it] + 1];
+    sj[it] = src[j[it]];
+  }
+  bool fast[kRxIters];
+  v4u v[kRxIters];
+  uint32_t w4[kRxIters];
+  int sa[kRxIters];
+#pragma unroll
+  for (int it = 0; it < kRxIters; ++it) {
+    const int y = c_lo[it] - lo;
+    fast[it] = c_hi[it] - c_lo[it] == 16 && y >= e[it] + kPrefix && y + 16 <= nxt[it];
+    sa[it] = fast[it] ? sj[it] + (y - e[it] - kPrefix) : 0;
+    v[it] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, sa[it] & ~3, 0, 0);
+    w4[it] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (sa[it] & ~3) + 16, 0, 0);
+  }
+#pragma unroll
+  for (int it = 0; it < kRxIters; ++it) {
+    if (fast[it]) {
+      const uint32_t sh = static_cast<uint32_t>(sa[it] & 3);
+      const v4u q = {__builtin_amdgcn_alignbyte(v[it].y, v[it].x, sh), __builtin_amdgcn_alignbyte(v[it].z, v[it].y, sh),
+                     __builtin_amdgcn_alignbyte(v[it].w, v[it].z, sh), __builtin_amdgcn_alignbyte(w4[it], v[it].w, sh)};
+      *reinterpret_cast<v4u*>(o + c_lo[it]) = q;
+      continue;
+    }
+    int jj = j[it];
+    int y = c_lo[it] - lo;
+    for (int x = c_lo[it]; x < c_hi[it]; ++x, ++y) {
+      while (jj + 1 < cnt && start[jj + 1] <= y) ++jj;
+      const int r = y - start[jj];
+      uint8_t byte;
+      if (r < kPrefix) {
+        const uint32_t len = static_cast<uint32_t>(start[jj + 1] - start[jj] - kPrefix);
+        byte = static_cast<uint8_t>(len >> (8 * (3 - r)));
+      } else {
+        byte = V[src[jj] + r - kPrefix];
+      }
+      o[x] = byte;
+    }
+  }
+}
+
+__global__ __launch_bounds__(kRxThreads) void remux_copy_kernel(
+    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
+    const int64_t* __restrict__ tile_prefix, int nseg, int64_t max_nal, int64_t max_aframes,
+    const int32_t* __restrict__ scratch, const int64_t* __restrict__ rinfo, uint8_t* __restrict__ out,
+    const int64_t* __restrict__ out_off) {
+  const int64_t gt = blockIdx.x;
+  const int seg = find_seg_wave(tile_prefix, nseg, gt);
+  const int b0 = static_cast<int>(gt - tile_prefix[seg]) * es::kRemuxTile;
+  const int64_t* ri = rinfo + static_cast<int64_t>(seg) * es::kRinfoWords;
+  const int P = static_cast<int>(ri[es::kVideoPayloadBytes]);
+  const int A0 = static_cast<int>(ri[es::kAudioBoxOffset]);
+  const int Q = static_cast<int>(ri[es::kAudioPayloadBytes]);
+  if (b0 >= A0 + 8 + Q) return;  // past the real output (A0 + 8 >= 8 + P)
+  const es::RemuxScratch part = es::remux_scratch(1, max_nal, max_aframes);
+  const int32_t* sc = scratch + static_cast<int64_t>(seg) * part.stride;
+  const int64_t off = es_off[seg];
+  const int64_t avail = es_numel - off;
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint8_t*>(es + off), 0, static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+  uint8_t* o = out + out_off[seg];
+  rx_copy_stream<4>(rsrc, es + off, o, b0, 8, 8 + P, sc + part.vstart, sc + part.vsrc, sc[0]);
+  rx_copy_stream<0>(rsrc, es + off, o, b0, A0 + 8, A0 + 8 + Q, sc + part.astart, sc + part.asrc, sc[1]);
+}
+
+hipError_t launch_remux(const RemuxArgs& a) {
+  if (a.nseg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(remux_plan_kernel, dim3(a.nseg), dim3(kRxThreads), 0, a.stream, a.es, a.es_off, a.cap, a.info,
+                     a.pes, a.max_pes, a.max_nal, a.nal, a.au, a.aframes, a.sinfo, a.max_aframes, a.scratch,
+                     a.vsamples, a.asamples, a.rinfo, a.out, a.out_off);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || a.total_tiles <= 0) return e;
+  hipLaunchKernelGGL(remux_copy_kernel, dim3(static_cast<unsigned>(a.total_tiles)), dim3(kRxThreads), 0, a.stream,
+                     a.es, a.es_numel, a.es_off, a.tile_prefix, a.nseg, a.max_nal, a.max_aframes, a.scratch, a.rinfo,
+                     a.out, a.out_off);
+  return hipGetLastError();
+}
+
+}  // namespace dev
+}  // namespace hlsp2p

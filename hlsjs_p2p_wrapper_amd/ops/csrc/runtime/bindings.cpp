@@ -22,6 +22,7 @@
 #include "es.hpp"
 #include "locator.hpp"
 #include "planner.hpp"
+#include "remux.hpp"
 #include "shm_control.hpp"
 #include "store.hpp"
 #include "ts.hpp"
@@ -385,6 +386,79 @@ PYBIND11_MODULE(_runtime, m) {
     fl["pps"] = int(es::kAuPps);
     fl["aud"] = int(es::kAuAud);
     m.attr("ES_AU_FLAGS") = fl;
+  }
+  // Batched CPU remux with the device kernels' layout (docs/REMUX.md): the inputs of index_batch, its
+  // four outputs, and per segment a region of remux_out_bytes(cap, max_nal) bytes of `out` at out_off.
+  //   vsamples: int32[B, max_pes, 5]; asamples: int32[B, max_aframes, 2]; rinfo: int64[B, 8]
+  m.def("remux_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
+                          int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au, Arr<int32_t> aframes,
+                          Arr<int64_t> sinfo, int64_t max_aframes, py::array vsamples, py::array asamples,
+                          py::array rinfo, py::array out, Arr<int64_t> out_off) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0 || max_aframes <= 0)
+      throw std::invalid_argument("remux_batch: max_pes, max_nal and max_aframes must be positive");
+    int32_t* vs = mut_ptr<int32_t>(vsamples, "vsamples");
+    int32_t* as = mut_ptr<int32_t>(asamples, "asamples");
+    int64_t* rp = mut_ptr<int64_t>(rinfo, "rinfo");
+    uint8_t* op = mut_ptr<uint8_t>(out, "out");
+    if (cap.size() != B || out_off.size() != B || info.size() < B * ts::kInfoWords ||
+        pes.size() < B * ts::kClasses * max_pes * 3 || nal.size() < B * max_nal * 4 || au.size() < B * max_pes * 4 ||
+        aframes.size() < B * max_pes * 2 || sinfo.size() < B * es::kSinfoWords ||
+        vsamples.size() < B * max_pes * es::kVsampleWords || asamples.size() < B * max_aframes * es::kAsampleWords ||
+        rinfo.size() < B * es::kRinfoWords)
+      throw std::invalid_argument("remux_batch: an argument is too small");
+    const int64_t* eo = es_off.data();
+    const int64_t* c = cap.data();
+    const int64_t* oo = out_off.data();
+    int64_t total = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (eo[b] < 0 || c[b] < 0 || eo[b] + c[b] > es.size()) throw std::invalid_argument("remux_batch: ES out of bounds");
+      if (oo[b] < 0 || oo[b] + es::remux_out_bytes(c[b], max_nal) > out.size())
+        throw std::invalid_argument("remux_batch: output region out of bounds");
+      total += c[b];
+    }
+    const uint8_t* e = es.data();
+    const int64_t* ip = info.data();
+    const int64_t* pp = pes.data();
+    const int32_t* np = nal.data();
+    const int32_t* up = au.data();
+    const int32_t* fp = aframes.data();
+    const int64_t* sp = sinfo.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      es::remux_segment(e + eo[b], c[b], ip + b * ts::kInfoWords, pp + b * ts::kClasses * max_pes * 3, max_pes, max_nal,
+                        np + b * max_nal * 4, up + b * max_pes * 4, fp + b * max_pes * 2, sp + b * es::kSinfoWords,
+                        max_aframes, vs + b * max_pes * es::kVsampleWords, as + b * max_aframes * es::kAsampleWords,
+                        rp + b * es::kRinfoWords, op + oo[b]);
+    }, total);
+  });
+  m.def("remux_out_bytes", py::vectorize(&es::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
+  m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
+    return es::remux_scratch(nseg, max_nal, max_aframes).end;
+  }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
+  m.attr("ES_RINFO_WORDS") = es::kRinfoWords;
+  m.attr("ES_DEFAULT_MAX_AFRAMES") = es::kDefaultMaxAframes;
+  m.attr("ES_REMUX_TILE") = es::kRemuxTile;
+  m.attr("ES_OUT_ALIGN") = es::kOutAlign;
+  {
+    py::dict d, st, fl;
+    d["status"] = int(es::kRStatus);
+    d["video_payload_bytes"] = int(es::kVideoPayloadBytes);
+    d["n_vsamples"] = int(es::kNumVsamples);
+    d["audio_box_offset"] = int(es::kAudioBoxOffset);
+    d["audio_payload_bytes"] = int(es::kAudioPayloadBytes);
+    d["n_aframes"] = int(es::kNumAframes);
+    d["video_base_dts"] = int(es::kVideoBaseDts);
+    d["audio_base_pts"] = int(es::kAudioBasePts);
+    m.attr("ES_RINFO") = d;
+    st["truncated"] = int64_t(es::kTruncated);
+    st["aframe_overflow"] = int64_t(es::kAframeOverflow);
+    st["bad_timestamps"] = int64_t(es::kBadTimestamps);
+    st["unsupported_video"] = int64_t(es::kRemuxUnsupportedVideo);
+    m.attr("ES_RSTATUS") = st;
+    fl["sync"] = int64_t(es::kSampleSync);
+    fl["non_sync"] = int64_t(es::kSampleNonSync);
+    m.attr("ES_SAMPLE_FLAGS") = fl;
   }
 
   // ------------------------------------------------------------------ store

@@ -210,5 +210,39 @@ HLSP2P_RULE AdtsWalk adts_walk(const uint8_t* A, int64_t start, int64_t end, boo
   r.used = static_cast<int32_t>(q - start);
   return r;
 }
+
+// ---- remux (docs/REMUX.md)
+// NAL types that go into an fMP4 sample.  H.264: slices, SEI, SPS, PPS (what hls.js pushes);
+// HEVC: everything but AUD, end of sequence, end of bitstream and filler data.
+HLSP2P_RULE bool nal_kept(bool hevc, int type) {
+  if (hevc) return type >= 0 && (type < 35 || type > 38);
+  return type == 1 || type == 5 || type == 6 || type == 7 || type == 8;
+}
+
+struct AdtsFrame {
+  int32_t len, hdr;  // whole frame and its header; len == 0: no frame at q
+};
+// The frame adts_walk would count at q of [.., end): the same sync, length and header rule.
+HLSP2P_RULE AdtsFrame adts_frame_at(const uint8_t* A, int64_t q, int64_t end) {
+  if (q + 7 > end || A[q] != 0xFF || (A[q + 1] & 0xF6) != 0xF0) return {0, 0};
+  const int32_t len = (int32_t(A[q + 3] & 3) << 11) | (int32_t(A[q + 4]) << 3) | (A[q + 5] >> 5);
+  const int32_t hdr = (A[q + 1] & 1) ? 7 : 9;
+  if (len < hdr || q + len > end) return {0, 0};
+  return {len, hdr};
+}
+
+// x - y as a sample duration (unsigned == true: 0 .. 2^31 - 1) or composition offset (the int32
+// range), exact for any int64 pair; fits == false: the caller stores 0 and flags bad_timestamps
+struct Delta32 { int32_t v; bool fits; };
+HLSP2P_RULE Delta32 delta32(int64_t x, int64_t y, bool non_negative) {
+  const uint64_t ux = static_cast<uint64_t>(x), uy = static_cast<uint64_t>(y);
+  if (x >= y) {
+    const uint64_t d = ux - uy;
+    return d <= 0x7fffffffu ? Delta32{static_cast<int32_t>(d), true} : Delta32{0, false};
+  }
+  const uint64_t d = uy - ux;
+  if (non_negative || d > 0x80000000u) return {0, false};
+  return {static_cast<int32_t>(-static_cast<int64_t>(d)), true};
+}
 }  // namespace es
 }  // namespace hlsp2p

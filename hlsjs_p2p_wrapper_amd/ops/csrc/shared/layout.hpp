@@ -70,6 +70,46 @@ struct IndexScratch { int64_t tile_cnt, tile_pre, pos, end; };
 constexpr IndexScratch index_scratch(int64_t total_tiles, int64_t nseg, int64_t max_nal) {
   return {0, total_tiles, 2 * total_tiles, 2 * total_tiles + nseg * (max_nal + 1)};
 }
+
+// ---- remux to fMP4 samples and mdat boxes (docs/REMUX.md)
+constexpr int kRinfoWords = 8;
+constexpr int64_t kDefaultMaxAframes = 1024;
+constexpr int kVsampleWords = 5;  // vsamples row: offset, size, duration, cts, flags
+constexpr int kAsampleWords = 2;  // asamples row: offset, size
+constexpr int kRemuxTile = 16384;  // output bytes per workgroup of the copy kernel
+constexpr int kOutAlign = 256;     // alignment of a segment's output region on the device
+constexpr int32_t kSampleSync = 0x02000000;     // sample_depends_on = 2
+constexpr int32_t kSampleNonSync = 0x01010000;  // sample_depends_on = 1, non-sync sample
+
+// rinfo[] row (int64), identical on host and device
+enum Rinfo : int {
+  kRStatus = 0,
+  kVideoPayloadBytes = 1,  // P
+  kNumVsamples = 2,
+  kAudioBoxOffset = 3,     // A0
+  kAudioPayloadBytes = 4,  // Q
+  kNumAframes = 5,         // true total, also when the table overflowed
+  kVideoBaseDts = 6,       // -1: no sample
+  kAudioBasePts = 7,       // -1: no audio PES
+};
+enum RemuxStatus : int64_t { kTruncated = 1, kAframeOverflow = 2, kBadTimestamps = 4, kRemuxUnsupportedVideo = 8 };
+
+// bytes of a segment's output region: each kept NAL trades a >= 3-byte start code for a 4-byte
+// length (P <= video bytes + recorded NALs), video + audio <= cap, two 8-byte box headers and
+// at most 15 bytes of padding in front of the audio box
+constexpr int64_t remux_out_bytes(int64_t cap, int64_t max_nal) { return cap + max_nal + 32; }
+// the video payload may take this much of the region; what is left holds the padding and the audio header
+constexpr int64_t remux_video_limit(int64_t cap, int64_t max_nal) { return cap + max_nal; }
+
+// scratch (int32), element offsets inside one segment's slice of `stride` elements:
+// [hdr: 8 | vstart: max_nal + 1 | vsrc: max_nal | astart: max_aframes + 1 | asrc: max_aframes]
+// hdr = (recorded NALs, recorded frames); *start are payload offsets with the total behind the
+// last row, *src the first body byte in the segment's ES
+struct RemuxScratch { int64_t vstart, vsrc, astart, asrc, stride, end; };
+constexpr RemuxScratch remux_scratch(int64_t nseg, int64_t max_nal, int64_t max_aframes) {
+  return {8, 9 + max_nal, 9 + 2 * max_nal, 10 + 2 * max_nal + max_aframes, 10 + 2 * (max_nal + max_aframes),
+          nseg * (10 + 2 * (max_nal + max_aframes))};
+}
 }  // namespace es
 
 // ---------------------------------------------------------------- CRC-32

@@ -94,6 +94,10 @@ def _default_config() -> Dict[str, Any]:
         # index NAL units, access units and ADTS frames of every fragment on the transmux
         # device (docs/ESINDEX.md): FRAG_PARSING_DATA gains "samples", FRAG_PARSED "independent"
         "indexSamples": False,
+        # remux every fragment to fragmented MP4 on the transmux device (docs/REMUX.md; implies the
+        # index): FRAG_PARSING_DATA carries the moof in "data1", the mdat device view in "data2",
+        # "startDTS" / "endDTS" and the sample count in "nb"
+        "remuxFmp4": False,
     }
 
 

@@ -769,7 +769,7 @@ class StreamController:
         ticket = getattr(payload, "swarm_verify", None)
         pipeline_for(dev, self.loop).submit(
             TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
-                        bool(self.hls.config.get("indexSamples"))))
+                        bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4"))))
 
     def _on_parsed(self, frag: Fragment, stats: Any, r: Any) -> None:  # r: dict-like transmux result
         hls = self.hls
@@ -825,7 +825,10 @@ class StreamController:
         end = start + dur
         # indexSamples: the fragment's sample index (ops/esindex.py) rides on the parsing events; a
         # result without one (a fleet player's: the columnar path does not index) leaves them as is
-        samples = r.get("samples") if hls.config.get("indexSamples") else None
+        # remuxFmp4: the fragment as fMP4 (ops/remux.py) takes the place of the raw ES on them: data1
+        # the moof, data2 the mdat on the device; its samples ride as under indexSamples
+        fmp4 = r.get("fmp4") if hls.config.get("remuxFmp4") else None
+        samples = r.get("samples") if fmp4 is not None or hls.config.get("indexSamples") else None
         if listening(Events.FRAG_PARSING_DATA):
             vdata = {"frag": frag, "type": "video", "startPTS": start, "endPTS": end,
                      "data1": r["video"], "nb": nv, "pts": (vfirst, vlast)}
@@ -834,6 +837,14 @@ class StreamController:
                      "pts": (info["audio_first_pts"], info["audio_last_pts"])}
             if samples is not None:
                 vdata["samples"] = adata["samples"] = samples
+            if fmp4 is not None:
+                for ev, track in ((vdata, fmp4["video"]), (adata, fmp4["audio"])):
+                    scale = track["timescale"] or 1
+                    ev["data1"] = track["moof"](frag.sn)
+                    ev["data2"] = track["mdat"]
+                    ev["nb"] = track["nb"]
+                    ev["startDTS"] = track["base"] / scale
+                    ev["endDTS"] = (track["base"] + track["duration"]) / scale
             hls.trigger(Events.FRAG_PARSING_DATA, vdata)
             hls.trigger(Events.FRAG_PARSING_DATA, adata)
         if listening(Events.FRAG_PARSED):

@@ -45,11 +45,11 @@ class TransmuxJob:
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
     code inside the compiled module."""
 
-    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index")
+    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
-                 index: bool = False) -> None:
+                 index: bool = False, remux: bool = False) -> None:
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -59,9 +59,12 @@ class TransmuxJob:
         # a received segment's pending CRC check (agent/node.py VerifyTicket: ``expect``,
         # ``report(ok)``): the batch verifies the bytes -- fused into the decrypt -- reports the
         # outcome, and a fragment that fails gets a ``verify_failed`` error result
-        self.index = index
+        self.index = index or remux
         # True: the batch also indexes this fragment's NAL units, access units and ADTS frames
         # (ops/esindex.py) and its result gains ``samples``
+        self.remux = remux
+        # True (implies ``index``): the batch also remuxes this fragment to fMP4 samples and mdat
+        # boxes (ops/remux.py) and its result gains ``fmp4``
 
     def __repr__(self) -> str:
         return f"TransmuxJob(key={'set' if self.key else None}, frag={self.frag!r})"
@@ -108,13 +111,13 @@ class _Columns:
     round keys ``drk[i]`` (``ops.aes.round_keys_le``) or, for the host, the raw key
     ``keys[i]``; ``expect`` (``None``: no checks) holds the CRC-32 fragment i's bytes must
     have, ``-1`` for no check; ``index`` (``None``: nobody) marks the fragments whose samples
-    are to be indexed."""
+    are to be indexed, ``remux`` those to be remuxed as well."""
 
-    __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index")
+    __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index", "remux")
 
     def __init__(self, src: torch.Tensor, offs: np.ndarray, nb: np.ndarray, enc: np.ndarray, iv: np.ndarray,
                  drk: Optional[np.ndarray] = None, keys: Any = None, expect: Optional[np.ndarray] = None,
-                 index: Optional[np.ndarray] = None) -> None:
+                 index: Optional[np.ndarray] = None, remux: Optional[np.ndarray] = None) -> None:
         self.src = src      # uint8 tensor on the pipeline's device
         self.offs = offs    # int64[n]
         self.nb = nb        # int64[n]
@@ -124,6 +127,7 @@ class _Columns:
         self.keys = keys    # n raw 16-byte keys (a list or uint8[n, 16]); read only where enc is set
         self.expect = expect  # int64[n]
         self.index = index  # bool[n]
+        self.remux = remux  # bool[n], a subset of index
 
 
 class MediaPipeline:
@@ -263,7 +267,8 @@ class MediaPipeline:
             expect[v] = [jobs[i].verify.expect & 0xFFFFFFFF for i in v]
         cols = _Columns(src, np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64), enc, iv, drk=drk,
                         keys=None if cuda else [j.key for j in jobs], expect=expect,
-                        index=_mask(n, [i for i, j in enumerate(jobs) if j.index]))
+                        index=_mask(n, [i for i, j in enumerate(jobs) if j.index]),
+                        remux=_mask(n, [i for i, j in enumerate(jobs) if j.remux]))
         self.timer.add("stage", time.perf_counter() - t0)
         return cols
 
@@ -278,7 +283,7 @@ class MediaPipeline:
         fragment is taken as clear.  ``expect[i] >= 0``: fragment i's bytes must have that
         CRC-32 (a peer's trailer, verified here instead of by the node); :meth:`complete_columns`
         reports the outcome.  ``tag`` comes back from :meth:`complete_columns`.  No fragment is
-        indexed (``TransmuxJob.index`` is the job form's)."""
+        indexed or remuxed (``TransmuxJob.index`` / ``.remux`` are the job form's)."""
         n = len(offs)
         if n == 0:
             return None
@@ -348,7 +353,7 @@ class MediaPipeline:
                 verify.append((rows[fused[0]], fused[1]))
         else:
             groups = self._host_groups(c, rows)
-        infos, host, index = [], [], []
+        infos, host, index, remux = [], [], [], []
         for idx, res, hinfo, hlens in groups:
             infos.append((idx, res, res.es_offs, hlens))
             host.append((hinfo, hlens))
@@ -360,13 +365,27 @@ class MediaPipeline:
                 from ..ops import esindex as _esx
 
                 ix = _esx.index_batch(res, c.nb[idx])
+                # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
+                # the index, its three tables on the same way to the host
+                if c.remux is not None and c.remux[idx].any():
+                    from ..ops import remux as _rmx
+
+                    out_offs, size = _rmx.layout_out(c.nb[idx], ix.nal.shape[1])
+                    rx = _rmx.remux_batch(res, ix, c.nb[idx],
+                                          torch.empty(size + ALIGN, dtype=torch.uint8, device=res.es.device), out_offs)
+                    remux.append((rx, _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)))
+                else:
+                    remux.append(None)
                 ix = (ix, _to_host(ix.sinfo))
+            else:
+                remux.append(None)
             index.append(ix)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
         return _Batch(None, infos=infos, host=host, event=ev, keep=keep, tag=tag, n=n, start=ev0,
-                      verify=verify or None, expect_mask=mask, index=index if any(index) else None)
+                      verify=verify or None, expect_mask=mask, index=index if any(index) else None,
+                      remux=remux if any(remux) else None)
 
     def _host_groups(self, c: _Columns, rows: np.ndarray) -> List[Any]:
         """The host backend: ``ops.aes.cbc_decrypt_batch`` over the encrypted rows, then
@@ -465,6 +484,11 @@ class MediaPipeline:
                 for k, i in enumerate(il):
                     if b.jobs[i].index:
                         results[i]["samples"] = Samples(srows[k], ix, k)
+                gr = b.remux[g] if b.remux is not None else None
+                if gr is not None:  # ... and those that asked for the remux
+                    for k, i in enumerate(il):
+                        if b.jobs[i].remux:
+                            results[i]["fmp4"] = Fmp4(gr, k, srows[k])
         self.timer.add("results", time.perf_counter() - t4)
         return results
 
@@ -593,6 +617,151 @@ class Samples:
         return f"Samples({fields})"
 
 
+class Fmp4Track:
+    """Read-only mapping of one remuxed track of a fragment: ``mdat`` (a device view of the whole
+    box, header included), ``samples`` (the filled device rows of the track's sample table),
+    ``nb`` (samples), ``base`` / ``duration`` / ``timescale`` (the fragment's decode time and
+    length in the track's units) and ``moof(sequence_number)`` (host bytes, built on first call)."""
+
+    __slots__ = ("_f", "_video", "_moofs")
+    _KEYS = ("mdat", "samples", "nb", "base", "duration", "timescale", "moof")
+
+    def __init__(self, f: "Fmp4", video: bool) -> None:
+        self._f = f
+        self._video = video
+        self._moofs: Dict[int, bytes] = {}
+
+    def _host_rows(self) -> np.ndarray:
+        f = self._f
+        if self._video:
+            return _np(f._g[2])[f._k, :self["nb"]]
+        rows = _np(f._g[3])[f._k]
+        return rows[:self["nb"]]
+
+    def moof(self, sequence_number: int) -> bytes:
+        from . import fmp4 as _fmp4
+
+        data = self._moofs.get(sequence_number)
+        if data is None:
+            f = self._f
+            if self._video:
+                data = _fmp4.video_moof(sequence_number, f._rinfo("video_base_dts"), self._host_rows())
+            else:
+                data = _fmp4.audio_moof(sequence_number, f._rinfo("audio_base_pts"), f._rate, self._host_rows())
+            self._moofs[sequence_number] = data
+        return data
+
+    def __getitem__(self, name: str):
+        from . import fmp4 as _fmp4
+
+        f = self._f
+        rx = f._g[0]
+        if name == "nb":
+            if self._video:
+                return f._rinfo("n_vsamples")
+            return int((_np(f._g[3])[f._k, :, 0] >= 0).sum())
+        if name == "mdat":
+            o = int(rx.out_offs[f._k]) + (0 if self._video else f._rinfo("audio_box_offset"))
+            return rx.out.narrow(0, o, 8 + f._rinfo("video_payload_bytes" if self._video else "audio_payload_bytes"))
+        if name == "samples":
+            return (rx.vsamples if self._video else rx.asamples)[f._k, :self["nb"]]
+        if name == "timescale":
+            return _fmp4.VIDEO_TIMESCALE if self._video else f._rate
+        if name == "base":
+            if self._video:
+                return max(f._rinfo("video_base_dts"), 0)
+            return _fmp4.audio_base(f._rinfo("audio_base_pts"), f._rate)
+        if name == "duration":
+            if self._video:
+                return int(self._host_rows()[:, 2].sum(dtype=np.int64))
+            return _fmp4.AAC_FRAME_SAMPLES * self["nb"]
+        if name == "moof":
+            return self.moof
+        raise KeyError(name)
+
+    def get(self, name: str, default=None):
+        try:
+            return self[name]
+        except KeyError:
+            return default
+
+    def keys(self):
+        return list(self._KEYS)
+
+    def items(self):
+        return ((k, self[k]) for k in self._KEYS)
+
+    def __contains__(self, name) -> bool:
+        return name in self._KEYS
+
+    def __iter__(self):
+        return iter(self._KEYS)
+
+    def __len__(self) -> int:
+        return len(self._KEYS)
+
+    def __repr__(self) -> str:
+        return f"Fmp4Track({'video' if self._video else 'audio'}, nb={self['nb']})"
+
+
+class Fmp4:
+    """Read-only mapping of one fragment's remux (``TransmuxJob.remux``): ``video`` and ``audio``
+    (:class:`Fmp4Track`) and the ``rinfo`` fields by name (:data:`ops.remux.RINFO`)."""
+
+    __slots__ = ("_g", "_k", "_rate", "_tracks")
+
+    def __init__(self, group, k: int, sinfo_row) -> None:
+        from ..ops.esindex import SINFO
+
+        self._g = group  # (Remuxed, host rinfo, host vsamples, host asamples) of the fragment's group
+        self._k = k
+        self._rate = sinfo_row[SINFO["audio_sample_rate"]]
+        self._tracks: Dict[str, Fmp4Track] = {}
+
+    def _rinfo(self, name: str) -> int:
+        from ..ops.remux import RINFO
+
+        return int(_np(self._g[1])[self._k, RINFO[name]])
+
+    def __getitem__(self, name: str):
+        from ..ops.remux import RINFO
+
+        if name in ("video", "audio"):
+            t = self._tracks.get(name)
+            if t is None:
+                t = self._tracks[name] = Fmp4Track(self, name == "video")
+            return t
+        if name in RINFO:
+            return self._rinfo(name)
+        raise KeyError(name)
+
+    def get(self, name: str, default=None):
+        try:
+            return self[name]
+        except KeyError:
+            return default
+
+    def keys(self):
+        from ..ops.remux import RINFO
+
+        return ["video", "audio", *RINFO]
+
+    def items(self):
+        return ((k, self[k]) for k in self.keys())
+
+    def __contains__(self, name) -> bool:
+        return name in self.keys()
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self) -> int:
+        return len(self.keys())
+
+    def __repr__(self) -> str:
+        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio')} })"
+
+
 @dataclass(eq=False)
 class _Batch:
     jobs: List[TransmuxJob]
@@ -607,6 +776,7 @@ class _Batch:
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
     index: Any = None  # per group of infos: (EsIndex, host sinfo rows) or None (no job of the batch asked: None)
+    remux: Any = None  # per group of infos: (Remuxed, host rinfo, vsamples, asamples) or None (nobody asked: None)
 
 
 _local = threading.local()
