@@ -101,7 +101,7 @@ void ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int
                          .aux = check<int32_t>(blk_sums, "aux", ws.aux),
                          .es = check<uint8_t>(es, "es"),
                          .es_off = check<int64_t>(es_off, "es_off", B),
-                         .pes = check<int64_t>(pes, "pes", B * ts::kClasses * max_pes * 3),
+                         .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
                          .max_pes = max_pes,
                          .info = check<int64_t>(info, "info", B * ts::kInfoWords),
                          .stream = stream()};
@@ -109,28 +109,40 @@ void ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int
   hip_ok(D::launch_ts_demux(a), "ts_demux launch");
 }
 
-// Sample index of a demuxed batch (es_index.hip): es / info / pes are ts_demux's outputs, cap the
-// host upper bound of each segment's ES bytes (the Python wrapper has checked es_off + cap
-// against es), tile_prefix the exclusive prefix of ceil(cap / es_index_tile_bytes()).
+// The demuxed batch es_index and remux share (launch.h EsBatch): es / info / pes are ts_demux's
+// outputs, cap the host upper bound of each segment's ES bytes (the Python wrapper has checked
+// es_off + cap against es), tile_prefix the exclusive prefix of the op's tiles per segment.
+// `before_tables` runs between the checks of pes and nal, where es_index checks its scratch.
+template <typename F>
+D::EsBatch es_batch(const Tensor& es, const Tensor& es_off, const Tensor& cap, const Tensor& tile_prefix,
+                    int64_t total_tiles, const Tensor& info, const Tensor& pes, int64_t max_pes, int64_t max_nal,
+                    const Tensor& nal, const Tensor& au, const Tensor& aframes, const Tensor& sinfo,
+                    F&& before_tables) {
+  const int64_t B = es_off.numel();
+  D::EsBatch b{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
+               .es_off = check<int64_t>(es_off, "es_off"),
+               .cap = check<int64_t>(cap, "cap", B),
+               .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
+               .nseg = static_cast<int>(B), .total_tiles = total_tiles,
+               .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+               .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+               .max_pes = max_pes, .max_nal = max_nal, .ix = {}, .stream = stream()};
+  before_tables();
+  b.ix = {check<int32_t>(nal, "nal", hlsp2p::table_words(B, max_nal, es_::kNalWords)),
+          check<int32_t>(au, "au", hlsp2p::table_words(B, max_pes, es_::kAuWords)),
+          check<int32_t>(aframes, "aframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+          check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords)};
+  return b;
+}
+
+// Sample index of a demuxed batch (es_index.hip): tile_prefix counts ceil(cap / es_index_tile_bytes()).
 void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
               int64_t max_pes, int64_t max_nal, Tensor scratch, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo) {
-  const int64_t B = es_off.numel();
   TORCH_CHECK(max_pes > 0 && max_nal > 0 && total_tiles >= 0, "es_index: max_pes / max_nal / total_tiles out of range");
-  const D::EsIndexArgs a{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
-                         .es_off = check<int64_t>(es_off, "es_off"),
-                         .cap = check<int64_t>(cap, "cap", B),
-                         .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
-                         .nseg = static_cast<int>(B), .total_tiles = total_tiles,
-                         .info = check<int64_t>(info, "info", B * ts::kInfoWords),
-                         .pes = check<int64_t>(pes, "pes", B * ts::kClasses * max_pes * 3),
-                         .max_pes = max_pes, .max_nal = max_nal,
-                         .scratch = check<int32_t>(scratch, "scratch",
-                                          es_::index_scratch(total_tiles, B, max_nal).end),
-                         .nal = check<int32_t>(nal, "nal", B * max_nal * 4),
-                         .au = check<int32_t>(au, "au", B * max_pes * 4),
-                         .aframes = check<int32_t>(aframes, "aframes", B * max_pes * 2),
-                         .sinfo = check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords),
-                         .stream = stream()};
+  D::EsIndexArgs a{};
+  a.b = es_batch(es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [&] {
+    a.scratch = check<int32_t>(scratch, "scratch", es_::index_scratch(total_tiles, es_off.numel(), max_nal).end);
+  });
   TORCH_CHECK(es.device() == sinfo.device(), "tensors on different devices");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0, "es must be 16-byte aligned");
   hip_ok(D::launch_es_index(a), "es_index launch");
@@ -138,35 +150,22 @@ void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t 
 
 // Remux of a demuxed and indexed batch (remux.hip): the inputs of es_index, its four outputs, and
 // per segment a region of es::remux_out_bytes(cap, max_nal) bytes of `out` at out_off (the Python
-// wrapper has checked the regions against out); tile_prefix is the exclusive prefix of
-// ceil(region / remux_tile_bytes()).
+// wrapper has checked the regions against out); tile_prefix counts ceil(region / remux_tile_bytes()).
 void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
            int64_t max_pes, int64_t max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_aframes,
            Tensor scratch, Tensor vsamples, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off) {
   const int64_t B = es_off.numel();
   TORCH_CHECK(max_pes > 0 && max_nal > 0 && max_aframes > 0 && total_tiles >= 0,
               "remux: max_pes / max_nal / max_aframes / total_tiles out of range");
-  const D::RemuxArgs a{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
-                       .es_off = check<int64_t>(es_off, "es_off"),
-                       .cap = check<int64_t>(cap, "cap", B),
-                       .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
-                       .nseg = static_cast<int>(B), .total_tiles = total_tiles,
-                       .info = check<int64_t>(info, "info", B * ts::kInfoWords),
-                       .pes = check<int64_t>(pes, "pes", B * ts::kClasses * max_pes * 3),
-                       .max_pes = max_pes, .max_nal = max_nal,
-                       .nal = check<int32_t>(nal, "nal", B * max_nal * 4),
-                       .au = check<int32_t>(au, "au", B * max_pes * 4),
-                       .aframes = check<int32_t>(aframes, "aframes", B * max_pes * 2),
-                       .sinfo = check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords),
-                       .max_aframes = max_aframes,
-                       .scratch = check<int32_t>(scratch, "scratch",
-                                        es_::remux_scratch(B, max_nal, max_aframes).end),
-                       .vsamples = check<int32_t>(vsamples, "vsamples", B * max_pes * es_::kVsampleWords),
-                       .asamples = check<int32_t>(asamples, "asamples", B * max_aframes * es_::kAsampleWords),
-                       .rinfo = check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords),
-                       .out = check<uint8_t>(out, "out"),
-                       .out_off = check<int64_t>(out_off, "out_off", B),
-                       .stream = stream()};
+  const D::RemuxArgs a{
+      .b = es_batch(es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .max_aframes = max_aframes,
+      .scratch = check<int32_t>(scratch, "scratch", es_::remux_scratch(B, max_nal, max_aframes).end),
+      .t = {check<int32_t>(vsamples, "vsamples", hlsp2p::table_words(B, max_pes, es_::kVsampleWords)),
+            check<int32_t>(asamples, "asamples", hlsp2p::table_words(B, max_aframes, es_::kAsampleWords)),
+            check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
+      .out = check<uint8_t>(out, "out"),
+      .out_off = check<int64_t>(out_off, "out_off", B)};
   TORCH_CHECK(es.device() == out.device() && es.device() == rinfo.device(), "tensors on different devices");
   TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
                   (reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0,

@@ -12,23 +12,27 @@ __device__ __forceinline__ int advance_seg(const int64_t* __restrict__ prefix, i
   return s;
 }
 
-// Largest s in [0, n) with prefix[s] <= v (prefix has n + 1 entries, ascending) for a
-// wave-uniform v, with all 64 lanes active: each lane tests
-// one prefix entry and a ballot counts the entries <= v, so segment lookup costs ONE
-// global round trip per 64-way level (n <= 64: one) instead of log2(n) dependent loads
-// at the head of every workgroup.
-__device__ __forceinline__ int find_seg_wave(const int64_t* __restrict__ prefix, int n, int64_t v) {
+// Largest j in [0, n) with t[j] <= v (t ascends, t[0] <= v) for a wave-uniform v, with all 64
+// lanes active: each lane tests one row and a ballot counts the rows <= v, so the lookup costs
+// ONE global round trip per 64-way level (n <= 64: one, n <= 4096: two) instead of log2(n)
+// dependent loads at the head of every workgroup.
+template <typename T>
+__device__ __forceinline__ int last_le_wave(const T* __restrict__ t, int n, T v) {
   const int lane = static_cast<int>(threadIdx.x & 63);
   int lo = 0, cnt = n;  // answer in [lo, lo + cnt)
   while (cnt > 64) {
     const int stride = (cnt + 63) >> 6;
     const int idx = lo + lane * stride;
-    const bool le = idx < lo + cnt && prefix[idx] <= v;
+    const bool le = idx < lo + cnt && t[idx] <= v;
     lo += (__popcll(__ballot(le)) - 1) * stride;
     cnt = stride < n - lo ? stride : n - lo;
   }
-  const bool le = lane < cnt && prefix[lo + lane] <= v;
+  const bool le = lane < cnt && t[lo + lane] <= v;
   return __builtin_amdgcn_readfirstlane(lo + __popcll(__ballot(le)) - 1);
+}
+// The segment of tile (block, chunk) v: prefix has n + 1 ascending entries.
+__device__ __forceinline__ int find_seg_wave(const int64_t* __restrict__ prefix, int n, int64_t v) {
+  return last_le_wave(prefix, n, v);
 }
 
 // Inclusive prefix sum over the wave64 in six DPP-modified moves and adds, no LDS traffic

@@ -2,10 +2,10 @@
 //
 // Input: what ts_demux.hip leaves in HBM (ES bytes, PES tables, info rows).  Output per
 // segment, identical to the host implementation runtime/es.cpp index_segment:
-//   nal:     int32[seg][max_nal][4] = (offset, length, type, access unit)   (-1 rows beyond)
-//   au:      int32[seg][max_pes][4] = (first NAL, NAL count, flags, size)    (-1 rows beyond)
-//   aframes: int32[seg][max_pes][2] = (ADTS frames, bytes consumed) per audio PES
-//   sinfo:   int64[seg][8]
+//   nal:     int32[seg][max_nal][kNalWords]   (NalRow: offset, length, type, access unit; -1 rows beyond)
+//   au:      int32[seg][max_pes][kAuWords]    (AuRow: first NAL, NAL count, flags, size; -1 rows beyond)
+//   aframes: int32[seg][max_pes][kApesWords]  (ApesRow: ADTS frames, bytes consumed, per audio PES)
+//   sinfo:   int64[seg][kSinfoWords]
 //
 // Four launches on the caller's stream, no host round trip (the video ES lengths come from
 // the demux's info rows; host caps size the tile space and bound every access):
@@ -40,7 +40,7 @@ int es_index_tile_bytes() { return kEsTile; }
 
 // bytes of video ES to index: 0 for an unsupported codec, never beyond the host cap
 __device__ __forceinline__ int64_t es_video_len(const int64_t* __restrict__ inf, int64_t cap) {
-  return es::video_supported(inf[ts::kVideoType]) ? clamp(inf[ts::kVideoBytes], 0, cap) : 0;
+  return es::video_span(inf, cap).len;
 }
 
 // 0x80 in every byte of x that is zero (exact: no carry leaves a byte)
@@ -194,21 +194,20 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
     int32_t* __restrict__ af_all, int64_t* __restrict__ sinfo) {
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
-  const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
-  int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
-  const int64_t room = cap[seg];
-  const uint8_t* V = es + es_off[seg];
-  const int64_t n = es_video_len(inf, room);
+  const es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);  // cap as the wrapper checked it
+  const es::IndexTables<int32_t, int64_t> tb = es::index_tables_at<int32_t, int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
+  int64_t* si = tb.sinfo;
+  const uint8_t* V = sg.es;
+  const es::VideoSpan video = es::video_span(sg);
+  const int64_t n = video.len;
   const int64_t n_nal = si[es::kNumNal];
   const int nn = static_cast<int>(n_nal < max_nal ? n_nal : max_nal);
-  const bool hevc = es::is_hevc(inf[ts::kVideoType]);
-  const int m = es::video_supported(inf[ts::kVideoType]) ? static_cast<int>(clamp(inf[ts::kNumVideoPes], 0, max_pes)) : 0;
-  const int64_t* vp = pes + static_cast<int64_t>(seg) * 3 * max_pes * 3;  // class 0
-  const int64_t* ap = vp + max_pes * 3;                                      // class 1
+  const bool hevc = video.hevc;
+  const int m = static_cast<int>(es::video_rows(video, sg.info[ts::kNumVideoPes], max_pes));  // the demux's count: one unit per PES
+  const es::PesRows rows = es::pes_rows(sg);
+  const int64_t *vp = rows.video, *ap = rows.audio;
   const int32_t* pos = pos_all + static_cast<int64_t>(seg) * (max_nal + 1);
-  int32_t* nal = nal_all + static_cast<int64_t>(seg) * max_nal * 4;
-  int32_t* au = au_all + static_cast<int64_t>(seg) * max_pes * 4;
-  int32_t* af = af_all + static_cast<int64_t>(seg) * max_pes * 2;
+  int32_t *nal = tb.nal, *au = tb.au, *af = tb.aframes;
 
   // ---- a lane per NAL row
   for (int64_t k = tid; k < max_nal; k += kEsThreads) {
@@ -225,17 +224,18 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
       int a_lo = 0, a_hi = m;  // AU: largest a < m with offset <= s, else -1
       while (a_lo < a_hi) {
         const int mid = (a_lo + a_hi) >> 1;
-        if (vp[3 * mid] <= s) a_lo = mid + 1; else a_hi = mid;
+        if (es::pes_at(vp, mid, ts::kPesEsOffset) <= s) a_lo = mid + 1; else a_hi = mid;
       }
       r0 = static_cast<int32_t>(s);
       r1 = static_cast<int32_t>(e - s);
       r2 = e == s ? -1 : es::nal_type(hevc, hb);
       r3 = a_lo - 1;
     }
-    nal[4 * k] = r0;
-    nal[4 * k + 1] = r1;
-    nal[4 * k + 2] = r2;
-    nal[4 * k + 3] = r3;
+    int32_t* row = nal + es::kNalWords * k;
+    row[es::kNalOffset] = r0;
+    row[es::kNalLength] = r1;
+    row[es::kNalType] = r2;
+    row[es::kNalAu] = r3;
   }
   __syncthreads();  // NAL rows of this segment are visible to the whole workgroup
 
@@ -243,21 +243,22 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   for (int64_t a = tid; a < max_pes; a += kEsThreads) {
     int32_t r0 = -1, r1 = -1, r2 = -1, r3 = -1;
     if (a < m) {
-      const int64_t o = vp[3 * a];
-      const int64_t o_next = a + 1 < m ? vp[3 * (a + 1)] : n;
+      const int64_t o = es::pes_at(vp, a, ts::kPesEsOffset);
+      const int64_t o_next = a + 1 < m ? es::pes_at(vp, a + 1, ts::kPesEsOffset) : n;
       const int first = es_first_nal_at(pos, nn, o);
       const int end = a + 1 < m ? es_first_nal_at(pos, nn, o_next) : nn;
       int flags = 0;
-      for (int k = first; k < end; ++k) flags |= es::nal_flags(hevc, nal[4 * k + 2]);
+      for (int k = first; k < end; ++k) flags |= es::nal_flags(hevc, nal[es::kNalWords * k + es::kNalType]);
       r1 = end > first ? end - first : 0;
       r0 = r1 > 0 ? first : -1;
       r2 = flags;
       r3 = static_cast<int32_t>(o_next - o);
     }
-    au[4 * a] = r0;
-    au[4 * a + 1] = r1;
-    au[4 * a + 2] = r2;
-    au[4 * a + 3] = r3;
+    int32_t* row = au + es::kAuWords * a;
+    row[es::kAuFirstNal] = r0;
+    row[es::kAuNalCount] = r1;
+    row[es::kAuFlags] = r2;
+    row[es::kAuSize] = r3;
   }
   __syncthreads();
   if (tid >= 64) return;
@@ -266,29 +267,26 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   const int lane = tid;
   int n_key = 0, first_key = 0x7fffffff;
   for (int a = lane; a < m; a += 64) {
-    if (au[4 * a + 2] & es::kAuKeyframe) {
+    if (au[es::kAuWords * a + es::kAuFlags] & es::kAuKeyframe) {
       ++n_key;
       if (a < first_key) first_key = a;
     }
   }
-  const int64_t a_off = clamp(inf[ts::kAudioEsOffset], 0, room);
-  const int64_t a_len = clamp(inf[ts::kAudioBytes], 0, room - a_off);
-  const uint8_t* A = V + a_off;
-  const int ma = es::is_adts(inf[ts::kAudioType]) ? static_cast<int>(clamp(inf[ts::kNumAudioPes], 0, max_pes)) : 0;
+  const es::AudioSpan audio = es::audio_span(sg);
+  const uint8_t* A = V + audio.off;
   int n_frames = 0, err = 0, rate = 0, chans = 0;
   for (int64_t k = lane; k < max_pes; k += 64) {
     int32_t frames = -1, used = -1;
-    if (k < ma) {
-      const int64_t start = clamp(ap[3 * k], 0, a_len);
-      const int64_t end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
-      const es::AdtsWalk w = es::adts_walk(A, start, end, k == 0, rate, chans);
+    if (k < audio.n_adts) {
+      const es::ByteRange r = es::audio_pes_range(ap, k, audio);
+      const es::AdtsWalk w = es::adts_walk(A, r.start, r.end, k == 0, rate, chans);
       frames = w.frames;
       used = w.used;
       err |= w.error;
       n_frames += frames;
     }
-    af[2 * k] = frames;
-    af[2 * k + 1] = used;
+    af[es::kApesWords * k + es::kApesFrames] = frames;
+    af[es::kApesWords * k + es::kApesUsed] = used;
   }
   n_key = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(wave_scan_dpp(n_key)), 63));
   n_frames = static_cast<int>(__builtin_amdgcn_readlane(static_cast<int>(wave_scan_dpp(n_frames)), 63));
@@ -308,12 +306,13 @@ __global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
   }
 }
 
-hipError_t launch_es_index(const EsIndexArgs& a) {
+hipError_t launch_es_index(const EsIndexArgs& args) {
+  const EsBatch& a = args.b;
   if (a.nseg <= 0) return hipSuccess;
   const es::IndexScratch part = es::index_scratch(a.total_tiles, a.nseg, a.max_nal);
-  int32_t* tile_cnt = a.scratch + part.tile_cnt;
-  int32_t* tile_pre = a.scratch + part.tile_pre;
-  int32_t* pos = a.scratch + part.pos;
+  int32_t* tile_cnt = args.scratch + part.tile_cnt;
+  int32_t* tile_pre = args.scratch + part.tile_pre;
+  int32_t* pos = args.scratch + part.pos;
   const dim3 tiles(static_cast<unsigned>(a.total_tiles));
   hipError_t e = hipSuccess;
   if (a.total_tiles > 0) {
@@ -323,7 +322,7 @@ hipError_t launch_es_index(const EsIndexArgs& a) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(es_prefix_kernel, dim3(a.nseg), dim3(64), 0, a.stream, a.tile_prefix, tile_cnt, tile_pre, a.info,
-                     a.max_nal, a.sinfo);
+                     a.max_nal, a.ix.sinfo);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (a.total_tiles > 0) {
@@ -333,7 +332,7 @@ hipError_t launch_es_index(const EsIndexArgs& a) {
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL(es_finish_kernel, dim3(a.nseg), dim3(kEsThreads), 0, a.stream, a.es, a.es_off, a.cap, a.info,
-                     a.pes, a.max_pes, a.max_nal, pos, a.nal, a.au, a.aframes, a.sinfo);
+                     a.pes, a.max_pes, a.max_nal, pos, a.ix.nal, a.ix.au, a.ix.aframes, a.ix.sinfo);
   return hipGetLastError();
 }
 

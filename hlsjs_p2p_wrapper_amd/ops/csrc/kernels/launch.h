@@ -93,7 +93,9 @@ struct TsDemuxArgs {
 };
 hipError_t launch_ts_demux(const TsDemuxArgs& a);
 
-struct EsIndexArgs {
+// A demuxed batch as the index and the remux take it: launch_ts_demux's outputs, the host caps
+// and a tile space over them, and the batch's four index tables.
+struct EsBatch {
   const uint8_t* es;
   int64_t es_numel;
   const int64_t *es_off, *cap, *tile_prefix;
@@ -101,31 +103,24 @@ struct EsIndexArgs {
   int64_t total_tiles;
   const int64_t *info, *pes;
   int64_t max_pes, max_nal;
-  int32_t* scratch;  // es::index_scratch(total_tiles, nseg, max_nal)
-  int32_t *nal, *au, *aframes;
-  int64_t* sinfo;
+  es::IndexTables<int32_t, int64_t> ix;
   hipStream_t stream;
+};
+
+struct EsIndexArgs {
+  EsBatch b;         // tiles of cap; ix is written
+  int32_t* scratch;  // es::index_scratch(total_tiles, nseg, max_nal)
 };
 int es_index_tile_bytes();
 hipError_t launch_es_index(const EsIndexArgs& a);
 
 struct RemuxArgs {
-  const uint8_t* es;
-  int64_t es_numel;
-  const int64_t *es_off, *cap, *tile_prefix;  // tiles of es::remux_out_bytes(cap, max_nal)
-  int nseg;
-  int64_t total_tiles;
-  const int64_t *info, *pes;
-  int64_t max_pes, max_nal;
-  const int32_t *nal, *au, *aframes;  // launch_es_index's outputs
-  const int64_t* sinfo;
+  EsBatch b;  // tiles of es::remux_out_bytes(cap, max_nal); ix is launch_es_index's output, only read
   int64_t max_aframes;
   int32_t* scratch;  // es::remux_scratch(nseg, max_nal, max_aframes)
-  int32_t *vsamples, *asamples;
-  int64_t* rinfo;
+  es::RemuxTables t;
   uint8_t* out;
   const int64_t* out_off;
-  hipStream_t stream;
 };
 int remux_tile_bytes();
 hipError_t launch_remux(const RemuxArgs& a);

@@ -3,9 +3,9 @@
 //
 // Input: what ts_demux.hip and es_index.hip leave in HBM.  Output per segment, identical to the
 // host implementation runtime/remux.cpp remux_segment:
-//   vsamples: int32[seg][max_pes][5]     = (offset, size, duration, cts, flags)   (-1 rows beyond)
-//   asamples: int32[seg][max_aframes][2] = (offset, size)                         (-1 rows beyond)
-//   rinfo:    int64[seg][8]
+//   vsamples: int32[seg][max_pes][kVsampleWords]      (VsampleRow: offset, size, duration, cts, flags; -1 rows beyond)
+//   asamples: int32[seg][max_aframes][kAsampleWords]  (AsampleRow: offset, size; -1 rows beyond)
+//   rinfo:    int64[seg][kRinfoWords]
 //   out:      at out_off[seg]: 'mdat' box of the video payload (4-byte length + NAL bytes per
 //             kept NAL), then at the next multiple of 16 the 'mdat' box of the ADTS frame bodies
 //
@@ -79,22 +79,22 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
   __shared__ int s_bad, s_nrec, s_q, s_aover;
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
-  const int64_t* inf = info + static_cast<int64_t>(seg) * ts::kInfoWords;
-  const int64_t* si = sinfo + static_cast<int64_t>(seg) * es::kSinfoWords;
-  const int64_t room_es = clamp(cap[seg], 0, 0x7fffffff);
-  const uint8_t* V = es + es_off[seg];
-  const int64_t vtype = inf[ts::kVideoType];
-  const bool supported = es::video_supported(vtype);
-  const bool hevc = es::is_hevc(vtype);
-  const int64_t R = supported ? clamp(si[es::kNumNal], 0, max_nal) : 0;
-  const int64_t m = supported ? clamp(si[es::kNumAu], 0, max_pes) : 0;
-  const int64_t* vp = pes + static_cast<int64_t>(seg) * ts::kClasses * max_pes * 3;  // class 0
-  const int64_t* ap = vp + max_pes * 3;                                               // class 1
-  const int32_t* nal = nal_all + static_cast<int64_t>(seg) * max_nal * 4;
-  const int32_t* au = au_all + static_cast<int64_t>(seg) * max_pes * 4;
-  const int32_t* af = af_all + static_cast<int64_t>(seg) * max_pes * 2;
-  int32_t* vs = vs_all + static_cast<int64_t>(seg) * max_pes * es::kVsampleWords;
-  int32_t* as = as_all + static_cast<int64_t>(seg) * max_aframes * es::kAsampleWords;
+  es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
+  sg.cap = clamp(sg.cap, 0, 0x7fffffff);  // offsets inside the segment are kept in int32 scratch rows
+  const es::IndexTables<const int32_t, const int64_t> ix =
+      es::index_tables_at<const int32_t, const int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
+  const es::RemuxTables tb = es::remux_tables_at({vs_all, as_all, rinfo}, sg, max_aframes, seg);
+  const int64_t* si = ix.sinfo;
+  const int64_t room_es = sg.cap;
+  const uint8_t* V = sg.es;
+  const es::VideoSpan video = es::video_span(sg);
+  const bool supported = video.supported, hevc = video.hevc;
+  const int64_t R = es::video_rows(video, si[es::kNumNal], max_nal);
+  const int64_t m = es::video_rows(video, si[es::kNumAu], max_pes);  // the index's count, not the demux's
+  const es::PesRows rows = es::pes_rows(sg);
+  const int64_t *vp = rows.video, *ap = rows.audio;
+  const int32_t *nal = ix.nal, *au = ix.au, *af = ix.aframes;
+  int32_t *vs = tb.vsamples, *as = tb.asamples;
   const es::RemuxScratch part = es::remux_scratch(1, max_nal, max_aframes);
   int32_t* sc = scratch + static_cast<int64_t>(seg) * part.stride;
   int32_t* vstart = sc + part.vstart;
@@ -118,26 +118,27 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
     int32_t r0 = -1, r1 = -1, r2 = -1, r3 = -1, r4 = -1;
     if (a < m) {
       es::Delta32 dur = {0, true};
-      if (a + 1 < m) dur = es::delta32(vp[3 * (a + 1) + 2], vp[3 * a + 2], true);
-      else if (m > 1) dur = es::delta32(vp[3 * a + 2], vp[3 * (a - 1) + 2], true);
-      const es::Delta32 cts = es::delta32(vp[3 * a + 1], vp[3 * a + 2], false);
+      const int64_t dts = es::pes_at(vp, a, ts::kPesDts);
+      if (a + 1 < m) dur = es::delta32(es::pes_at(vp, a + 1, ts::kPesDts), dts, true);
+      else if (m > 1) dur = es::delta32(dts, es::pes_at(vp, a - 1, ts::kPesDts), true);
+      const es::Delta32 cts = es::delta32(es::pes_at(vp, a, ts::kPesPts), dts, false);
       bad |= !dur.fits || !cts.fits;
       r0 = 0;
       r1 = 0;
       r2 = dur.v;
       r3 = cts.v;
-      r4 = (au[4 * a + 2] & es::kAuKeyframe) ? es::kSampleSync : es::kSampleNonSync;
+      r4 = (au[es::kAuWords * a + es::kAuFlags] & es::kAuKeyframe) ? es::kSampleSync : es::kSampleNonSync;
     }
     int32_t* row = vs + a * es::kVsampleWords;
-    row[0] = r0;
-    row[1] = r1;
-    row[2] = r2;
-    row[3] = r3;
-    row[4] = r4;
+    row[es::kVsOffset] = r0;
+    row[es::kVsSize] = r1;
+    row[es::kVsDuration] = r2;
+    row[es::kVsCts] = r3;
+    row[es::kVsFlags] = r4;
   }
   for (int64_t f = tid; f < max_aframes; f += kRxThreads) {
-    as[2 * f] = -1;
-    as[2 * f + 1] = -1;
+    as[es::kAsampleWords * f + es::kAsOffset] = -1;
+    as[es::kAsampleWords * f + es::kAsSize] = -1;
   }
   __syncthreads();  // rows and the shared words are set
   if (bad) atomicOr(&s_bad, 1);
@@ -148,10 +149,11 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
     const int64_t k = kb + tid;
     int64_t ob = 0, s = 0, a = -1;
     if (k < R) {
-      s = clamp(nal[4 * k], 0, room_es);
-      const int64_t len = clamp(nal[4 * k + 1], 0, room_es - s);
-      a = nal[4 * k + 3];
-      if (a >= 0 && a < m && len > 0 && es::nal_kept(hevc, nal[4 * k + 2])) ob = 4 + len;
+      const int32_t* row = nal + es::kNalWords * k;
+      s = clamp(row[es::kNalOffset], 0, room_es);
+      const int64_t len = clamp(row[es::kNalLength], 0, room_es - s);
+      a = row[es::kNalAu];
+      if (a >= 0 && a < m && len > 0 && es::nal_kept(hevc, row[es::kNalType])) ob = 4 + len;
     }
     int64_t total;
     const int64_t d = carry + rx_block_scan(ob, s_w, total);
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
       vstart[k] = rx_sat32(d);
       vsrc[k] = static_cast<int32_t>(s);
       if (ob > 0) {
-        if (d + ob <= v_limit) atomicAdd(&vs[a * es::kVsampleWords + 1], static_cast<int32_t>(ob));
+        if (d + ob <= v_limit) atomicAdd(&vs[a * es::kVsampleWords + es::kVsSize], static_cast<int32_t>(ob));
         else atomicMin(&s_first_unfit, static_cast<unsigned long long>(d));
       }
     }
@@ -174,29 +176,28 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
   int64_t acarry = 0;
   for (int64_t ab = 0; ab < m; ab += kRxThreads) {
     const int64_t a = ab + tid;
-    const int64_t sz = a < m ? vs[a * es::kVsampleWords + 1] : 0;
+    const int64_t sz = a < m ? vs[a * es::kVsampleWords + es::kVsSize] : 0;
     int64_t total;
     const int64_t off = acarry + rx_block_scan(sz, s_w, total);
     acarry += total;
-    if (a < m) vs[a * es::kVsampleWords] = static_cast<int32_t>(off);
+    if (a < m) vs[a * es::kVsampleWords + es::kVsOffset] = static_cast<int32_t>(off);
   }
 
   // ---- audio: a lane per PES walks its counted frames, twice around the scan of the totals
   const int64_t A0 = (8 + P + 15) & ~int64_t(15);
   const int64_t a_room = region - (A0 + 8);
-  const int64_t ma_all = clamp(inf[ts::kNumAudioPes], 0, max_pes);
-  const int64_t ma = es::is_adts(inf[ts::kAudioType]) ? ma_all : 0;
-  const int64_t a_off = clamp(inf[ts::kAudioEsOffset], 0, room_es);
-  const int64_t a_len = clamp(inf[ts::kAudioBytes], 0, room_es - a_off);
+  const es::AudioSpan audio = es::audio_span(sg);
+  const int64_t ma = audio.n_adts, a_off = audio.off;
   const uint8_t* A = V + a_off;
   int64_t fcarry = 0, bcarry = 0;
   for (int64_t kb = 0; kb < ma; kb += kRxThreads) {
     const int64_t k = kb + tid;
     int64_t start = 0, end = 0, want = 0, cnt = 0, bytes = 0;
     if (k < ma) {
-      start = clamp(ap[3 * k], 0, a_len);
-      end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
-      want = af[2 * k];
+      const es::ByteRange r = es::audio_pes_range(ap, k, audio);
+      start = r.start;
+      end = r.end;
+      want = af[es::kApesWords * k + es::kApesFrames];
       int64_t q = start;
       for (; cnt < want; ++cnt) {
         const es::AdtsFrame f = es::adts_frame_at(A, q, end);
@@ -217,8 +218,8 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
       const es::AdtsFrame f = es::adts_frame_at(A, q, end);
       const int64_t size = f.len - f.hdr;
       if (fi < max_aframes && bo + size <= a_room) {  // a prefix of the frames: both sides only grow
-        as[2 * fi] = static_cast<int32_t>(bo);
-        as[2 * fi + 1] = static_cast<int32_t>(size);
+        as[es::kAsampleWords * fi + es::kAsOffset] = static_cast<int32_t>(bo);
+        as[es::kAsampleWords * fi + es::kAsSize] = static_cast<int32_t>(size);
         astart[fi] = static_cast<int32_t>(bo);
         asrc[fi] = static_cast<int32_t>(a_off + q + f.hdr);
         ++nrec;
@@ -254,15 +255,15 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
     if ((si[es::kStatus] & es::kNalOverflow) || v_cut) status |= es::kTruncated;
     if (s_aover) status |= es::kAframeOverflow;
     if (s_bad) status |= es::kBadTimestamps;
-    int64_t* ri = rinfo + static_cast<int64_t>(seg) * es::kRinfoWords;
+    int64_t* ri = tb.rinfo;
     ri[es::kRStatus] = status;
     ri[es::kVideoPayloadBytes] = P;
     ri[es::kNumVsamples] = m;
     ri[es::kAudioBoxOffset] = A0;
     ri[es::kAudioPayloadBytes] = Q;
     ri[es::kNumAframes] = fcarry;
-    ri[es::kVideoBaseDts] = m > 0 ? vp[2] : -1;
-    ri[es::kAudioBasePts] = ma_all > 0 ? ap[1] : -1;
+    ri[es::kVideoBaseDts] = m > 0 ? es::pes_at(vp, 0, ts::kPesDts) : -1;
+    ri[es::kAudioBasePts] = audio.n_pes > 0 ? es::pes_at(ap, 0, ts::kPesPts) : -1;
   }
 }
 
@@ -274,25 +275,6 @@ __device__ __forceinline__ int rx_last_le(const int32_t* __restrict__ t, int lo,
     if (t[mid] <= y) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// The same for a workgroup-uniform y with all 64 lanes of the wave active, over rows [0, cnt): each
-// lane tests one row and a ballot counts the rows <= y, so the lookup costs one global round trip
-// per 64-way level (two up to 4096 rows) instead of log2(cnt) dependent loads at the head of
-// every workgroup (find_seg_wave's scheme, on int32 rows).
-__device__ __forceinline__ int rx_last_le_wave(const int32_t* __restrict__ t, int cnt, int y) {
-  const int lane = static_cast<int>(threadIdx.x & 63);
-  const int n = cnt;
-  int lo = 0;
-  while (cnt > 64) {
-    const int stride = (cnt + 63) >> 6;
-    const int idx = lo + lane * stride;
-    const bool le = idx < lo + cnt && t[idx] <= y;
-    lo += (__popcll(__ballot(le)) - 1) * stride;
-    cnt = stride < n - lo ? stride : n - lo;
-  }
-  const bool le = lane < cnt && t[lo + lane] <= y;
-  return __builtin_amdgcn_readfirstlane(lo + __popcll(__ballot(le)) - 1);
 }
 
 // One payload inside one tile.  Output bytes [lo, hi) of the region hold the payload: row j of
@@ -309,8 +291,8 @@ __device__ __forceinline__ void rx_copy_stream(__amdgpu_buffer_rsrc_t rsrc, cons
   const int t_lo = lo > b0 ? lo : b0;
   const int t_hi = hi < b0 + es::kRemuxTile ? hi : b0 + es::kRemuxTile;
   if (t_lo >= t_hi || cnt <= 0) return;  // workgroup-uniform
-  const int j_lo = rx_last_le_wave(start, cnt, t_lo - lo);  // uniform: the rows this tile touches
-  const int j_hi = rx_last_le_wave(start, cnt, t_hi - 1 - lo);
+  const int j_lo = last_le_wave<int32_t>(start, cnt, t_lo - lo);  // workgroup-uniform: the rows this tile touches
+  const int j_hi = last_le_wave<int32_t>(start, cnt, t_hi - 1 - lo);
   int c_lo[kRxIters], c_hi[kRxIters], j[kRxIters], e[kRxIters], nxt[kRxIters], sj[kRxIters];
 #pragma unroll
   for (int it = 0; it < kRxIters; ++it) {
@@ -388,14 +370,15 @@ __global__ __launch_bounds__(kRxThreads) void remux_copy_kernel(
 }
 
 hipError_t launch_remux(const RemuxArgs& a) {
-  if (a.nseg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(remux_plan_kernel, dim3(a.nseg), dim3(kRxThreads), 0, a.stream, a.es, a.es_off, a.cap, a.info,
-                     a.pes, a.max_pes, a.max_nal, a.nal, a.au, a.aframes, a.sinfo, a.max_aframes, a.scratch,
-                     a.vsamples, a.asamples, a.rinfo, a.out, a.out_off);
+  const EsBatch& b = a.b;
+  if (b.nseg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(remux_plan_kernel, dim3(b.nseg), dim3(kRxThreads), 0, b.stream, b.es, b.es_off, b.cap, b.info,
+                     b.pes, b.max_pes, b.max_nal, b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo, a.max_aframes, a.scratch,
+                     a.t.vsamples, a.t.asamples, a.t.rinfo, a.out, a.out_off);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess || a.total_tiles <= 0) return e;
-  hipLaunchKernelGGL(remux_copy_kernel, dim3(static_cast<unsigned>(a.total_tiles)), dim3(kRxThreads), 0, a.stream,
-                     a.es, a.es_numel, a.es_off, a.tile_prefix, a.nseg, a.max_nal, a.max_aframes, a.scratch, a.rinfo,
+  if (e != hipSuccess || b.total_tiles <= 0) return e;
+  hipLaunchKernelGGL(remux_copy_kernel, dim3(static_cast<unsigned>(b.total_tiles)), dim3(kRxThreads), 0, b.stream,
+                     b.es, b.es_numel, b.es_off, b.tile_prefix, b.nseg, b.max_nal, a.max_aframes, a.scratch, a.t.rinfo,
                      a.out, a.out_off);
   return hipGetLastError();
 }

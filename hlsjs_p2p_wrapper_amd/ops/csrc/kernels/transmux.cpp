@@ -314,7 +314,7 @@ py::tuple transmux_launch(Tensor src, I64 src_off, I64 nbytes, py::array_t<uint8
     const int64_t nb_blocks = std::max<int64_t>(1, p.total_blocks);
     Tensor es = torch::empty({p.es_bytes}, dev_opts.dtype(torch::kUInt8));
     Tensor info = torch::empty({n, kInfo}, dev_opts.dtype(torch::kInt64));
-    Tensor pes = torch::empty({n, ts::kClasses, max_pes, 3}, dev_opts.dtype(torch::kInt64));
+    Tensor pes = torch::empty({n, ts::kClasses, max_pes, ts::kPesWords}, dev_opts.dtype(torch::kInt64));
     const auto ws = ts::demux_workspace(nb_blocks, n);
     Tensor meta = torch::empty({ws.meta}, dev_opts.dtype(torch::kInt32));
     Tensor pts = torch::empty({ws.pts_dts}, dev_opts.dtype(torch::kInt64));

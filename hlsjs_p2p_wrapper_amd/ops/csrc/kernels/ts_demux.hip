@@ -46,8 +46,8 @@ __global__ __launch_bounds__(64) void ts_psi_kernel(const uint8_t* __restrict__ 
   const int seg = blockIdx.x;
   const int lane = threadIdx.x;
   int64_t* inf = info + static_cast<int64_t>(seg) * kInfoWords;
-  int64_t* pe = pes + static_cast<int64_t>(seg) * kClasses * max_pes * 3;
-  for (int64_t i = lane; i < static_cast<int64_t>(kClasses) * max_pes * 3; i += 64) pe[i] = -1;
+  int64_t* pe = pes + pes_words(seg, max_pes);
+  for (int64_t i = lane; i < pes_words(1, max_pes); i += 64) pe[i] = -1;
   if (lane != 0) return;
   const int64_t raw_len = seg_len[seg];
   const int64_t n = raw_len < 0 ? 0 : raw_len;
@@ -367,10 +367,10 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
       if (pes_idx == 0) infc[kFirstPts + c] = pts_dts[2 * gpk];
       if (pes_idx == tot_pes - 1) infc[kLastPts + c] = pts_dts[2 * gpk];
       if (pes_idx < max_pes) {
-        int64_t* r = pes + ((static_cast<int64_t>(seg) * kClasses + c) * max_pes + pes_idx) * 3;
-        r[0] = es_in_class;
-        r[1] = pts_dts[2 * gpk];
-        r[2] = pts_dts[2 * gpk + 1];
+        int64_t* r = pes + ((static_cast<int64_t>(seg) * kClasses + c) * max_pes + pes_idx) * kPesWords;
+        r[kPesEsOffset] = es_in_class;
+        r[kPesPts] = pts_dts[2 * gpk];
+        r[kPesDts] = pts_dts[2 * gpk + 1];
       }
     }
   }

@@ -62,6 +62,35 @@ void parallel_for(int64_t n, F&& f, int64_t work_bytes = -1) {
   for (auto& x : th) x.join();
 }
 
+// The demuxed and indexed batch index_batch and remux_batch take: its sizes are checked here, once
+// (`more_ok`: the caller's own sizes, part of the same check), then each segment's ES range and,
+// right behind it, whatever `also(b)` checks of segment b.
+struct EsBatch {
+  const uint8_t* es;
+  const int64_t *es_off, *cap, *info, *pes;
+  int64_t max_pes, max_nal;
+  int64_t total = 0;  // ES bytes, the work to spread over threads
+  es::Segment at(int64_t b) const { return es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, b); }
+};
+template <typename F>
+EsBatch es_batch(const std::string& op, const Arr<uint8_t>& es, const Arr<int64_t>& es_off, const Arr<int64_t>& cap,
+                 const Arr<int64_t>& info, const Arr<int64_t>& pes, int64_t max_pes, int64_t max_nal,
+                 const es::IndexTables<const py::array, const py::array>& ix, bool more_ok, F&& also) {
+  const int64_t B = es_off.size();
+  if (cap.size() != B || !more_ok || info.size() < B * ts::kInfoWords || pes.size() < ts::pes_words(B, max_pes) ||
+      ix.nal->size() < table_words(B, max_nal, es::kNalWords) || ix.au->size() < table_words(B, max_pes, es::kAuWords) ||
+      ix.aframes->size() < table_words(B, max_pes, es::kApesWords) || ix.sinfo->size() < B * es::kSinfoWords)
+    throw std::invalid_argument(op + ": an argument is too small");
+  EsBatch r{es.data(), es_off.data(), cap.data(), info.data(), pes.data(), max_pes, max_nal};
+  for (int64_t b = 0; b < B; ++b) {
+    if (r.es_off[b] < 0 || r.cap[b] < 0 || r.es_off[b] + r.cap[b] > es.size())
+      throw std::invalid_argument(op + ": ES out of bounds");
+    also(b);
+    r.total += r.cap[b];
+  }
+  return r;
+}
+
 SegKey key_from(const int64_t* p) {
   return SegKey{uint32_t(p[0]), uint32_t(p[1]), uint32_t(p[2]), uint32_t(p[3])};
 }
@@ -275,14 +304,14 @@ PYBIND11_MODULE(_runtime, m) {
      py::arg("seed"), py::arg("sn"), py::arg("start_time"));
   // Batched CPU demux with the device kernels' layout.
   //   buf: flat uint8 plaintext; off/len: int64[B]; es: flat uint8 (segment b writes at es_off[b])
-  //   pes: int64[B, 3, max_pes, 3]; info: int64[B, 16]
+  //   pes: int64[B, TS_CLASSES, max_pes, TS_PES_WORDS]; info: int64[B, TS_INFO_WORDS]
   m.def("demux_batch", [](Arr<uint8_t> buf, Arr<int64_t> off, Arr<int64_t> len, py::array es, Arr<int64_t> es_off,
                           py::array pes, py::array info, int64_t max_pes) {
     const int64_t B = off.size();
     uint8_t* e = mut_ptr<uint8_t>(es, "es");
     int64_t* pp = mut_ptr<int64_t>(pes, "pes");
     int64_t* ip = mut_ptr<int64_t>(info, "info");
-    if (pes.size() < B * ts::kClasses * max_pes * 3 || info.size() < B * ts::kInfoWords)
+    if (pes.size() < ts::pes_words(B, max_pes) || info.size() < B * ts::kInfoWords)
       throw std::invalid_argument("demux_batch: pes/info too small");
     for (int64_t b = 0; b < B; ++b)
       if (off.data()[b] < 0 || len.data()[b] < 0 || off.data()[b] + len.data()[b] > buf.size() ||
@@ -296,7 +325,7 @@ PYBIND11_MODULE(_runtime, m) {
     for (int64_t b = 0; b < B; ++b) total += l[b];
     py::gil_scoped_release nogil;
     parallel_for(B, [&](int64_t b) {
-      ts::demux_segment(p + o[b], l[b], e + eo[b], pp + b * ts::kClasses * max_pes * 3, max_pes,
+      ts::demux_segment(p + o[b], l[b], e + eo[b], pp + ts::pes_words(b, max_pes), max_pes,
                         ip + b * ts::kInfoWords);
     }, total);
   });
@@ -304,6 +333,7 @@ PYBIND11_MODULE(_runtime, m) {
   m.attr("TS_INFO_WORDS") = ts::kInfoWords;
   m.attr("TS_CLASSES") = ts::kClasses;
   m.attr("TS_PACKET") = ts::kPacket;
+  m.attr("TS_PES_WORDS") = ts::kPesWords;
   {  // the info row and status bits by name (shared/layout.hpp)
     py::dict d, st;
     d["status"] = int(ts::kStatus);
@@ -334,37 +364,26 @@ PYBIND11_MODULE(_runtime, m) {
   }
   // Batched CPU sample index with the device kernels' layout (docs/ESINDEX.md).
   //   es: flat uint8 (segment b's ES at es_off[b], cap[b] bytes readable); info / pes: demux_batch's
-  //   nal: int32[B, max_nal, 4]; au: int32[B, max_pes, 4]; aframes: int32[B, max_pes, 2]; sinfo: int64[B, 8]
+  //   nal: int32[B, max_nal, ES_NAL_WORDS]; au: int32[B, max_pes, ES_AU_WORDS];
+  //   aframes: int32[B, max_pes, ES_APES_WORDS]; sinfo: int64[B, ES_SINFO_WORDS]
   m.def("index_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
                           int64_t max_pes, int64_t max_nal, py::array nal, py::array au, py::array aframes,
                           py::array sinfo) {
-    const int64_t B = es_off.size();
     if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("index_batch: max_pes and max_nal must be positive");
-    int32_t* np = mut_ptr<int32_t>(nal, "nal");
-    int32_t* up = mut_ptr<int32_t>(au, "au");
-    int32_t* fp = mut_ptr<int32_t>(aframes, "aframes");
-    int64_t* sp = mut_ptr<int64_t>(sinfo, "sinfo");
-    if (cap.size() != B || info.size() < B * ts::kInfoWords || pes.size() < B * ts::kClasses * max_pes * 3 ||
-        nal.size() < B * max_nal * 4 || au.size() < B * max_pes * 4 || aframes.size() < B * max_pes * 2 ||
-        sinfo.size() < B * es::kSinfoWords)
-      throw std::invalid_argument("index_batch: an argument is too small");
-    const int64_t* eo = es_off.data();
-    const int64_t* c = cap.data();
-    int64_t total = 0;
-    for (int64_t b = 0; b < B; ++b) {
-      if (eo[b] < 0 || c[b] < 0 || eo[b] + c[b] > es.size()) throw std::invalid_argument("index_batch: ES out of bounds");
-      total += c[b];
-    }
-    const uint8_t* e = es.data();
-    const int64_t* ip = info.data();
-    const int64_t* pp = pes.data();
+    const es::IndexTables<int32_t, int64_t> out{mut_ptr<int32_t>(nal, "nal"), mut_ptr<int32_t>(au, "au"),
+                                                mut_ptr<int32_t>(aframes, "aframes"), mut_ptr<int64_t>(sinfo, "sinfo")};
+    const EsBatch batch = es_batch("index_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal, &au, &aframes, &sinfo}, true, [](int64_t) {});
     py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
-      es::index_segment(e + eo[b], c[b], ip + b * ts::kInfoWords, pp + b * ts::kClasses * max_pes * 3, max_pes, max_nal,
-                        np + b * max_nal * 4, up + b * max_pes * 4, fp + b * max_pes * 2, sp + b * es::kSinfoWords);
-    }, total);
+    parallel_for(es_off.size(), [&](int64_t b) {
+      const es::Segment s = batch.at(b);
+      es::index_segment(s, es::index_tables_at(out, s, b));
+    }, batch.total);
   });
   m.attr("ES_SINFO_WORDS") = es::kSinfoWords;
+  m.attr("ES_NAL_WORDS") = es::kNalWords;
+  m.attr("ES_AU_WORDS") = es::kAuWords;
+  m.attr("ES_APES_WORDS") = es::kApesWords;
   m.attr("ES_DEFAULT_MAX_NAL") = es::kDefaultMaxNal;
   {
     py::dict d, st, fl;
@@ -389,7 +408,8 @@ PYBIND11_MODULE(_runtime, m) {
   }
   // Batched CPU remux with the device kernels' layout (docs/REMUX.md): the inputs of index_batch, its
   // four outputs, and per segment a region of remux_out_bytes(cap, max_nal) bytes of `out` at out_off.
-  //   vsamples: int32[B, max_pes, 5]; asamples: int32[B, max_aframes, 2]; rinfo: int64[B, 8]
+  //   vsamples: int32[B, max_pes, ES_VSAMPLE_WORDS]; asamples: int32[B, max_aframes, ES_ASAMPLE_WORDS];
+  //   rinfo: int64[B, ES_RINFO_WORDS]
   m.def("remux_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
                           int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au, Arr<int32_t> aframes,
                           Arr<int64_t> sinfo, int64_t max_aframes, py::array vsamples, py::array asamples,
@@ -397,46 +417,33 @@ PYBIND11_MODULE(_runtime, m) {
     const int64_t B = es_off.size();
     if (max_pes <= 0 || max_nal <= 0 || max_aframes <= 0)
       throw std::invalid_argument("remux_batch: max_pes, max_nal and max_aframes must be positive");
-    int32_t* vs = mut_ptr<int32_t>(vsamples, "vsamples");
-    int32_t* as = mut_ptr<int32_t>(asamples, "asamples");
-    int64_t* rp = mut_ptr<int64_t>(rinfo, "rinfo");
+    const es::RemuxTables tables{mut_ptr<int32_t>(vsamples, "vsamples"), mut_ptr<int32_t>(asamples, "asamples"),
+                                 mut_ptr<int64_t>(rinfo, "rinfo")};
     uint8_t* op = mut_ptr<uint8_t>(out, "out");
-    if (cap.size() != B || out_off.size() != B || info.size() < B * ts::kInfoWords ||
-        pes.size() < B * ts::kClasses * max_pes * 3 || nal.size() < B * max_nal * 4 || au.size() < B * max_pes * 4 ||
-        aframes.size() < B * max_pes * 2 || sinfo.size() < B * es::kSinfoWords ||
-        vsamples.size() < B * max_pes * es::kVsampleWords || asamples.size() < B * max_aframes * es::kAsampleWords ||
-        rinfo.size() < B * es::kRinfoWords)
-      throw std::invalid_argument("remux_batch: an argument is too small");
-    const int64_t* eo = es_off.data();
-    const int64_t* c = cap.data();
     const int64_t* oo = out_off.data();
-    int64_t total = 0;
-    for (int64_t b = 0; b < B; ++b) {
-      if (eo[b] < 0 || c[b] < 0 || eo[b] + c[b] > es.size()) throw std::invalid_argument("remux_batch: ES out of bounds");
-      if (oo[b] < 0 || oo[b] + es::remux_out_bytes(c[b], max_nal) > out.size())
+    const bool sized = out_off.size() == B && vsamples.size() >= table_words(B, max_pes, es::kVsampleWords) &&
+                       asamples.size() >= table_words(B, max_aframes, es::kAsampleWords) &&
+                       rinfo.size() >= B * es::kRinfoWords;
+    const EsBatch batch = es_batch("remux_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal, &au, &aframes, &sinfo}, sized, [&](int64_t b) {
+      if (oo[b] < 0 || oo[b] + es::remux_out_bytes(cap.data()[b], max_nal) > out.size())
         throw std::invalid_argument("remux_batch: output region out of bounds");
-      total += c[b];
-    }
-    const uint8_t* e = es.data();
-    const int64_t* ip = info.data();
-    const int64_t* pp = pes.data();
-    const int32_t* np = nal.data();
-    const int32_t* up = au.data();
-    const int32_t* fp = aframes.data();
-    const int64_t* sp = sinfo.data();
+    });
+    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
     py::gil_scoped_release nogil;
     parallel_for(B, [&](int64_t b) {
-      es::remux_segment(e + eo[b], c[b], ip + b * ts::kInfoWords, pp + b * ts::kClasses * max_pes * 3, max_pes, max_nal,
-                        np + b * max_nal * 4, up + b * max_pes * 4, fp + b * max_pes * 2, sp + b * es::kSinfoWords,
-                        max_aframes, vs + b * max_pes * es::kVsampleWords, as + b * max_aframes * es::kAsampleWords,
-                        rp + b * es::kRinfoWords, op + oo[b]);
-    }, total);
+      const es::Segment s = batch.at(b);
+      es::remux_segment(s, es::index_tables_at(ix, s, b), max_aframes, es::remux_tables_at(tables, s, max_aframes, b),
+                        op + oo[b]);
+    }, batch.total);
   });
   m.def("remux_out_bytes", py::vectorize(&es::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
     return es::remux_scratch(nseg, max_nal, max_aframes).end;
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
   m.attr("ES_RINFO_WORDS") = es::kRinfoWords;
+  m.attr("ES_VSAMPLE_WORDS") = es::kVsampleWords;
+  m.attr("ES_ASAMPLE_WORDS") = es::kAsampleWords;
   m.attr("ES_DEFAULT_MAX_AFRAMES") = es::kDefaultMaxAframes;
   m.attr("ES_REMUX_TILE") = es::kRemuxTile;
   m.attr("ES_OUT_ALIGN") = es::kOutAlign;

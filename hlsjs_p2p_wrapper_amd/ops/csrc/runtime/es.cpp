@@ -1,30 +1,29 @@
-// Host sample index: the serial loops that fill the rows.  The codec, NAL-type and ADTS byte
-// rules are shared/grammar.hpp (namespace es), the same functions kernels/es_index.hip calls.
+// Host sample index: the serial loops that fill the rows.  The segment view and the codec,
+// NAL-type and ADTS byte rules are shared/grammar.hpp (namespace es), the same functions
+// kernels/es_index.hip calls.
 #include "es.hpp"
 
 #include <algorithm>
 #include <vector>
 
-#include "grammar.hpp"
-#include "ts.hpp"
-
 namespace hlsp2p {
 namespace es {
 
-void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const int64_t* pes, int64_t max_pes,
-                   int64_t max_nal, int32_t* nal, int32_t* au, int32_t* aframes, int64_t* sinfo) {
-  std::fill(nal, nal + max_nal * 4, -1);
-  std::fill(au, au + max_pes * 4, -1);
-  std::fill(aframes, aframes + max_pes * 2, -1);
+void index_segment(Segment s, const IndexTables<int32_t, int64_t>& t) {
+  const int64_t max_pes = s.max_pes, max_nal = s.max_nal;
+  int32_t *nal = t.nal, *au = t.au, *aframes = t.aframes;
+  int64_t* sinfo = t.sinfo;
+  std::fill(nal, nal + table_words(1, max_nal, kNalWords), -1);
+  std::fill(au, au + table_words(1, max_pes, kAuWords), -1);
+  std::fill(aframes, aframes + table_words(1, max_pes, kApesWords), -1);
   std::fill(sinfo, sinfo + kSinfoWords, int64_t(0));
   sinfo[kFirstKeyframeAu] = -1;
-  cap = std::max<int64_t>(cap, 0);
-  const int64_t vtype = info[ts::kVideoType];
-  const bool supported = video_supported(vtype);
-  const bool hevc = is_hevc(vtype);
-  int64_t status = supported ? 0 : kUnsupportedVideo;
-  const uint8_t* V = es;
-  const int64_t n = supported ? clamp(info[ts::kVideoBytes], 0, cap) : 0;
+  s.cap = std::max<int64_t>(s.cap, 0);  // the host takes any cap: a negative one reads nothing
+  const VideoSpan video = video_span(s);
+  const bool hevc = video.hevc;
+  int64_t status = video.supported ? 0 : kUnsupportedVideo;
+  const uint8_t* V = s.es;
+  const int64_t n = video.len;
 
   // ---- start codes, in offset order; one position past the table ends its last NAL
   std::vector<int64_t> p;  // start-code positions of the first max_nal + 1 NALs
@@ -42,42 +41,46 @@ void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const in
   const int64_t nn = std::min(n_nal, max_nal);
 
   // ---- NAL rows
-  const int64_t m = supported ? clamp(info[ts::kNumVideoPes], 0, max_pes) : 0;  // unsupported: no units either
-  const int64_t* vp = pes;  // class 0
-  int64_t a = -1;           // access unit of the current NAL: PES offsets ascend with the NAL starts
+  const int64_t m = video_rows(video, s.info[ts::kNumVideoPes], max_pes);  // the demux's count: one unit per PES
+  const PesRows rows = pes_rows(s);
+  const int64_t* vp = rows.video;
+  int64_t a = -1;  // access unit of the current NAL: PES offsets ascend with the NAL starts
   for (int64_t k = 0; k < nn; ++k) {
-    const int64_t s = p[k] + 3;
+    const int64_t b = p[k] + 3;
     int64_t e = n;
     if (k + 1 < n_nal) {
       const int64_t p1 = p[k + 1];
       const int64_t z1 = (p1 > 0 && V[p1 - 1] == 0) ? 1 : 0;
-      e = std::max(s, p1 - z1);
+      e = std::max(b, p1 - z1);
     }
-    while (a + 1 < m && vp[3 * (a + 1)] <= s) ++a;
-    nal[4 * k] = static_cast<int32_t>(s);
-    nal[4 * k + 1] = static_cast<int32_t>(e - s);
-    nal[4 * k + 2] = e == s ? -1 : nal_type(hevc, V[s]);
-    nal[4 * k + 3] = static_cast<int32_t>(a);
+    while (a + 1 < m && pes_at(vp, a + 1, ts::kPesEsOffset) <= b) ++a;
+    int32_t* row = nal + kNalWords * k;
+    row[kNalOffset] = static_cast<int32_t>(b);
+    row[kNalLength] = static_cast<int32_t>(e - b);
+    row[kNalType] = e == b ? -1 : nal_type(hevc, V[b]);
+    row[kNalAu] = static_cast<int32_t>(a);
   }
 
   // ---- access unit rows
   int64_t n_key = 0, first_key = -1;
   for (int64_t u = 0; u < m; ++u) {
-    const int64_t next = u + 1 < m ? vp[3 * (u + 1)] : n;
-    au[4 * u] = -1;
-    au[4 * u + 1] = 0;
-    au[4 * u + 2] = 0;
-    au[4 * u + 3] = static_cast<int32_t>(next - vp[3 * u]);
+    const int64_t next = u + 1 < m ? pes_at(vp, u + 1, ts::kPesEsOffset) : n;
+    int32_t* row = au + kAuWords * u;
+    row[kAuFirstNal] = -1;
+    row[kAuNalCount] = 0;
+    row[kAuFlags] = 0;
+    row[kAuSize] = static_cast<int32_t>(next - pes_at(vp, u, ts::kPesEsOffset));
   }
   for (int64_t k = 0; k < nn; ++k) {
-    const int64_t u = nal[4 * k + 3];
+    const int64_t u = nal[kNalWords * k + kNalAu];
     if (u < 0) continue;
-    if (au[4 * u + 1] == 0) au[4 * u] = static_cast<int32_t>(k);
-    ++au[4 * u + 1];
-    au[4 * u + 2] |= nal_flags(hevc, nal[4 * k + 2]);
+    int32_t* row = au + kAuWords * u;
+    if (row[kAuNalCount] == 0) row[kAuFirstNal] = static_cast<int32_t>(k);
+    ++row[kAuNalCount];
+    row[kAuFlags] |= nal_flags(hevc, nal[kNalWords * k + kNalType]);
   }
   for (int64_t u = 0; u < m; ++u) {
-    if (au[4 * u + 2] & kAuKeyframe) {
+    if (au[kAuWords * u + kAuFlags] & kAuKeyframe) {
       if (n_key++ == 0) first_key = u;
     }
   }
@@ -85,21 +88,15 @@ void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const in
   // ---- ADTS frames, one walk per audio PES
   int64_t n_frames = 0;
   int rate = 0, chans = 0;
-  if (is_adts(info[ts::kAudioType])) {
-    const int64_t a_off = clamp(info[ts::kAudioEsOffset], 0, cap);
-    const int64_t a_len = clamp(info[ts::kAudioBytes], 0, cap - a_off);
-    const uint8_t* A = es + a_off;
-    const int64_t ma = clamp(info[ts::kNumAudioPes], 0, max_pes);
-    const int64_t* ap = pes + max_pes * 3;  // class 1
-    for (int64_t k = 0; k < ma; ++k) {
-      const int64_t start = clamp(ap[3 * k], 0, a_len);
-      const int64_t end = k + 1 < ma ? clamp(ap[3 * (k + 1)], start, a_len) : a_len;
-      const AdtsWalk w = adts_walk(A, start, end, k == 0, rate, chans);
-      if (w.error) status |= kAdtsError;
-      aframes[2 * k] = w.frames;
-      aframes[2 * k + 1] = w.used;
-      n_frames += w.frames;
-    }
+  const AudioSpan audio = audio_span(s);
+  const uint8_t* A = s.es + audio.off;
+  for (int64_t k = 0; k < audio.n_adts; ++k) {
+    const ByteRange r = audio_pes_range(rows.audio, k, audio);
+    const AdtsWalk w = adts_walk(A, r.start, r.end, k == 0, rate, chans);
+    if (w.error) status |= kAdtsError;
+    aframes[kApesWords * k + kApesFrames] = w.frames;
+    aframes[kApesWords * k + kApesUsed] = w.used;
+    n_frames += w.frames;
   }
 
   sinfo[kStatus] = status;

@@ -8,23 +8,22 @@
 #pragma once
 #include <cstdint>
 
-#include "layout.hpp"
+#include "grammar.hpp"
 
 namespace hlsp2p {
 namespace es {
 
-// sinfo[] row layout, status bits and access-unit flags: shared/layout.hpp
+// row layouts (NalRow, AuRow, ApesRow, Sinfo), status bits and access-unit flags: shared/layout.hpp
 
 // Index one segment.
-//   es:      the segment's [video ES | audio ES | id3 ES]; `cap` bytes are readable
-//   info:    the demux info row (int64[ts::kInfoWords]); byte counts are clamped to `cap`
-//   pes:     the demux PES table int64[ts::kClasses][max_pes][3]
-//   nal:     int32[max_nal][4] = (offset, length, type, access unit), -1 rows beyond
-//   au:      int32[max_pes][4] = (first NAL, NAL count, flags, size), -1 rows beyond
-//   aframes: int32[max_pes][2] = (ADTS frames, bytes consumed) per audio PES, -1 rows beyond
-//   sinfo:   int64[kSinfoWords]
-void index_segment(const uint8_t* es, int64_t cap, const int64_t* info, const int64_t* pes, int64_t max_pes,
-                   int64_t max_nal, int32_t* nal, int32_t* au, int32_t* aframes, int64_t* sinfo);
+//   s.es:      the segment's [video ES | audio ES | id3 ES]; `s.cap` bytes are readable
+//   s.info:    the demux info row (int64[ts::kInfoWords]); byte counts are clamped to `s.cap`
+//   s.pes:     the demux PES table int64[ts::kClasses][max_pes][ts::kPesWords]
+//   t.nal:     int32[max_nal][kNalWords], -1 rows beyond
+//   t.au:      int32[max_pes][kAuWords], -1 rows beyond
+//   t.aframes: int32[max_pes][kApesWords] per audio PES, -1 rows beyond
+//   t.sinfo:   int64[kSinfoWords]
+void index_segment(Segment s, const IndexTables<int32_t, int64_t>& t);
 
 }  // namespace es
 }  // namespace hlsp2p

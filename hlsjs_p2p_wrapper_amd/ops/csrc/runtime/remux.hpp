@@ -8,25 +8,23 @@
 #pragma once
 #include <cstdint>
 
-#include "layout.hpp"
+#include "grammar.hpp"
 
 namespace hlsp2p {
 namespace es {
 
-// rinfo[] row layout and status bits, region and scratch sizes: shared/layout.hpp
+// row layouts (VsampleRow, AsampleRow, Rinfo) and status bits, region and scratch sizes: shared/layout.hpp
 
 // Remux one segment.
-//   es / cap / info / pes:      as index_segment took them
-//   nal / au / aframes / sinfo: what index_segment wrote (rows are used as found, clamped)
-//   vsamples: int32[max_pes][5] = (offset, size, duration, cts, flags), -1 rows beyond
-//   asamples: int32[max_aframes][2] = (offset, size), -1 rows beyond
-//   rinfo:    int64[kRinfoWords]
-//   out:      the segment's output region, remux_out_bytes(cap, max_nal) bytes writable; only
-//             the two box headers and the two payloads are written
-void remux_segment(const uint8_t* es, int64_t cap, const int64_t* info, const int64_t* pes, int64_t max_pes,
-                   int64_t max_nal, const int32_t* nal, const int32_t* au, const int32_t* aframes,
-                   const int64_t* sinfo, int64_t max_aframes, int32_t* vsamples, int32_t* asamples, int64_t* rinfo,
-                   uint8_t* out);
+//   s:          as index_segment took it
+//   ix:         what index_segment wrote (rows are used as found, clamped)
+//   t.vsamples: int32[max_pes][kVsampleWords], -1 rows beyond
+//   t.asamples: int32[max_aframes][kAsampleWords], -1 rows beyond
+//   t.rinfo:    int64[kRinfoWords]
+//   out:        the segment's output region, remux_out_bytes(cap, max_nal) bytes writable; only
+//               the two box headers and the two payloads are written
+void remux_segment(Segment s, const IndexTables<const int32_t, const int64_t>& ix, int64_t max_aframes,
+                   const RemuxTables& t, uint8_t* out);
 
 }  // namespace es
 }  // namespace hlsp2p

@@ -302,7 +302,7 @@ std::vector<uint8_t> mux_segment(const MuxConfig& cfg, MuxStats* stats) {
 
 void demux_segment(const uint8_t* data, int64_t n, uint8_t* es_out, int64_t* pes_out, int64_t max_pes, int64_t* info) {
   std::fill(info, info + kInfoWords, 0);
-  for (int64_t i = 0; i < int64_t(kClasses) * max_pes * 3; ++i) pes_out[i] = -1;
+  for (int64_t i = 0; i < pes_words(1, max_pes); ++i) pes_out[i] = -1;
   const int64_t np = n / kPacket;
   const Psi psi = parse_psi(data, np);
   int64_t status = psi.status | (n % kPacket ? kBadLength : 0);
@@ -332,8 +332,8 @@ void demux_segment(const uint8_t* data, int64_t n, uint8_t* es_out, int64_t* pes
           if (cnt[c] == 0) first_pts[c] = pk.pts;
           last_pts[c] = pk.pts;
           if (cnt[c] < max_pes) {
-            int64_t* r = pes_out + (int64_t(c) * max_pes + cnt[c]) * 3;
-            r[0] = cur[c]; r[1] = pk.pts; r[2] = pk.dts;
+            int64_t* r = pes_out + (int64_t(c) * max_pes + cnt[c]) * kPesWords;
+            r[kPesEsOffset] = cur[c]; r[kPesPts] = pk.pts; r[kPesDts] = pk.dts;
           }
         }
         cnt[c] += 1;

@@ -1,7 +1,7 @@
 // The MPEG-TS / PES / NAL / ADTS byte rules that fill the rows of layout.hpp: the only definition
-// of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp) and by the gfx950 kernels
-// (kernels/ts_demux.hip, kernels/es_index.hip).  Plain inline functions over <cstdint> and
-// layout.hpp: no containers, no statics, no tables in memory.
+// of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp) and by
+// the gfx950 kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip).  Plain inline
+// functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
 
@@ -162,6 +162,65 @@ HLSP2P_RULE bool video_supported(int64_t vtype) { return vtype == ts::kAvc || vt
 HLSP2P_RULE bool is_hevc(int64_t vtype) { return vtype == ts::kHevc; }
 HLSP2P_RULE bool is_adts(int64_t atype) { return atype == ts::kAdtsAac; }
 HLSP2P_RULE int nal_type(bool hevc, int byte) { return hevc ? (byte >> 1) & 0x3f : byte & 0x1f; }
+
+// ---- one demuxed segment as the index and the remux read it: damaged info rows are clamped
+// here, once, so host and device agree byte for byte
+struct Segment {
+  const uint8_t* es;  // [video ES | audio ES | id3 ES]
+  int64_t cap;        // readable bytes of es; the caller decides how far it trusts the value
+  const int64_t *info, *pes;
+  int64_t max_pes, max_nal;
+};
+// segment b of a batch
+HLSP2P_RULE Segment segment_at(const uint8_t* es, const int64_t* es_off, const int64_t* cap, const int64_t* info,
+                               const int64_t* pes, int64_t max_pes, int64_t max_nal, int64_t b) {
+  return {es + es_off[b], cap[b], info + b * ts::kInfoWords, pes + ts::pes_words(b, max_pes), max_pes, max_nal};
+}
+template <class I32, class I64>
+HLSP2P_RULE IndexTables<I32, I64> index_tables_at(const IndexTables<I32, I64>& t, const Segment& s, int64_t b) {
+  return {t.nal + table_words(b, s.max_nal, kNalWords), t.au + table_words(b, s.max_pes, kAuWords),
+          t.aframes + table_words(b, s.max_pes, kApesWords), t.sinfo + b * kSinfoWords};
+}
+HLSP2P_RULE RemuxTables remux_tables_at(const RemuxTables& t, const Segment& s, int64_t max_aframes, int64_t b) {
+  return {t.vsamples + table_words(b, s.max_pes, kVsampleWords), t.asamples + table_words(b, max_aframes, kAsampleWords),
+          t.rinfo + b * kRinfoWords};
+}
+
+struct PesRows { const int64_t *video, *audio; };
+HLSP2P_RULE PesRows pes_rows(const Segment& s) { return {s.pes, s.pes + table_words(1, s.max_pes, ts::kPesWords)}; }
+HLSP2P_RULE int64_t pes_at(const int64_t* rows, int64_t k, ts::PesRow col) { return rows[ts::kPesWords * k + col]; }
+
+struct VideoSpan {
+  bool supported, hevc;
+  int64_t len;  // video ES bytes to read: 0 for an unsupported codec, never beyond cap
+};
+HLSP2P_RULE VideoSpan video_span(const int64_t* info, int64_t cap) {
+  const int64_t vtype = info[ts::kVideoType];
+  const bool supported = video_supported(vtype);
+  return {supported, is_hevc(vtype), supported ? clamp(info[ts::kVideoBytes], 0, cap) : 0};
+}
+HLSP2P_RULE VideoSpan video_span(const Segment& s) { return video_span(s.info, s.cap); }
+// rows of a video table (NALs, access units) among `count` claimed ones: an unsupported codec has none
+HLSP2P_RULE int64_t video_rows(const VideoSpan& v, int64_t count, int64_t max_rows) {
+  return v.supported ? clamp(count, 0, max_rows) : 0;
+}
+
+struct AudioSpan {
+  int64_t off, len;  // the audio ES inside es
+  int64_t n_pes;     // rows of the audio PES table
+  int64_t n_adts;    // the same, 0 unless the stream is ADTS: the PES whose frames are walked
+};
+HLSP2P_RULE AudioSpan audio_span(const Segment& s) {
+  const int64_t off = clamp(s.info[ts::kAudioEsOffset], 0, s.cap);
+  const int64_t n_pes = clamp(s.info[ts::kNumAudioPes], 0, s.max_pes);
+  return {off, clamp(s.info[ts::kAudioBytes], 0, s.cap - off), n_pes, is_adts(s.info[ts::kAudioType]) ? n_pes : 0};
+}
+// bytes [start, end) of the audio ES that audio PES k < a.n_adts covers: up to the next PES, inside the ES
+struct ByteRange { int64_t start, end; };
+HLSP2P_RULE ByteRange audio_pes_range(const int64_t* ap, int64_t k, const AudioSpan& a) {
+  const int64_t start = clamp(pes_at(ap, k, ts::kPesEsOffset), 0, a.len);
+  return {start, k + 1 < a.n_adts ? clamp(pes_at(ap, k + 1, ts::kPesEsOffset), start, a.len) : a.len};
+}
 
 HLSP2P_RULE int nal_flags(bool hevc, int type) {
   if (hevc)

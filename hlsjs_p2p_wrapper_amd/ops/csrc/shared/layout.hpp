@@ -5,6 +5,9 @@
 
 namespace hlsp2p {
 
+// elements of a table of `rows` rows of `width` words per segment: a batch's size, and where segment nseg starts
+constexpr int64_t table_words(int64_t nseg, int64_t rows, int width) { return nseg * rows * width; }
+
 // ---------------------------------------------------------------- MPEG-TS demux
 namespace ts {
 constexpr int kPacket = 188;
@@ -29,6 +32,11 @@ enum Info : int {
   kId3EsOffset = 23,    // byte offset of the id3 ES: [video | audio | id3] packed back to back
 };
 enum Status : int64_t { kBadSync = 1, kNoPat = 2, kNoPmt = 4, kPesOverflow = 8, kPesHeaderError = 16, kBadLength = 32 };
+
+// pes[] (int64): [segment][class][max_pes] rows, -1 rows beyond a class's PES count
+constexpr int kPesWords = 3;
+enum PesRow : int { kPesEsOffset = 0, kPesPts = 1, kPesDts = 2 };  // offset inside the class's ES
+constexpr int64_t pes_words(int64_t nseg, int64_t max_pes) { return nseg * kClasses * max_pes * kPesWords; }
 
 // demux blocks of a segment of at most n bytes
 constexpr int64_t demux_blocks(int64_t n) { return ((n + kPacket - 1) / kPacket + kBlockPackets - 1) / kBlockPackets; }
@@ -63,7 +71,21 @@ enum Sinfo : int {
   kNumAdtsFrames = 5, kAudioSampleRate = 6, kAudioChannels = 7,
 };
 enum Status : int64_t { kNalOverflow = 1, kAdtsError = 2, kUnsupportedVideo = 4 };
-enum AuFlags : int { kAuKeyframe = 1, kAuSps = 2, kAuPps = 4, kAuAud = 8 };  // au[..][2]
+enum AuFlags : int { kAuKeyframe = 1, kAuSps = 2, kAuPps = 4, kAuAud = 8 };  // au[..][kAuFlags]
+
+// index tables (int32), -1 rows beyond: nal [segment][max_nal], au and aframes [segment][max_pes]
+constexpr int kNalWords = 4;
+enum NalRow : int { kNalOffset = 0, kNalLength = 1, kNalType = 2, kNalAu = 3 };  // offset inside the video ES
+constexpr int kAuWords = 4;
+enum AuRow : int { kAuFirstNal = 0, kAuNalCount = 1, kAuFlags = 2, kAuSize = 3 };
+constexpr int kApesWords = 2;  // aframes row: one per audio PES
+enum ApesRow : int { kApesFrames = 0, kApesUsed = 1 };  // whole ADTS frames, and their bytes
+// One segment's four index tables, or a batch's; I32 / I64 are const where they are only read.
+template <class I32, class I64>
+struct IndexTables {
+  I32 *nal, *au, *aframes;
+  I64* sinfo;
+};
 
 // scratch (int32), element offsets: [tile_cnt: total_tiles | tile_pre: total_tiles | pos: nseg x (max_nal + 1)]
 struct IndexScratch { int64_t tile_cnt, tile_pre, pos, end; };
@@ -74,8 +96,15 @@ constexpr IndexScratch index_scratch(int64_t total_tiles, int64_t nseg, int64_t 
 // ---- remux to fMP4 samples and mdat boxes (docs/REMUX.md)
 constexpr int kRinfoWords = 8;
 constexpr int64_t kDefaultMaxAframes = 1024;
-constexpr int kVsampleWords = 5;  // vsamples row: offset, size, duration, cts, flags
-constexpr int kAsampleWords = 2;  // asamples row: offset, size
+constexpr int kVsampleWords = 5;  // vsamples row [segment][max_pes], one per access unit
+enum VsampleRow : int { kVsOffset = 0, kVsSize = 1, kVsDuration = 2, kVsCts = 3, kVsFlags = 4 };  // offset in the payload
+constexpr int kAsampleWords = 2;  // asamples row [segment][max_aframes], one per AAC frame
+enum AsampleRow : int { kAsOffset = 0, kAsSize = 1 };
+// One segment's three remux tables, or a batch's.
+struct RemuxTables {
+  int32_t *vsamples, *asamples;
+  int64_t* rinfo;
+};
 constexpr int kRemuxTile = 16384;  // output bytes per workgroup of the copy kernel
 constexpr int kOutAlign = 256;     // alignment of a segment's output region on the device
 constexpr int32_t kSampleSync = 0x02000000;     // sample_depends_on = 2

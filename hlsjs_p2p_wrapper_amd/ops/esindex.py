@@ -17,7 +17,7 @@ the demux was sized with) size the grid and bound every access.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Dict, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -37,10 +37,10 @@ DEFAULT_MAX_NAL = 2048
 
 @dataclass
 class EsIndex:
-    nal: torch.Tensor      # int32[B, max_nal, 4]
-    au: torch.Tensor       # int32[B, max_pes, 4]
-    aframes: torch.Tensor  # int32[B, max_pes, 2]
-    sinfo: torch.Tensor    # int64[B, 8]
+    nal: torch.Tensor      # int32[B, max_nal, ES_NAL_WORDS]
+    au: torch.Tensor       # int32[B, max_pes, ES_AU_WORDS]
+    aframes: torch.Tensor  # int32[B, max_pes, ES_APES_WORDS]
+    sinfo: torch.Tensor    # int64[B, SINFO_WORDS]
 
     def segment(self, i: int) -> dict:
         """Host view of segment ``i`` (syncs): the ``sinfo`` fields by name, ``independent``
@@ -55,46 +55,66 @@ class EsIndex:
         return out
 
 
+class BatchPlan:
+    """What :func:`index_batch` and ``remux_batch`` settle before their launch, once: the batch's
+    arrays with the ES ranges checked (``op`` names the caller in every message), one allocation
+    per result table on the batch's device, and for the device path the launch rules, the tile
+    space and the packed descriptors."""
+
+    __slots__ = ("op", "es", "eo", "cap", "B", "max_pes", "dev")
+
+    def __init__(self, op: str, res: DemuxResult, caps: Sequence[int]):
+        self.op, self.es = op, res.es
+        self.eo = np.asarray(res.es_offs, dtype=np.int64)
+        self.cap = np.asarray(caps, dtype=np.int64)
+        self.B = len(self.eo)
+        self.max_pes = int(res.pes.shape[2])
+        self.dev = res.es.device
+        check_ranges(op, "ES", self.eo, self.cap, res.es.numel())
+
+    def table(self, rows: int, words: int, dtype: torch.dtype = torch.int32) -> torch.Tensor:
+        """One result table ``[B, rows, words]`` (``rows == 0``: ``[B, words]``) on the batch's
+        device; the CPU path hands its ``.numpy()`` view to the runtime."""
+        return torch.empty((self.B, rows, words) if rows else (self.B, words), dtype=dtype, device=self.dev)
+
+    def on_device(self, sized: np.ndarray, what: str, tile: int, **offsets) -> Tuple[Dict[str, torch.Tensor], int]:
+        """The device path's descriptors ``eo`` / ``cap`` / ``tp`` plus one per ``offsets`` entry
+        ``key=(name, array, alignment)``, and the tile count: ``sized[i]`` bytes of segment i
+        (``what`` in the message) are cut into tiles of ``tile`` bytes."""
+        op, es = self.op, self.es
+        arrays = {"eo": self.eo, "cap": self.cap, "tp": None}
+        for key, (name, offs, align) in (("eo", ("ES", self.eo, 16)), *offsets.items()):
+            if np.any(offs % align):
+                raise ValueError(f"{op}: {name} offsets must be {align}-byte aligned on device")
+            arrays[key] = offs
+        if np.any(sized >= 2 ** 31 - tile):
+            raise ValueError(f"{op}: a segment's {what} must be below 2 GiB")
+        # the video ES is read in dwords: a segment may not reach into a trailing partial dword of the buffer
+        if np.any(self.eo + self.cap > es.numel() - es.numel() % 4):
+            raise ValueError(f"{op}: ES range reaches the buffer's last partial dword on device")
+        tile_prefix = np.zeros(self.B + 1, dtype=np.int64)
+        np.cumsum((sized + tile - 1) // tile, out=tile_prefix[1:])
+        arrays["tp"] = tile_prefix
+        return pack_to_device(arrays, self.dev), int(tile_prefix[-1])
+
+
 def index_batch(res: DemuxResult, caps: Sequence[int], max_nal: int = DEFAULT_MAX_NAL) -> EsIndex:
     """Index every segment of a demuxed batch on the device its tensors live on.  ``caps[i]``
     bounds segment i's ES bytes (what ``demux_batch`` was sized with)."""
-    eo = np.asarray(res.es_offs, dtype=np.int64)
-    cap = np.asarray(caps, dtype=np.int64)
-    B = len(eo)
-    max_pes = int(res.pes.shape[2])
     max_nal = int(max_nal)
     if max_nal <= 0:
         raise ValueError("index_batch: max_nal must be positive")
-    es = res.es
-    check_ranges("index_batch", "ES", eo, cap, es.numel())
-    dev = es.device
-    if dev.type == "cpu":
-        nal = np.empty((B, max_nal, 4), dtype=np.int32)
-        au = np.empty((B, max_pes, 4), dtype=np.int32)
-        aframes = np.empty((B, max_pes, 2), dtype=np.int32)
-        sinfo = np.empty((B, SINFO_WORDS), dtype=np.int64)
-        _rt().index_batch(es.numpy(), eo, cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal, nal, au, aframes,
-                          sinfo)
-        return EsIndex(torch.from_numpy(nal), torch.from_numpy(au), torch.from_numpy(aframes), torch.from_numpy(sinfo))
-    if np.any(eo % 16):
-        raise ValueError("index_batch: ES offsets must be 16-byte aligned on device")
-    tile = _dev().es_index_tile_bytes()
-    if np.any(cap >= 2 ** 31 - tile):
-        raise ValueError("index_batch: a segment's ES must be below 2 GiB")
-    # the video ES is read in dwords: a segment may not reach into a trailing partial dword of the buffer
-    if np.any(eo + cap > es.numel() - es.numel() % 4):
-        raise ValueError("index_batch: ES range reaches the buffer's last partial dword on device")
-    tiles = (cap + tile - 1) // tile
-    tile_prefix = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(tiles, out=tile_prefix[1:])
-    total_tiles = int(tile_prefix[-1])
-    d = pack_to_device({"eo": eo, "cap": cap, "tp": tile_prefix}, dev)
-    scratch = torch.empty(_dev().es_index_scratch_words(total_tiles, B, max_nal), dtype=torch.int32, device=dev)
-    nal = torch.empty((B, max_nal, 4), dtype=torch.int32, device=dev)
-    au = torch.empty((B, max_pes, 4), dtype=torch.int32, device=dev)
-    aframes = torch.empty((B, max_pes, 2), dtype=torch.int32, device=dev)
-    sinfo = torch.empty((B, SINFO_WORDS), dtype=torch.int64, device=dev)
+    plan = BatchPlan("index_batch", res, caps)
+    B, max_pes, rt = plan.B, plan.max_pes, _rt()
+    ix = EsIndex(plan.table(max_nal, rt.ES_NAL_WORDS), plan.table(max_pes, rt.ES_AU_WORDS),
+                 plan.table(max_pes, rt.ES_APES_WORDS), plan.table(0, SINFO_WORDS, torch.int64))
+    if plan.dev.type == "cpu":
+        rt.index_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
+                       ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy())
+        return ix
+    d, total_tiles = plan.on_device(plan.cap, "ES", _dev().es_index_tile_bytes())
+    scratch = torch.empty(_dev().es_index_scratch_words(total_tiles, B, max_nal), dtype=torch.int32, device=plan.dev)
     if B:
-        _dev().es_index(es, d["eo"], d["cap"], d["tp"], total_tiles, res.info, res.pes, max_pes, max_nal, scratch, nal,
-                        au, aframes, sinfo)
-    return EsIndex(nal, au, aframes, sinfo)
+        _dev().es_index(res.es, d["eo"], d["cap"], d["tp"], total_tiles, res.info, res.pes, max_pes, max_nal, scratch,
+                        ix.nal, ix.au, ix.aframes, ix.sinfo)
+    return ix

@@ -26,8 +26,8 @@ import torch
 
 from ._native import device as _dev
 from ._native import runtime as _rt
-from .desc import check_ranges, pack_to_device
-from .esindex import EsIndex
+from .desc import check_ranges
+from .esindex import BatchPlan, EsIndex
 from .tsdemux import DemuxResult
 
 RINFO = {"status": 0, "video_payload_bytes": 1, "n_vsamples": 2, "audio_box_offset": 3, "audio_payload_bytes": 4,
@@ -41,12 +41,12 @@ OUT_ALIGN = 256
 
 def remux_out_bytes(cap, max_nal: int):
     """Bytes of a segment's output region (scalar or array ``cap``): ``cap + max_nal + 32``."""
-    return cap + max_nal + 32
+    return _rt().remux_out_bytes(cap, max_nal)
 
 
 def remux_scratch_words(nseg: int, max_nal: int, max_aframes: int) -> int:
     """``int32`` elements of the device scratch of one ``remux_batch`` call."""
-    return nseg * (10 + 2 * (max_nal + max_aframes))
+    return _rt().remux_scratch_words(nseg, max_nal, max_aframes)
 
 
 def layout_out(caps: Sequence[int], max_nal: int, align: int = OUT_ALIGN) -> Tuple[np.ndarray, int]:
@@ -62,9 +62,9 @@ def layout_out(caps: Sequence[int], max_nal: int, align: int = OUT_ALIGN) -> Tup
 
 @dataclass
 class Remuxed:
-    rinfo: torch.Tensor     # int64[B, 8]
-    vsamples: torch.Tensor  # int32[B, max_pes, 5]
-    asamples: torch.Tensor  # int32[B, max_aframes, 2]
+    rinfo: torch.Tensor     # int64[B, RINFO_WORDS]
+    vsamples: torch.Tensor  # int32[B, max_pes, ES_VSAMPLE_WORDS]
+    asamples: torch.Tensor  # int32[B, max_aframes, ES_ASAMPLE_WORDS]
     out: torch.Tensor       # uint8, the caller's buffer
     out_offs: np.ndarray    # int64[B]
 
@@ -89,58 +89,38 @@ def remux_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], out: torch.T
     ``caps`` are what ``index_batch`` took; segment i's boxes go to ``out[out_offs[i]:]``, a region
     of :func:`remux_out_bytes` bytes (:func:`layout_out` lays them out) of which only the box
     headers and payloads are written."""
-    eo = np.asarray(res.es_offs, dtype=np.int64)
-    cap = np.asarray(caps, dtype=np.int64)
     oo = np.asarray(out_offs, dtype=np.int64)
-    B = len(eo)
-    max_pes = int(res.pes.shape[2])
+    B, max_pes, dev, rt = len(res.es_offs), int(res.pes.shape[2]), res.es.device, _rt()
     max_nal = int(ix.nal.shape[1])
     max_aframes = int(max_aframes)
     if max_aframes <= 0:
         raise ValueError("remux_batch: max_aframes must be positive")
-    es = res.es
-    dev = es.device
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
         raise ValueError("remux_batch: out must be a contiguous one-dimensional uint8 tensor")
     if out.device != dev or ix.nal.device != dev:
         raise ValueError("remux_batch: the batch, its index and out must be on one device")
-    if tuple(ix.nal.shape) != (B, max_nal, 4) or tuple(ix.au.shape) != (B, max_pes, 4) \
-            or tuple(ix.aframes.shape) != (B, max_pes, 2) or tuple(ix.sinfo.shape) != (B, 8):
+    if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
+            or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
+            or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
         raise ValueError("remux_batch: the index does not belong to this batch")
-    check_ranges("remux_batch", "ES", eo, cap, es.numel())
-    region = remux_out_bytes(cap, max_nal)
+    plan = BatchPlan("remux_batch", res, caps)
+    region = remux_out_bytes(plan.cap, max_nal)
     check_ranges("remux_batch", "output", oo, region, out.numel())
     order = np.argsort(oo, kind="stable")
     if np.any(oo[order][1:] < (oo + region)[order][:-1]):
         raise ValueError("remux_batch: output regions overlap")
+    rx = Remuxed(plan.table(0, RINFO_WORDS, torch.int64), plan.table(max_pes, rt.ES_VSAMPLE_WORDS),
+                 plan.table(max_aframes, rt.ES_ASAMPLE_WORDS), out, oo)
     if dev.type == "cpu":
-        vsamples = np.empty((B, max_pes, 5), dtype=np.int32)
-        asamples = np.empty((B, max_aframes, 2), dtype=np.int32)
-        rinfo = np.empty((B, RINFO_WORDS), dtype=np.int64)
-        _rt().remux_batch(es.numpy(), eo, cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal, ix.nal.numpy(),
-                          ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), max_aframes, vsamples, asamples, rinfo,
-                          out.numpy(), oo)
-        return Remuxed(torch.from_numpy(rinfo), torch.from_numpy(vsamples), torch.from_numpy(asamples), out, oo)
-    if np.any(eo % 16):
-        raise ValueError("remux_batch: ES offsets must be 16-byte aligned on device")
-    if np.any(oo % OUT_ALIGN):
-        raise ValueError(f"remux_batch: output offsets must be {OUT_ALIGN}-byte aligned on device")
+        rt.remux_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
+                       ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), max_aframes,
+                       rx.vsamples.numpy(), rx.asamples.numpy(), rx.rinfo.numpy(), out.numpy(), oo)
+        return rx
     tile = _dev().remux_tile_bytes()
-    if np.any(region >= 2 ** 31 - tile):
-        raise ValueError("remux_batch: a segment's output region must be below 2 GiB")
-    # the video ES is read in dwords: a segment may not reach into a trailing partial dword of the buffer
-    if np.any(eo + cap > es.numel() - es.numel() % 4):
-        raise ValueError("remux_batch: ES range reaches the buffer's last partial dword on device")
-    tiles = (region + tile - 1) // tile
-    tile_prefix = np.zeros(B + 1, dtype=np.int64)
-    np.cumsum(tiles, out=tile_prefix[1:])
-    total_tiles = int(tile_prefix[-1])
-    d = pack_to_device({"eo": eo, "cap": cap, "tp": tile_prefix, "oo": oo}, dev)
+    d, total_tiles = plan.on_device(region, "output region", tile, oo=("output", oo, OUT_ALIGN))
     scratch = torch.empty(_dev().remux_scratch_words(B, max_nal, max_aframes), dtype=torch.int32, device=dev)
-    vsamples = torch.empty((B, max_pes, 5), dtype=torch.int32, device=dev)
-    asamples = torch.empty((B, max_aframes, 2), dtype=torch.int32, device=dev)
-    rinfo = torch.empty((B, RINFO_WORDS), dtype=torch.int64, device=dev)
     if B:
-        _dev().remux(es, d["eo"], d["cap"], d["tp"], total_tiles, res.info, res.pes, max_pes, max_nal, ix.nal, ix.au,
-                     ix.aframes, ix.sinfo, max_aframes, scratch, vsamples, asamples, rinfo, out, d["oo"])
-    return Remuxed(rinfo, vsamples, asamples, out, oo)
+        _dev().remux(res.es, d["eo"], d["cap"], d["tp"], total_tiles, res.info, res.pes, max_pes, max_nal, ix.nal,
+                     ix.au, ix.aframes, ix.sinfo, max_aframes, scratch, rx.vsamples, rx.asamples, rx.rinfo, out,
+                     d["oo"])
+    return rx

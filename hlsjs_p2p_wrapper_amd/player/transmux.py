@@ -23,7 +23,7 @@ from __future__ import annotations
 
 import threading
 import time
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -167,7 +167,7 @@ class MediaPipeline:
         try:
             b = self._launch_core(self._job_columns(jobs))
         except Exception as e:  # deliver the failure to every job of the batch
-            return _Batch(jobs, infos=[], host=[], error=e, n=len(jobs))
+            return _Batch(jobs, groups=[], error=e, n=len(jobs))
         b.jobs = jobs
         return b
 
@@ -334,7 +334,7 @@ class MediaPipeline:
                 verify.append((side, _to_host(okd)))
             if fuse.any():
                 ex = np.where(fuse, c.expect, -1)[rows]
-        groups: List[Any] = []
+        groups: List[_Group] = []
         keep = ev0 = None
         if not len(rows):  # nothing to decrypt or demux (the CRC checks above still run)
             pass
@@ -348,49 +348,40 @@ class MediaPipeline:
                 _ts.DEFAULT_MAX_PES, ex, cw, ctab)
             keep = (dec, host_block)
             for gidx, info, pes, es, es_offs, hinfo, hlens in out:
-                groups.append((rows[gidx], _ts.DemuxResult(info, pes, es, es_offs), hinfo, hlens))
+                groups.append(_Group(rows[gidx], _ts.DemuxResult(info, pes, es, es_offs), hinfo, hlens))
             if fused is not None:  # rows of the launch -> rows of the batch
                 verify.append((rows[fused[0]], fused[1]))
         else:
             groups = self._host_groups(c, rows)
-        infos, host, index, remux = [], [], [], []
-        for idx, res, hinfo, hlens in groups:
-            infos.append((idx, res, res.es_offs, hlens))
-            host.append((hinfo, hlens))
+        for g in groups:
             # the sample index of a group in which any row asked for it: one ``index_batch`` call
             # after the group's demux on the same stream, its ``sinfo`` rows on their way to the
             # host before the batch's event
-            ix = None
-            if c.index is not None and c.index[idx].any():
-                from ..ops import esindex as _esx
+            if c.index is None or not c.index[g.rows].any():
+                continue
+            from ..ops import esindex as _esx
 
-                ix = _esx.index_batch(res, c.nb[idx])
-                # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
-                # the index, its three tables on the same way to the host
-                if c.remux is not None and c.remux[idx].any():
-                    from ..ops import remux as _rmx
+            g.ix = ix = _esx.index_batch(g.res, c.nb[g.rows])
+            g.sinfo = _to_host(ix.sinfo)
+            # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
+            # the index, its three tables on the same way to the host
+            if c.remux is not None and c.remux[g.rows].any():
+                from ..ops import remux as _rmx
 
-                    out_offs, size = _rmx.layout_out(c.nb[idx], ix.nal.shape[1])
-                    rx = _rmx.remux_batch(res, ix, c.nb[idx],
-                                          torch.empty(size + ALIGN, dtype=torch.uint8, device=res.es.device), out_offs)
-                    remux.append((rx, _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)))
-                else:
-                    remux.append(None)
-                ix = (ix, _to_host(ix.sinfo))
-            else:
-                remux.append(None)
-            index.append(ix)
+                out_offs, size = _rmx.layout_out(c.nb[g.rows], ix.nal.shape[1])
+                g.rx = rx = _rmx.remux_batch(g.res, ix, c.nb[g.rows],
+                                             torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
+                                             out_offs)
+                g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
-        return _Batch(None, infos=infos, host=host, event=ev, keep=keep, tag=tag, n=n, start=ev0,
-                      verify=verify or None, expect_mask=mask, index=index if any(index) else None,
-                      remux=remux if any(remux) else None)
+        return _Batch(None, groups=groups, event=ev, keep=keep, tag=tag, n=n, start=ev0, verify=verify or None,
+                      expect_mask=mask)
 
-    def _host_groups(self, c: _Columns, rows: np.ndarray) -> List[Any]:
+    def _host_groups(self, c: _Columns, rows: np.ndarray) -> List["_Group"]:
         """The host backend: ``ops.aes.cbc_decrypt_batch`` over the encrypted rows, then
-        ``ops.tsdemux.demux_batch`` per group.  Returns ``(rows of the batch, DemuxResult, info
-        rows, plaintext lengths)`` per group, like the native call's groups."""
+        ``ops.tsdemux.demux_batch`` per group, like the native call's groups."""
         dev = self.device
         work = []
         e, cl = rows[c.enc[rows]], rows[~c.enc[rows]]
@@ -408,7 +399,8 @@ class MediaPipeline:
             es_offs, size = _layout(caps)
             es = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
             res = _ts.demux_batch(buf, offs, lens, es, es_offs, caps=caps)
-            groups.append((idx, res, _to_host(res.info), _to_host(lens) if isinstance(lens, torch.Tensor) else lens))
+            hlens = _to_host(lens) if isinstance(lens, torch.Tensor) else lens
+            groups.append(_Group(idx, res, _to_host(res.info), hlens))
         return groups
 
     # ------------------------------------------------------------------ completion
@@ -424,11 +416,11 @@ class MediaPipeline:
         t3 = time.perf_counter()
         self._wait(batch)
         self.timer.add("wait_device", time.perf_counter() - t3)
-        for (idx, _res, _es_offs, _lens), (hinfo, hlens) in zip(batch.infos, batch.host):
-            k = len(idx)
-            rows[idx] = _np(hinfo)[:k]
-            plain[idx] = _np(hlens)[:k]
-            has[idx] = True
+        for g in batch.groups:
+            k = len(g.rows)
+            rows[g.rows] = _np(g.hinfo)[:k]
+            plain[g.rows] = _np(g.hlens)[:k]
+            has[g.rows] = True
         return rows, plain, has
 
     def complete_arrays(self, batch: Optional["_Batch"]):
@@ -465,10 +457,11 @@ class MediaPipeline:
         results: List[Any] = [None] * b.n
         for i in np.flatnonzero(~has).tolist():  # rejected before launch
             results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1}
-        for g, (idx, res, es_offs, _lens) in enumerate(b.infos):
+        for g in b.groups:
+            res = g.res
             es = res.es
-            il = idx.tolist()
-            for k, (i, base) in enumerate(zip(il, es_offs.tolist())):
+            il = g.rows.tolist()
+            for k, (i, base) in enumerate(zip(il, res.es_offs.tolist())):
                 row = rl[i]
                 # ES views (per class, at the row's offsets from base) are built on first access: the
                 # buffer path only needs their byte counts, which the info row holds
@@ -477,18 +470,13 @@ class MediaPipeline:
                 if pl[i] < 0:
                     r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
                 results[i] = r
-            gi = b.index[g] if b.index is not None else None
-            if gi is not None:  # the jobs of this group that asked for the sample index
-                ix, hs = gi
-                srows = _np(hs).tolist()
+            if g.ix is not None:  # the jobs of this group that asked for the sample index
+                srows = _np(g.sinfo).tolist()
                 for k, i in enumerate(il):
                     if b.jobs[i].index:
-                        results[i]["samples"] = Samples(srows[k], ix, k)
-                gr = b.remux[g] if b.remux is not None else None
-                if gr is not None:  # ... and those that asked for the remux
-                    for k, i in enumerate(il):
-                        if b.jobs[i].remux:
-                            results[i]["fmp4"] = Fmp4(gr, k, srows[k])
+                        results[i]["samples"] = Samples(srows[k], g.ix, k)
+                    if g.rx is not None and b.jobs[i].remux:  # ... and those that asked for the remux
+                        results[i]["fmp4"] = Fmp4(g, k, srows[k])
         self.timer.add("results", time.perf_counter() - t4)
         return results
 
@@ -563,7 +551,31 @@ class InfoRow:
         return f"InfoRow({self.to_dict()})"
 
 
-class Samples:
+class _View:
+    """The read-only mapping protocol of the result views below, from ``keys()`` and ``__getitem__``."""
+
+    __slots__ = ()
+
+    def get(self, name: str, default=None):
+        try:
+            return self[name]
+        except KeyError:
+            return default
+
+    def items(self):
+        return ((k, self[k]) for k in self.keys())
+
+    def __contains__(self, name) -> bool:
+        return name in self.keys()
+
+    def __iter__(self):
+        return iter(self.keys())
+
+    def __len__(self) -> int:
+        return len(self.keys())
+
+
+class Samples(_View):
     """Read-only mapping of one fragment's sample index (``TransmuxJob.index``): the ``sinfo``
     fields by name (:data:`ops.esindex.SINFO`), ``independent`` (access unit 0 holds a
     keyframe), and ``nal`` / ``au`` / ``aframes``: the fragment's rows of the batch's device
@@ -589,35 +601,17 @@ class Samples:
             return getattr(self._ix, name)[self._k]
         raise KeyError(name)
 
-    def get(self, name: str, default=None):
-        try:
-            return self[name]
-        except KeyError:
-            return default
-
     def keys(self):
         from ..ops.esindex import SINFO
 
         return list(SINFO) + ["independent", *self._TABLES]
-
-    def items(self):
-        return ((k, self[k]) for k in self.keys())
-
-    def __contains__(self, name) -> bool:
-        return name in self.keys()
-
-    def __iter__(self):
-        return iter(self.keys())
-
-    def __len__(self) -> int:
-        return len(self.keys())
 
     def __repr__(self) -> str:
         fields = {k: self[k] for k in self.keys() if k not in self._TABLES}
         return f"Samples({fields})"
 
 
-class Fmp4Track:
+class Fmp4Track(_View):
     """Read-only mapping of one remuxed track of a fragment: ``mdat`` (a device view of the whole
     box, header included), ``samples`` (the filled device rows of the track's sample table),
     ``nb`` (samples), ``base`` / ``duration`` / ``timescale`` (the fragment's decode time and
@@ -634,8 +628,8 @@ class Fmp4Track:
     def _host_rows(self) -> np.ndarray:
         f = self._f
         if self._video:
-            return _np(f._g[2])[f._k, :self["nb"]]
-        rows = _np(f._g[3])[f._k]
+            return _np(f._g.vsamples)[f._k, :self["nb"]]
+        rows = _np(f._g.asamples)[f._k]
         return rows[:self["nb"]]
 
     def moof(self, sequence_number: int) -> bytes:
@@ -655,11 +649,11 @@ class Fmp4Track:
         from . import fmp4 as _fmp4
 
         f = self._f
-        rx = f._g[0]
+        rx = f._g.rx
         if name == "nb":
             if self._video:
                 return f._rinfo("n_vsamples")
-            return int((_np(f._g[3])[f._k, :, 0] >= 0).sum())
+            return int((_np(f._g.asamples)[f._k, :, 0] >= 0).sum())
         if name == "mdat":
             o = int(rx.out_offs[f._k]) + (0 if self._video else f._rinfo("audio_box_offset"))
             return rx.out.narrow(0, o, 8 + f._rinfo("video_payload_bytes" if self._video else "audio_payload_bytes"))
@@ -679,32 +673,14 @@ class Fmp4Track:
             return self.moof
         raise KeyError(name)
 
-    def get(self, name: str, default=None):
-        try:
-            return self[name]
-        except KeyError:
-            return default
-
     def keys(self):
         return list(self._KEYS)
-
-    def items(self):
-        return ((k, self[k]) for k in self._KEYS)
-
-    def __contains__(self, name) -> bool:
-        return name in self._KEYS
-
-    def __iter__(self):
-        return iter(self._KEYS)
-
-    def __len__(self) -> int:
-        return len(self._KEYS)
 
     def __repr__(self) -> str:
         return f"Fmp4Track({'video' if self._video else 'audio'}, nb={self['nb']})"
 
 
-class Fmp4:
+class Fmp4(_View):
     """Read-only mapping of one fragment's remux (``TransmuxJob.remux``): ``video`` and ``audio``
     (:class:`Fmp4Track`) and the ``rinfo`` fields by name (:data:`ops.remux.RINFO`)."""
 
@@ -713,7 +689,7 @@ class Fmp4:
     def __init__(self, group, k: int, sinfo_row) -> None:
         from ..ops.esindex import SINFO
 
-        self._g = group  # (Remuxed, host rinfo, host vsamples, host asamples) of the fragment's group
+        self._g = group  # the fragment's _Group: its Remuxed and the three host tables
         self._k = k
         self._rate = sinfo_row[SINFO["audio_sample_rate"]]
         self._tracks: Dict[str, Fmp4Track] = {}
@@ -721,7 +697,7 @@ class Fmp4:
     def _rinfo(self, name: str) -> int:
         from ..ops.remux import RINFO
 
-        return int(_np(self._g[1])[self._k, RINFO[name]])
+        return int(_np(self._g.rinfo)[self._k, RINFO[name]])
 
     def __getitem__(self, name: str):
         from ..ops.remux import RINFO
@@ -735,38 +711,34 @@ class Fmp4:
             return self._rinfo(name)
         raise KeyError(name)
 
-    def get(self, name: str, default=None):
-        try:
-            return self[name]
-        except KeyError:
-            return default
-
     def keys(self):
         from ..ops.remux import RINFO
 
         return ["video", "audio", *RINFO]
-
-    def items(self):
-        return ((k, self[k]) for k in self.keys())
-
-    def __contains__(self, name) -> bool:
-        return name in self.keys()
-
-    def __iter__(self):
-        return iter(self.keys())
-
-    def __len__(self) -> int:
-        return len(self.keys())
 
     def __repr__(self) -> str:
         return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio')} })"
 
 
 @dataclass(eq=False)
+class _Group:
+    """One demux group of a batch (its encrypted rows, or its clear ones) and what was run on it."""
+    rows: np.ndarray  # rows of the batch, in the group's order
+    res: Any  # the group's DemuxResult, on the device
+    hinfo: Any  # its info rows and ...
+    hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
+    ix: Any = None  # EsIndex, when a job of the group asked for it, with ...
+    sinfo: Any = None  # ... its sinfo rows on the host
+    rx: Any = None  # Remuxed, when a job of the group asked for it, with ...
+    rinfo: Any = None  # ... its three tables on the host
+    vsamples: Any = None
+    asamples: Any = None
+
+
+@dataclass(eq=False)
 class _Batch:
     jobs: List[TransmuxJob]
-    infos: Any = None
-    host: Any = None
+    groups: List[_Group] = field(default_factory=list)
     event: Any = None
     error: Optional[BaseException] = None
     keep: Any = None  # device/pinned buffers the batch's in-flight work uses
@@ -775,8 +747,15 @@ class _Batch:
     start: Any = None  # timing event recorded before the batch's first launch
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
-    index: Any = None  # per group of infos: (EsIndex, host sinfo rows) or None (no job of the batch asked: None)
-    remux: Any = None  # per group of infos: (Remuxed, host rinfo, vsamples, asamples) or None (nobody asked: None)
+
+    # the groups as the benchmark's output dump reads them: derived, nothing is stored twice
+    @property
+    def infos(self):
+        return [(g.rows, g.res, g.res.es_offs, g.hlens) for g in self.groups]
+
+    @property
+    def host(self):
+        return [(g.hinfo, g.hlens) for g in self.groups]
 
 
 _local = threading.local()

@@ -281,6 +281,16 @@ def tiny_segments(seed: int = 27):
             seg(SC + b"\x65", vpes=[0]), seg(b"\x00", vpes=[0])]
 
 
+def many_nal_segments(seed: int = 28):
+    """4200 kept NALs of 1..3 bytes in 6 access units of 700: more than 4096 rows, so the copy
+    kernel's wave lookup of a tile's rows runs three 64-way levels, and 25200 payload bytes, so the
+    payload crosses a copy-tile edge."""
+    rng = np.random.default_rng(seed)
+    v, offs = annexb([[body(rng, 0x65 if a == 0 else 0x41, 1 + (700 * a + j) % 3) for j in range(700)]
+                      for a in range(6)])
+    return [seg(v, vpes=offs)]
+
+
 def mixed_segments(T: int):
     return (dropping_segments() + codec_segments() + timestamp_segments() + adts_segments() + tiny_segments()
             + alignment_segments() + audio_overflow_segments() + tile_edge_segments(T)[-2:])
@@ -299,6 +309,7 @@ CASES = {
     "tiny": lambda T: (tiny_segments(), 8, 2048, 1024),
     "no_segments": lambda T: ([], 8, 2048, 1024),
     "mixed": lambda T: (mixed_segments(T), 8, 128, 4),
+    "many_nals": lambda T: (many_nal_segments(), 8, 8192, 1024),
 }
 
 

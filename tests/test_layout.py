@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from esindex_cases import background, hand_batch, plant, seg
-from hlsjs_p2p_wrapper_amd.ops import crc, esindex, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import crc, esindex, remux, tsdemux
 from hlsjs_p2p_wrapper_amd.ops._native import device
 from hlsjs_p2p_wrapper_amd.ops.desc import pack_to_device
 
@@ -23,6 +23,22 @@ def test_python_tables_equal_the_runtime_exports(rt):
     assert esindex.DEFAULT_MAX_NAL == rt.ES_DEFAULT_MAX_NAL
     assert max(tsdemux.INFO.values()) < tsdemux.INFO_WORDS and len(set(tsdemux.INFO.values())) == len(tsdemux.INFO)
     assert sorted(esindex.SINFO.values()) == list(range(esindex.SINFO_WORDS))
+    assert remux.RINFO == dict(rt.ES_RINFO) and remux.RINFO_WORDS == rt.ES_RINFO_WORDS
+    assert sorted(remux.RINFO.values()) == list(range(remux.RINFO_WORDS))
+    assert remux.RSTATUS == dict(rt.ES_RSTATUS) and remux.SAMPLE_FLAGS == dict(rt.ES_SAMPLE_FLAGS)
+    assert remux.DEFAULT_MAX_AFRAMES == rt.ES_DEFAULT_MAX_AFRAMES and remux.OUT_ALIGN == rt.ES_OUT_ALIGN
+    # the row widths are the shapes the two batch calls return
+    res, caps = hand_batch([seg(b"\x00\x00\x01\x65\x11", vpes=[0]), seg(b"")], "cpu", max_pes=4)
+    assert tuple(res.pes.shape) == (2, rt.TS_CLASSES, 4, rt.TS_PES_WORDS)
+    ix = esindex.index_batch(res, caps, max_nal=6)
+    assert tuple(ix.nal.shape) == (2, 6, rt.ES_NAL_WORDS) and tuple(ix.au.shape) == (2, 4, rt.ES_AU_WORDS)
+    assert tuple(ix.aframes.shape) == (2, 4, rt.ES_APES_WORDS) and tuple(ix.sinfo.shape) == (2, rt.ES_SINFO_WORDS)
+    offs, size = remux.layout_out(caps, 6)
+    rx = remux.remux_batch(res, ix, caps, torch.zeros(size, dtype=torch.uint8), offs, max_aframes=3)
+    assert tuple(rx.vsamples.shape) == (2, 4, rt.ES_VSAMPLE_WORDS) and tuple(rx.rinfo.shape) == (2, rt.ES_RINFO_WORDS)
+    assert tuple(rx.asamples.shape) == (2, 3, rt.ES_ASAMPLE_WORDS)
+    assert (rt.TS_PES_WORDS, rt.ES_NAL_WORDS, rt.ES_AU_WORDS, rt.ES_APES_WORDS) == (3, 4, 4, 2)
+    assert (rt.ES_VSAMPLE_WORDS, rt.ES_ASAMPLE_WORDS) == (5, 2)
 
 
 def test_per_class_info_slots_are_base_plus_class():
