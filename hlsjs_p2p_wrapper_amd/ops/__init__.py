@@ -1,11 +1,13 @@
-"""Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``): import the
-submodule you need.  The entry points of the sample index and of the remux are also reachable
-from the package (``ops.index_batch``, ``ops.EsIndex``, ``ops.remux_batch``, ``ops.Remuxed``),
+"""Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
+``codecconfig``): import the submodule you need.  The entry points of the sample index, of the
+remux and of the codec configuration are also reachable from the package (``ops.index_batch``,
+``ops.EsIndex``, ``ops.remux_batch``, ``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``),
 resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
-__all__ = list(_ESINDEX + _REMUX)
+_CODECCONFIG = ("config_batch", "CodecConfig")
+__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG)
 
 
 def __getattr__(name):
@@ -17,4 +19,8 @@ def __getattr__(name):
         from . import remux
 
         return getattr(remux, name)
+    if name in _CODECCONFIG:
+        from . import codecconfig
+
+        return getattr(codecconfig, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

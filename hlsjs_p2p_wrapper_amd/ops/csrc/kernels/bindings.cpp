@@ -113,8 +113,9 @@ void ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int
 // outputs, cap the host upper bound of each segment's ES bytes (the Python wrapper has checked
 // es_off + cap against es), tile_prefix the exclusive prefix of the op's tiles per segment.
 // `before_tables` runs between the checks of pes and nal, where es_index checks its scratch.
+// An op without a tile space (codec_config) passes no tile_prefix and 0 tiles.
 template <typename F>
-D::EsBatch es_batch(const Tensor& es, const Tensor& es_off, const Tensor& cap, const Tensor& tile_prefix,
+D::EsBatch es_batch(const Tensor& es, const Tensor& es_off, const Tensor& cap, const c10::optional<Tensor>& tile_prefix,
                     int64_t total_tiles, const Tensor& info, const Tensor& pes, int64_t max_pes, int64_t max_nal,
                     const Tensor& nal, const Tensor& au, const Tensor& aframes, const Tensor& sinfo,
                     F&& before_tables) {
@@ -122,7 +123,7 @@ D::EsBatch es_batch(const Tensor& es, const Tensor& es_off, const Tensor& cap, c
   D::EsBatch b{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
                .es_off = check<int64_t>(es_off, "es_off"),
                .cap = check<int64_t>(cap, "cap", B),
-               .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
+               .tile_prefix = tile_prefix.has_value() ? check<int64_t>(*tile_prefix, "tile_prefix", B + 1) : nullptr,
                .nseg = static_cast<int>(B), .total_tiles = total_tiles,
                .info = check<int64_t>(info, "info", B * ts::kInfoWords),
                .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
@@ -172,6 +173,27 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
               "es / out must be 16-byte aligned");
   TORCH_CHECK(es.data_ptr() != out.data_ptr(), "remux cannot run in place");
   hip_ok(D::launch_remux(a), "remux launch");
+}
+
+// Codec configuration of a demuxed and indexed batch (codec_config.hip): the inputs of es_index
+// without a tile space, its four outputs, and per segment a cinfo row and two rows of max_ps bytes.
+void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
+                  Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_ps, Tensor cinfo, Tensor ps) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_nal > 0, "codec_config: max_pes / max_nal out of range");
+  TORCH_CHECK(es_::max_ps_ok(max_ps), "codec_config: max_ps must be a positive multiple of 16 up to 1024");
+  const D::CodecConfigArgs a{
+      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .max_ps = max_ps,
+      .ps = check<uint8_t>(ps, "ps", es_::ps_bytes(B, max_ps)),
+      .cinfo = check<int32_t>(cinfo, "cinfo", B * es_::kCinfoWords)};
+  TORCH_CHECK(es.device() == ps.device() && es.device() == cinfo.device() && es.device() == nal.device(),
+              "tensors on different devices");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(ps.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(nal.data_ptr()) & 15) == 0,
+              "es / ps / nal must be 16-byte aligned");
+  hip_ok(D::launch_codec_config(a), "codec_config launch");
 }
 
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
@@ -303,6 +325,8 @@ TORCH_LIBRARY(hlsp2p, m) {
         "int max_pes, int max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_aframes, "
         "Tensor(a!) scratch, Tensor(b!) vsamples, Tensor(c!) asamples, Tensor(d!) rinfo, Tensor(e!) out, "
         "Tensor out_off) -> ()");
+  m.def("codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
+        "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -313,6 +337,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("ts_demux", &ts_demux);
   m.impl("es_index", &es_index);
   m.impl("remux", &remux);
+  m.impl("codec_config", &codec_config);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -346,6 +371,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
     return es_::remux_scratch(nseg, max_nal, max_aframes).end;
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
+  m.def("codec_config", &codec_config);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

@@ -93,8 +93,9 @@ struct TsDemuxArgs {
 };
 hipError_t launch_ts_demux(const TsDemuxArgs& a);
 
-// A demuxed batch as the index and the remux take it: launch_ts_demux's outputs, the host caps
-// and a tile space over them, and the batch's four index tables.
+// A demuxed batch as the index, the remux and the codec configuration take it: launch_ts_demux's
+// outputs, the host caps and a tile space over them (none for an op of one workgroup per
+// segment), and the batch's four index tables.
 struct EsBatch {
   const uint8_t* es;
   int64_t es_numel;
@@ -124,6 +125,14 @@ struct RemuxArgs {
 };
 int remux_tile_bytes();
 hipError_t launch_remux(const RemuxArgs& a);
+
+struct CodecConfigArgs {
+  EsBatch b;       // no tile space (tile_prefix == nullptr, total_tiles == 0); ix is only read
+  int64_t max_ps;  // es::max_ps_ok(max_ps)
+  uint8_t* ps;     // es::ps_bytes(nseg, max_ps)
+  int32_t* cinfo;  // nseg x es::kCinfoWords
+};
+hipError_t launch_codec_config(const CodecConfigArgs& a);
 
 struct SegmentCopyArgs {
   const uint8_t* src;

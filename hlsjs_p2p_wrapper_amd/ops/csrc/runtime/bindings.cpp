@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "aes_host.hpp"
+#include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
 #include "locator.hpp"
@@ -62,7 +63,7 @@ void parallel_for(int64_t n, F&& f, int64_t work_bytes = -1) {
   for (auto& x : th) x.join();
 }
 
-// The demuxed and indexed batch index_batch and remux_batch take: its sizes are checked here, once
+// The demuxed and indexed batch index_batch, remux_batch and config_batch take: its sizes are checked here, once
 // (`more_ok`: the caller's own sizes, part of the same check), then each segment's ES range and,
 // right behind it, whatever `also(b)` checks of segment b.
 struct EsBatch {
@@ -466,6 +467,62 @@ PYBIND11_MODULE(_runtime, m) {
     fl["sync"] = int64_t(es::kSampleSync);
     fl["non_sync"] = int64_t(es::kSampleNonSync);
     m.attr("ES_SAMPLE_FLAGS") = fl;
+  }
+
+  // Batched CPU codec configuration with the device kernel's layout (docs/INITSEGMENT.md): the inputs of
+  // index_batch and its four outputs.
+  //   cinfo: int32[B, ES_CINFO_WORDS]; ps: uint8[B, 2, max_ps]
+  m.def("config_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
+                           int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au, Arr<int32_t> aframes,
+                           Arr<int64_t> sinfo, int64_t max_ps, py::array cinfo, py::array ps) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("config_batch: max_pes and max_nal must be positive");
+    if (!es::max_ps_ok(max_ps))
+      throw std::invalid_argument("config_batch: max_ps must be a positive multiple of 16 up to 1024");
+    int32_t* ci = mut_ptr<int32_t>(cinfo, "cinfo");
+    uint8_t* pp = mut_ptr<uint8_t>(ps, "ps");
+    const bool sized = cinfo.size() >= B * es::kCinfoWords && ps.size() >= es::ps_bytes(B, max_ps);
+    const EsBatch batch = es_batch("config_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
+    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      const es::Segment s = batch.at(b);
+      es::config_segment(s, es::index_tables_at(ix, s, b), max_ps, pp + es::ps_bytes(b, max_ps),
+                         ci + b * es::kCinfoWords);
+    }, batch.total);
+  });
+  m.attr("ES_CINFO_WORDS") = es::kCinfoWords;
+  m.attr("ES_DEFAULT_MAX_PS") = es::kDefaultMaxPs;
+  {
+    py::dict d, st;
+    d["status"] = int(es::kCStatus);
+    d["sps_nal"] = int(es::kCSpsNal);
+    d["sps_bytes"] = int(es::kCSpsBytes);
+    d["sps_rbsp_bytes"] = int(es::kCSpsRbspBytes);
+    d["pps_nal"] = int(es::kCPpsNal);
+    d["pps_bytes"] = int(es::kCPpsBytes);
+    d["profile_idc"] = int(es::kCProfileIdc);
+    d["profile_compat"] = int(es::kCProfileCompat);
+    d["level_idc"] = int(es::kCLevelIdc);
+    d["chroma_format_idc"] = int(es::kCChromaFormatIdc);
+    d["bit_depth_luma"] = int(es::kCBitDepthLuma);
+    d["bit_depth_chroma"] = int(es::kCBitDepthChroma);
+    d["width"] = int(es::kCWidth);
+    d["height"] = int(es::kCHeight);
+    d["sar_width"] = int(es::kCSarWidth);
+    d["sar_height"] = int(es::kCSarHeight);
+    d["aac_object_type"] = int(es::kCAacObjectType);
+    d["aac_rate_index"] = int(es::kCAacRateIndex);
+    d["aac_channel_config"] = int(es::kCAacChannelConfig);
+    m.attr("ES_CINFO") = d;
+    st["no_sps"] = int(es::kNoSps);
+    st["no_pps"] = int(es::kNoPps);
+    st["ps_overflow"] = int(es::kPsOverflow);
+    st["bad_sps"] = int(es::kBadSps);
+    st["unsupported_video"] = int(es::kConfigUnsupportedVideo);
+    st["no_audio_config"] = int(es::kNoAudioConfig);
+    m.attr("ES_CSTATUS") = st;
   }
 
   // ------------------------------------------------------------------ store

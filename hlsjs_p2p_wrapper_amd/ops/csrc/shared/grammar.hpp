@@ -1,6 +1,7 @@
-// The MPEG-TS / PES / NAL / ADTS byte rules that fill the rows of layout.hpp: the only definition
-// of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp) and by
-// the gfx950 kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip).  Plain inline
+// The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
+// definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
+// runtime/codec.cpp) and by the gfx950 kernels (kernels/ts_demux.hip, kernels/es_index.hip,
+// kernels/remux.hip, kernels/codec_config.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -288,6 +289,169 @@ HLSP2P_RULE AdtsFrame adts_frame_at(const uint8_t* A, int64_t q, int64_t end) {
   const int32_t hdr = (A[q + 1] & 1) ? 7 : 9;
   if (len < hdr || q + len > end) return {0, 0};
   return {len, hdr};
+}
+
+// ---- codec configuration (docs/INITSEGMENT.md)
+// The three ADTS header fields an AudioSpecificConfig is made of, from the frame at q.
+struct AdtsConfig { int32_t object_type, rate_index, channel_config; };
+HLSP2P_RULE AdtsConfig adts_config_at(const uint8_t* A, int64_t q) {
+  return {((A[q + 2] >> 6) & 3) + 1, (A[q + 2] >> 2) & 15, ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6)};
+}
+HLSP2P_RULE bool adts_config_usable(const AdtsConfig& c) { return c.rate_index < 13 && c.channel_config != 0; }
+
+// Byte j >= 2 of a NAL unit is an emulation-prevention byte iff it is 03 behind two raw zeros
+// (p2 = b[j - 2], p1 = b[j - 1], b = b[j]).  Equal to the sequential rule: a dropped byte is never zero.
+HLSP2P_RULE bool is_emulation_prevention(int p2, int p1, int b) { return b == 3 && p1 == 0 && p2 == 0; }
+
+// What sps_parse reads, in the order of the cinfo row (Cinfo kCProfileIdc .. kCSarHeight).
+struct SpsFields {
+  int32_t profile_idc, profile_compat, level_idc;
+  int32_t chroma_format_idc, bit_depth_luma, bit_depth_chroma, width, height, sar_width, sar_height;
+};
+constexpr int kSpsFieldWords = 10;
+static_assert(sizeof(SpsFields) == kSpsFieldWords * sizeof(int32_t) && kCSarHeight - kCProfileIdc + 1 == kSpsFieldWords,
+              "SpsFields is the cinfo row's kCProfileIdc .. kCSarHeight");
+
+// Most-significant-bit-first reader over RBSP bytes rb(0 .. n); a read past the end or a ue
+// with more than 31 leading zeros sets err and yields 0 from then on.
+template <class RB>
+struct SpsBits {
+  RB rb;
+  int64_t nbits, pos;
+  bool err;
+  HLSP2P_RULE uint32_t u(int k) {
+    uint32_t v = 0;
+    for (int i = 0; i < k; ++i) {
+      if (err || pos >= nbits) {
+        err = true;
+        return 0;
+      }
+      v = (v << 1) | ((static_cast<uint32_t>(rb(pos >> 3)) >> (7 - (pos & 7))) & 1u);
+      ++pos;
+    }
+    return v;
+  }
+  HLSP2P_RULE uint32_t ue() {
+    int z = 0;
+    while (!err && u(1) == 0 && !err) {
+      if (++z > 31) err = true;
+    }
+    if (err) return 0;
+    const uint32_t rest = u(z);
+    return err ? 0 : ((uint32_t(1) << z) - 1u) + rest;  // z <= 31: at most 2^32 - 2
+  }
+  HLSP2P_RULE int64_t se() {
+    const int64_t k = ue();
+    return (k & 1) ? (k + 1) / 2 : -(k / 2);
+  }
+};
+
+HLSP2P_RULE bool sps_high_profile(uint32_t p) {
+  return p == 100 || p == 110 || p == 122 || p == 244 || p == 44 || p == 83 || p == 86 || p == 118 || p == 128 ||
+         p == 138 || p == 139 || p == 134 || p == 135;
+}
+// the sample aspect ratio of aspect_ratio_idc 1..16 as (width << 16) | height, 0 for any other idc
+HLSP2P_RULE uint32_t sps_sar(uint32_t idc) {
+  switch (idc) {
+    case 1: return (1u << 16) | 1; case 2: return (12u << 16) | 11; case 3: return (10u << 16) | 11;
+    case 4: return (16u << 16) | 11; case 5: return (40u << 16) | 33; case 6: return (24u << 16) | 11;
+    case 7: return (20u << 16) | 11; case 8: return (32u << 16) | 11; case 9: return (80u << 16) | 33;
+    case 10: return (18u << 16) | 11; case 11: return (15u << 16) | 11; case 12: return (64u << 16) | 33;
+    case 13: return (160u << 16) | 99; case 14: return (4u << 16) | 3; case 15: return (3u << 16) | 2;
+    case 16: return (2u << 16) | 1; default: return 0;
+  }
+}
+
+// An H.264 sequence parameter set from its RBSP (the NAL without header byte and emulation
+// prevention): rb(i) is RBSP byte i < n.  false: an error (docs/INITSEGMENT.md lists them); f then
+// keeps profile_idc / profile_compat / level_idc as read (0 with n < 3) and 0 in every other field.
+// Every loop is bounded by a constant or consumes input, so any bytes terminate.
+template <class RB>
+HLSP2P_RULE bool sps_parse(RB rb, int64_t n, SpsFields& f) {
+  f = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  if (n < 3) return false;
+  SpsBits<RB> r = {rb, 8 * n, 0, false};
+  const uint32_t profile = r.u(8);
+  f.profile_idc = static_cast<int32_t>(profile);
+  f.profile_compat = static_cast<int32_t>(r.u(8));
+  f.level_idc = static_cast<int32_t>(r.u(8));
+  r.ue();  // seq_parameter_set_id
+  uint32_t chroma = 1, depth_luma = 0, depth_chroma = 0, separate = 0;
+  if (sps_high_profile(profile)) {
+    chroma = r.ue();
+    if (r.err || chroma > 3) return false;
+    if (chroma == 3) separate = r.u(1);
+    depth_luma = r.ue();
+    depth_chroma = r.ue();
+    if (r.err || depth_luma > 6 || depth_chroma > 6) return false;
+    r.u(1);  // qpprime_y_zero_transform_bypass
+    if (r.u(1)) {  // seq_scaling_matrix_present
+      const int lists = chroma == 3 ? 12 : 8;
+      for (int l = 0; l < lists && !r.err; ++l) {
+        if (!r.u(1)) continue;
+        const int entries = l < 6 ? 16 : 64;
+        int64_t last = 8, next = 8;
+        for (int e = 0; e < entries && !r.err; ++e) {
+          if (next != 0) next = (((last + r.se()) % 256) + 256) % 256;
+          last = next ? next : last;
+        }
+      }
+    }
+  }
+  r.ue();  // log2_max_frame_num_minus4
+  const uint32_t poc_type = r.ue();
+  if (r.err) return false;
+  if (poc_type == 0) {
+    r.ue();
+  } else if (poc_type == 1) {
+    r.u(1);
+    r.se();
+    r.se();
+    const uint32_t cycle = r.ue();
+    if (r.err || cycle > 255) return false;
+    for (uint32_t i = 0; i < cycle && !r.err; ++i) r.se();
+  }
+  r.ue();  // max_num_ref_frames
+  r.u(1);  // gaps_in_frame_num_value_allowed
+  const int64_t W = r.ue(), H = r.ue();
+  const int64_t F = r.u(1);
+  if (!F) r.u(1);  // mb_adaptive_frame_field
+  r.u(1);          // direct_8x8_inference
+  int64_t left = 0, right = 0, top = 0, bottom = 0;
+  if (r.u(1)) {  // frame_cropping
+    left = r.ue();
+    right = r.ue();
+    top = r.ue();
+    bottom = r.ue();
+  }
+  uint32_t sar_w = 1, sar_h = 1;
+  if (r.u(1) && r.u(1)) {  // vui_parameters_present, aspect_ratio_info_present
+    const uint32_t idc = r.u(8);
+    uint32_t w = sps_sar(idc) >> 16, h = sps_sar(idc) & 0xffff;
+    if (idc == 255) {
+      w = r.u(16);
+      h = r.u(16);
+    }
+    if (w != 0 && h != 0) {
+      sar_w = w;
+      sar_h = h;
+    }
+  }
+  if (r.err) return false;
+  const bool planes = chroma == 0 || separate != 0;
+  const int64_t cx = planes ? 1 : chroma == 3 ? 1 : 2;
+  const int64_t cy = (2 - F) * (planes ? 1 : chroma == 1 ? 2 : 1);
+  const int64_t width = 16 * (W + 1) - cx * (left + right);
+  const int64_t height = 16 * (2 - F) * (H + 1) - cy * (top + bottom);
+  if (width < 1 || width > 65535 || height < 1 || height > 65535) return false;
+  f.chroma_format_idc = static_cast<int32_t>(chroma);
+  f.bit_depth_luma = static_cast<int32_t>(8 + depth_luma);
+  f.bit_depth_chroma = static_cast<int32_t>(8 + depth_chroma);
+  f.width = static_cast<int32_t>(width);
+  f.height = static_cast<int32_t>(height);
+  f.sar_width = static_cast<int32_t>(sar_w);
+  f.sar_height = static_cast<int32_t>(sar_h);
+  return true;
 }
 
 // x - y as a sample duration (unsigned == true: 0 .. 2^31 - 1) or composition offset (the int32

@@ -139,6 +139,31 @@ constexpr RemuxScratch remux_scratch(int64_t nseg, int64_t max_nal, int64_t max_
   return {8, 9 + max_nal, 9 + 2 * max_nal, 10 + 2 * max_nal + max_aframes, 10 + 2 * (max_nal + max_aframes),
           nseg * (10 + 2 * (max_nal + max_aframes))};
 }
+
+// ---- codec configuration for the fMP4 init segment (docs/INITSEGMENT.md)
+constexpr int kCinfoWords = 19;
+constexpr int64_t kDefaultMaxPs = 256;  // stored bytes per parameter set
+constexpr int64_t kMaxPsLimit = 1024;   // max_ps: a positive multiple of kPsAlign up to this
+constexpr int kPsAlign = 16;
+constexpr bool max_ps_ok(int64_t max_ps) { return max_ps > 0 && max_ps <= kMaxPsLimit && max_ps % kPsAlign == 0; }
+constexpr int kPsRows = 2;  // ps [segment][kPsRows][max_ps] (uint8): row 0 the SPS, row 1 the PPS
+enum PsRow : int { kPsSps = 0, kPsPps = 1 };
+constexpr int64_t ps_bytes(int64_t nseg, int64_t max_ps) { return nseg * kPsRows * max_ps; }
+
+// cinfo[] row (int32), identical on host and device; kCProfileIdc .. kCSarHeight are SpsFields in order
+enum Cinfo : int {
+  kCStatus = 0,
+  kCSpsNal = 1,  // row of the nal table, -1: none
+  kCSpsBytes = 2, kCSpsRbspBytes = 3,
+  kCPpsNal = 4, kCPpsBytes = 5,
+  kCProfileIdc = 6, kCProfileCompat = 7, kCLevelIdc = 8,
+  kCChromaFormatIdc = 9, kCBitDepthLuma = 10, kCBitDepthChroma = 11,
+  kCWidth = 12, kCHeight = 13, kCSarWidth = 14, kCSarHeight = 15,
+  kCAacObjectType = 16, kCAacRateIndex = 17, kCAacChannelConfig = 18,
+};
+enum ConfigStatus : int32_t {
+  kNoSps = 1, kNoPps = 2, kPsOverflow = 4, kBadSps = 8, kConfigUnsupportedVideo = 16, kNoAudioConfig = 32,
+};
 }  // namespace es
 
 // ---------------------------------------------------------------- CRC-32

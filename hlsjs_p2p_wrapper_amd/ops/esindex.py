@@ -56,7 +56,7 @@ class EsIndex:
 
 
 class BatchPlan:
-    """What :func:`index_batch` and ``remux_batch`` settle before their launch, once: the batch's
+    """What :func:`index_batch`, ``remux_batch`` and ``config_batch`` settle before their launch, once: the batch's
     arrays with the ES ranges checked (``op`` names the caller in every message), one allocation
     per result table on the batch's device, and for the device path the launch rules, the tile
     space and the packed descriptors."""
@@ -80,9 +80,10 @@ class BatchPlan:
     def on_device(self, sized: np.ndarray, what: str, tile: int, **offsets) -> Tuple[Dict[str, torch.Tensor], int]:
         """The device path's descriptors ``eo`` / ``cap`` / ``tp`` plus one per ``offsets`` entry
         ``key=(name, array, alignment)``, and the tile count: ``sized[i]`` bytes of segment i
-        (``what`` in the message) are cut into tiles of ``tile`` bytes."""
+        (``what`` in the message) are cut into tiles of ``tile`` bytes.  ``tile == 0``: an op
+        without a tile space (one workgroup per segment): no ``tp``, a tile count of 0."""
         op, es = self.op, self.es
-        arrays = {"eo": self.eo, "cap": self.cap, "tp": None}
+        arrays = {"eo": self.eo, "cap": self.cap, "tp": None} if tile else {"eo": self.eo, "cap": self.cap}
         for key, (name, offs, align) in (("eo", ("ES", self.eo, 16)), *offsets.items()):
             if np.any(offs % align):
                 raise ValueError(f"{op}: {name} offsets must be {align}-byte aligned on device")
@@ -92,6 +93,8 @@ class BatchPlan:
         # the video ES is read in dwords: a segment may not reach into a trailing partial dword of the buffer
         if np.any(self.eo + self.cap > es.numel() - es.numel() % 4):
             raise ValueError(f"{op}: ES range reaches the buffer's last partial dword on device")
+        if not tile:
+            return pack_to_device(arrays, self.dev), 0
         tile_prefix = np.zeros(self.B + 1, dtype=np.int64)
         np.cumsum((sized + tile - 1) // tile, out=tile_prefix[1:])
         arrays["tp"] = tile_prefix

@@ -96,7 +96,8 @@ def _default_config() -> Dict[str, Any]:
         "indexSamples": False,
         # remux every fragment to fragmented MP4 on the transmux device (docs/REMUX.md; implies the
         # index): FRAG_PARSING_DATA carries the moof in "data1", the mdat device view in "data2",
-        # "startDTS" / "endDTS" and the sample count in "nb"
+        # "startDTS" / "endDTS" and the sample count in "nb"; FRAG_PARSING_INIT_SEGMENT carries each
+        # track's init segment, codec and container (docs/INITSEGMENT.md)
         "remuxFmp4": False,
     }
 

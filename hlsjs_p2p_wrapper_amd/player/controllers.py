@@ -467,6 +467,7 @@ class StreamController:
         self._retry_until = 0.0
         self._eos = False
         self._init_levels: set = set()
+        self._init_announced: Any = None  # remuxFmp4: the (sps, pps, AudioSpecificConfig) last announced
         self._starts_cache: Tuple[int, int, List[float]] = (0, 0, [])
         self.fragments_buffered = 0
         self.bytes_buffered = 0
@@ -805,11 +806,27 @@ class StreamController:
             self.loop.set_timeout(self._kick, delay)
             return
         info = r["info"]
-        if frag.level not in self._init_levels:
+        # remuxFmp4: the fragment as fMP4 (ops/remux.py), with the codec configuration its init
+        # segments are built from (ops/codecconfig.py, docs/INITSEGMENT.md)
+        fmp4 = r.get("fmp4") if hls.config.get("remuxFmp4") else None
+        announce = frag.level not in self._init_levels
+        sig = None
+        if fmp4 is not None:
+            cfg = fmp4["config"]
+            sig = (cfg["sps"], cfg["pps"], cfg["aac_object_type"], cfg["aac_rate_index"], cfg["aac_channel_config"])
+            announce = announce or sig != self._init_announced
+        if announce:
             self._init_levels.add(frag.level)
-            hls.trigger(Events.FRAG_PARSING_INIT_SEGMENT, {"frag": frag, "tracks": {
-                "video": {"pid": info["video_pid"], "type": info["video_type"]},
-                "audio": {"pid": info["audio_pid"], "type": info["audio_type"]}}})
+            tracks = {"video": {"pid": info["video_pid"], "type": info["video_type"]},
+                      "audio": {"pid": info["audio_pid"], "type": info["audio_type"]}}
+            if fmp4 is not None:  # a track that has an init segment carries it, as hls.js's remuxer announces it
+                self._init_announced = sig
+                for name, meta in (("video", ("width", "height")), ("audio", ("channelCount",))):
+                    track = fmp4[name]
+                    if track["init"] is not None:
+                        tracks[name].update(container=track["container"], codec=track["codec"],
+                                            initSegment=track["init"], metadata={k: track[k] for k in meta})
+            hls.trigger(Events.FRAG_PARSING_INIT_SEGMENT, {"frag": frag, "tracks": tracks})
         # events nobody listens to are not built (no observable difference: hls.trigger with
         # no listener does nothing); this runs once per buffered fragment
         listening = hls.listening
@@ -827,7 +844,6 @@ class StreamController:
         # result without one (a fleet player's: the columnar path does not index) leaves them as is
         # remuxFmp4: the fragment as fMP4 (ops/remux.py) takes the place of the raw ES on them: data1
         # the moof, data2 the mdat on the device; its samples ride as under indexSamples
-        fmp4 = r.get("fmp4") if hls.config.get("remuxFmp4") else None
         samples = r.get("samples") if fmp4 is not None or hls.config.get("indexSamples") else None
         if listening(Events.FRAG_PARSING_DATA):
             vdata = {"frag": frag, "type": "video", "startPTS": start, "endPTS": end,

@@ -1,5 +1,7 @@
 """Movie fragment boxes for the remuxed samples (``docs/REMUX.md``): the ``moof`` that goes in
-front of an ``mdat`` box written by :func:`..ops.remux.remux_batch`.
+front of an ``mdat`` box written by :func:`..ops.remux.remux_batch`, and the init segment
+(``ftyp`` + ``moov``) of each track from the codec configuration of
+:func:`..ops.codecconfig.config_batch` (``docs/INITSEGMENT.md``).
 
 Host work on a few KB: the per-sample rows are packed big-endian with numpy in one piece, no
 Python loop per sample.  A fragment is ``moof{ mfhd, traf{ tfhd, tfdt, trun } }`` with
@@ -34,6 +36,96 @@ def _box(kind: bytes, payload: bytes) -> bytes:
 
 def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
     return _box(kind, struct.pack(">I", (version << 24) | flags) + payload)
+
+
+# ---------------------------------------------------------------- init segments (docs/INITSEGMENT.md)
+ADTS_RATES = (96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350)
+VIDEO_DISQUALIFIED = 1 | 2 | 4 | 8 | 16  # no_sps, no_pps, ps_overflow, bad_sps, unsupported_video
+AUDIO_DISQUALIFIED = 32                  # no_audio_config
+VIDEO_TREX_FLAGS = 0x01010000            # a non-sync sample; every trun row carries its own flags
+_MATRIX = struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
+
+
+def video_codec(cfg) -> str:
+    """The RFC 6381 codec string of the video track of a codec configuration (``ops.codecconfig``)."""
+    return "avc1.%02x%02x%02x" % (cfg["profile_idc"], cfg["profile_compat"], cfg["level_idc"])
+
+
+def audio_codec(cfg) -> str:
+    """``mp4a.40.<object type>``: what the ADTS header says, no HE-AAC guess."""
+    return "mp4a.40.%d" % cfg["aac_object_type"]
+
+
+def audio_sample_rate(cfg) -> int:
+    idx = cfg["aac_rate_index"]
+    return ADTS_RATES[idx] if 0 <= idx < len(ADTS_RATES) else 0
+
+
+def audio_channels(cfg) -> int:
+    """Channels of an ADTS channel configuration (7 is 7.1)."""
+    c = cfg["aac_channel_config"]
+    return 8 if c == 7 else c
+
+
+def _init(track: int, timescale: int, handler: bytes, name: bytes, volume: int, width: int, height: int,
+          media_header: bytes, entry: bytes, trex: bytes) -> bytes:
+    """``ftyp`` + ``moov`` of one track with empty sample tables and duration 0."""
+    ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 1) + b"isom" + b"avc1")
+    mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIIIIH10x", 0, 0, timescale, 0, 0x00010000, 0x0100) + _MATRIX +
+                 bytes(24) + struct.pack(">I", 0xFFFFFFFF))
+    tkhd = _full(b"tkhd", 0, 7, struct.pack(">III4xI8xHHH2x", 0, 0, track, 0, 0, 0, volume) + _MATRIX +
+                 struct.pack(">II", width, height))
+    mdhd = _full(b"mdhd", 0, 0, struct.pack(">IIIIHH", 0, 0, timescale, 0, 0x55C4, 0))
+    hdlr = _full(b"hdlr", 0, 0, struct.pack(">I4s12x", 0, handler) + name + b"\x00")
+    dinf = _box(b"dinf", _full(b"dref", 0, 0, struct.pack(">I", 1) + _full(b"url ", 0, 1, b"")))
+    stbl = _box(b"stbl", _full(b"stsd", 0, 0, struct.pack(">I", 1) + entry) + _full(b"stts", 0, 0, bytes(4)) +
+                _full(b"stsc", 0, 0, bytes(4)) + _full(b"stsz", 0, 0, bytes(8)) + _full(b"stco", 0, 0, bytes(4)))
+    mdia = _box(b"mdia", mdhd + hdlr + _box(b"minf", media_header + dinf + stbl))
+    mvex = _box(b"mvex", _full(b"trex", 0, 0, trex))
+    return ftyp + _box(b"moov", mvhd + _box(b"trak", tkhd + mdia) + mvex)
+
+
+def video_init(cfg):
+    """The video track's init segment from a codec configuration (``CodecConfig.segment(i)`` or the
+    pipeline's ``config`` mapping): ``ftyp`` + ``moov`` with one ``avc1{ avcC, pasp }`` entry, track 1 at
+    90 kHz.  ``None`` when the configuration cannot describe the track (no SPS or PPS, an overflowed
+    or unparsable SPS, a codec other than H.264)."""
+    if cfg["status"] & VIDEO_DISQUALIFIED:
+        return None
+    sps, pps = bytes(cfg["sps"]), bytes(cfg["pps"])
+    width, height, sar_w, sar_h = cfg["width"], cfg["height"], cfg["sar_width"], cfg["sar_height"]
+    avcc = _box(b"avcC", bytes([1, cfg["profile_idc"], cfg["profile_compat"], cfg["level_idc"], 0xFF, 0xE1]) +
+                struct.pack(">H", len(sps)) + sps + b"\x01" + struct.pack(">H", len(pps)) + pps)
+    pasp = _box(b"pasp", struct.pack(">II", sar_w, sar_h))
+    avc1 = _box(b"avc1", struct.pack(">6xH16xHHII4xH32xHh", 1, width, height, 0x00480000, 0x00480000, 1, 0x0018, -1)
+                + avcc + pasp)
+    shown = min((width * sar_w << 16) // sar_h, 0xFFFFFFFF)
+    vmhd = _full(b"vmhd", 0, 1, bytes(8))
+    trex = struct.pack(">IIIII", VIDEO_TRACK, 1, 0, 0, VIDEO_TREX_FLAGS)
+    return _init(VIDEO_TRACK, VIDEO_TIMESCALE, b"vide", b"VideoHandler", 0, shown, height << 16, vmhd, avc1, trex)
+
+
+def audio_specific_config(cfg) -> bytes:
+    """The two-byte AudioSpecificConfig of the ADTS header fields."""
+    return struct.pack(">H", (cfg["aac_object_type"] << 11) | (cfg["aac_rate_index"] << 7) |
+                       (cfg["aac_channel_config"] << 3))
+
+
+def audio_init(cfg):
+    """The audio track's init segment: ``ftyp`` + ``moov`` with one ``mp4a{ esds }`` entry, track 2 in
+    units of the sample rate.  ``None`` without a usable ADTS header."""
+    if cfg["status"] & AUDIO_DISQUALIFIED:
+        return None
+    rate, channels = audio_sample_rate(cfg), audio_channels(cfg)
+    asc = audio_specific_config(cfg)
+    dec_specific = b"\x05" + bytes([len(asc)]) + asc
+    dec_config = b"\x04" + bytes([13 + len(dec_specific)]) + struct.pack(">BB3xII", 0x40, 0x15, 0, 0) + dec_specific
+    es_body = struct.pack(">HB", 1, 0) + dec_config + b"\x06\x01\x02"  # ES_ID 1, no flags, ..., the SL config
+    esds = _full(b"esds", 0, 0, b"\x03" + bytes([len(es_body)]) + es_body)
+    mp4a = _box(b"mp4a", struct.pack(">6xH8xHHHHI", 1, channels, 16, 0, 0, (rate << 16) if rate < 65536 else 0) + esds)
+    smhd = _full(b"smhd", 0, 0, bytes(4))
+    trex = struct.pack(">IIIII", AUDIO_TRACK, 1, AAC_FRAME_SAMPLES, 0, AUDIO_SAMPLE_FLAGS)
+    return _init(AUDIO_TRACK, rate, b"soun", b"SoundHandler", 0x0100, 0, 0, smhd, mp4a, trex)
 
 
 def _moof(sequence_number: int, tfhd: bytes, base: int, trun_flags: int, version: int, rows: np.ndarray) -> bytes:

@@ -373,6 +373,12 @@ class MediaPipeline:
                                              torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
                                              out_offs)
                 g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
+                # ... and what the init segments are built from: one ``config_batch`` call behind the
+                # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
+                from ..ops import codecconfig as _cfg
+
+                g.cfg = cfg = _cfg.config_batch(g.res, ix, c.nb[g.rows])
+                g.cinfo, g.ps = _to_host(cfg.cinfo), _to_host(cfg.ps)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
@@ -615,15 +621,41 @@ class Fmp4Track(_View):
     """Read-only mapping of one remuxed track of a fragment: ``mdat`` (a device view of the whole
     box, header included), ``samples`` (the filled device rows of the track's sample table),
     ``nb`` (samples), ``base`` / ``duration`` / ``timescale`` (the fragment's decode time and
-    length in the track's units) and ``moof(sequence_number)`` (host bytes, built on first call)."""
+    length in the track's units) and ``moof(sequence_number)`` (host bytes, built on first call);
+    from the fragment's codec configuration ``init`` (the track's init segment as host bytes, built
+    on first access, ``None`` when the configuration cannot describe the track), ``codec`` (the RFC
+    6381 string, ``None`` like ``init``), ``container`` and ``width`` / ``height`` (video) or
+    ``channelCount`` / ``samplerate`` (audio)."""
 
-    __slots__ = ("_f", "_video", "_moofs")
-    _KEYS = ("mdat", "samples", "nb", "base", "duration", "timescale", "moof")
+    __slots__ = ("_f", "_video", "_moofs", "_init")
+    _KEYS = ("mdat", "samples", "nb", "base", "duration", "timescale", "moof", "init", "codec", "container")
+    _UNBUILT = object()
 
     def __init__(self, f: "Fmp4", video: bool) -> None:
         self._f = f
         self._video = video
         self._moofs: Dict[int, bytes] = {}
+        self._init: Any = self._UNBUILT
+
+    def _config_key(self, name: str):
+        from . import fmp4 as _fmp4
+
+        cfg = self._f["config"]
+        if name == "init":
+            if self._init is self._UNBUILT:
+                self._init = _fmp4.video_init(cfg) if self._video else _fmp4.audio_init(cfg)
+            return self._init
+        if name == "container":
+            return "video/mp4" if self._video else "audio/mp4"
+        if name == "codec":
+            if cfg["status"] & (_fmp4.VIDEO_DISQUALIFIED if self._video else _fmp4.AUDIO_DISQUALIFIED):
+                return None
+            return _fmp4.video_codec(cfg) if self._video else _fmp4.audio_codec(cfg)
+        if name == "channelCount":
+            return _fmp4.audio_channels(cfg)
+        if name == "samplerate":
+            return _fmp4.audio_sample_rate(cfg)
+        return cfg[name]  # width / height
 
     def _host_rows(self) -> np.ndarray:
         f = self._f
@@ -671,10 +703,13 @@ class Fmp4Track(_View):
             return _fmp4.AAC_FRAME_SAMPLES * self["nb"]
         if name == "moof":
             return self.moof
+        if name in ("init", "codec", "container") or name in (("width", "height") if self._video
+                                                              else ("channelCount", "samplerate")):
+            return self._config_key(name)
         raise KeyError(name)
 
     def keys(self):
-        return list(self._KEYS)
+        return list(self._KEYS) + (["width", "height"] if self._video else ["channelCount", "samplerate"])
 
     def __repr__(self) -> str:
         return f"Fmp4Track({'video' if self._video else 'audio'}, nb={self['nb']})"
@@ -682,9 +717,11 @@ class Fmp4Track(_View):
 
 class Fmp4(_View):
     """Read-only mapping of one fragment's remux (``TransmuxJob.remux``): ``video`` and ``audio``
-    (:class:`Fmp4Track`) and the ``rinfo`` fields by name (:data:`ops.remux.RINFO`)."""
+    (:class:`Fmp4Track`), the ``rinfo`` fields by name (:data:`ops.remux.RINFO`) and ``config``: the
+    fragment's codec configuration, a read-only mapping of the ``cinfo`` fields by name
+    (:data:`ops.codecconfig.CINFO`) plus ``sps`` / ``pps`` as bytes."""
 
-    __slots__ = ("_g", "_k", "_rate", "_tracks")
+    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config")
 
     def __init__(self, group, k: int, sinfo_row) -> None:
         from ..ops.esindex import SINFO
@@ -693,6 +730,7 @@ class Fmp4(_View):
         self._k = k
         self._rate = sinfo_row[SINFO["audio_sample_rate"]]
         self._tracks: Dict[str, Fmp4Track] = {}
+        self._config: Any = None
 
     def _rinfo(self, name: str) -> int:
         from ..ops.remux import RINFO
@@ -709,15 +747,24 @@ class Fmp4(_View):
             return t
         if name in RINFO:
             return self._rinfo(name)
+        if name == "config":
+            if self._config is None:
+                from types import MappingProxyType
+
+                from ..ops.codecconfig import segment_view
+
+                g, k = self._g, self._k
+                self._config = MappingProxyType(segment_view(_np(g.cinfo)[k], _np(g.ps)[k]))
+            return self._config
         raise KeyError(name)
 
     def keys(self):
         from ..ops.remux import RINFO
 
-        return ["video", "audio", *RINFO]
+        return ["video", "audio", *RINFO, "config"]
 
     def __repr__(self) -> str:
-        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio')} })"
+        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config')} })"
 
 
 @dataclass(eq=False)
@@ -733,6 +780,9 @@ class _Group:
     rinfo: Any = None  # ... its three tables on the host
     vsamples: Any = None
     asamples: Any = None
+    cfg: Any = None  # CodecConfig, behind the remux, with ...
+    cinfo: Any = None  # ... its two tensors on the host
+    ps: Any = None
 
 
 @dataclass(eq=False)

@@ -1,6 +1,7 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
-index over the demuxed ES, the remux to fMP4 samples and the MFMA CRC with HIP events and reports us / GB/s of input.
+index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
+and the MFMA CRC with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
@@ -12,7 +13,7 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import aes, crc, esindex, remux, segment, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, remux, segment, tsdemux
 
 
 def timed(fn, iters):
@@ -78,6 +79,12 @@ def main():
     a0 = int(hr.rinfo[0, remux.RINFO["audio_box_offset"]])
     for lo, hi in ((0, vend), (a0, used)):  # both boxes; the bytes between and behind them belong to nobody
         assert torch.equal(boxes[int(oo[0]) + lo:int(oo[0]) + hi].cpu(), hr.out[lo:hi]), "remux mismatch"
+    # the codec configuration of the indexed ES for the init segments (one workgroup per segment)
+    cfg = codecconfig.config_batch(r, ix, caps)
+    res["codecconfig_us"] = timed(lambda: codecconfig.config_batch(r, ix, caps), args.iters)
+    hc = codecconfig.config_batch(cpu, hx, [len(ref)])
+    assert all(torch.equal(getattr(cfg, k)[0].cpu(), getattr(hc, k)[0]) for k in ("cinfo", "ps")), \
+        "codecconfig mismatch"
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
@@ -86,7 +93,7 @@ def main():
     res["copy_us"] = timed(lambda: segment.copy_segments(src, cp, offs, offs, lens), args.iters)
     assert torch.equal(cp[offs[5]:offs[5] + lens[5]], src[offs[5]:offs[5] + lens[5]]), "copy mismatch"
     res["torch_copy_us"] = timed(lambda: cp.copy_(src), args.iters)
-    for k in ("aes", "demux", "esindex", "remux", "crc", "copy", "torch_copy"):
+    for k in ("aes", "demux", "esindex", "remux", "codecconfig", "crc", "copy", "torch_copy"):
         res[f"{k}_GBps"] = round(total / (res[f"{k}_us"] * 1e-6) / 1e9, 1)
         res[f"{k}_us"] = round(res[f"{k}_us"], 1)
     res["bytes"] = total
