@@ -1,13 +1,14 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
-``codecconfig``): import the submodule you need.  The entry points of the sample index, of the
-remux and of the codec configuration are also reachable from the package (``ops.index_batch``,
-``ops.EsIndex``, ``ops.remux_batch``, ``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``),
-resolved on first use."""
+``codecconfig``, ``hevcconfig``): import the submodule you need.  The entry points of the sample
+index, of the remux and of the two codec configurations are also reachable from the package
+(``ops.index_batch``, ``ops.EsIndex``, ``ops.remux_batch``, ``ops.Remuxed``, ``ops.config_batch``,
+``ops.CodecConfig``, ``ops.hevc_config_batch``, ``ops.HevcConfig``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
 _CODECCONFIG = ("config_batch", "CodecConfig")
-__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG)
+_HEVCCONFIG = ("hevc_config_batch", "HevcConfig")
+__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG)
 
 
 def __getattr__(name):
@@ -23,4 +24,8 @@ def __getattr__(name):
         from . import codecconfig
 
         return getattr(codecconfig, name)
+    if name in _HEVCCONFIG:
+        from . import hevcconfig
+
+        return getattr(hevcconfig, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -196,6 +196,29 @@ void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes,
   hip_ok(D::launch_codec_config(a), "codec_config launch");
 }
 
+// HEVC configuration of a demuxed and indexed batch (hevc_config.hip): the inputs of codec_config,
+// and per segment an hinfo row and three rows of max_ps bytes.
+void hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
+                 Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_ps, Tensor hinfo, Tensor hps) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_nal > 0, "hevc_config: max_pes / max_nal out of range");
+  TORCH_CHECK(es_::max_ps_ok(max_ps), "hevc_config: max_ps must be a positive multiple of 16 up to 1024");
+  const D::HevcConfigArgs a{
+      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .max_ps = max_ps,
+      .hps = check<uint8_t>(hps, "hps", es_::hps_bytes(B, max_ps)),
+      .hinfo = check<int32_t>(hinfo, "hinfo", B * es_::kHinfoWords)};
+  TORCH_CHECK(es.device() == hps.device() && es.device() == hinfo.device() && es.device() == nal.device() &&
+                  es.device() == es_off.device() && es.device() == cap.device() && es.device() == info.device() &&
+                  es.device() == pes.device() && es.device() == sinfo.device(),
+              "tensors on different devices");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(hps.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(nal.data_ptr()) & 15) == 0,
+              "es / hps / nal must be 16-byte aligned");
+  hip_ok(D::launch_hevc_config(a), "hevc_config launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -327,6 +350,8 @@ TORCH_LIBRARY(hlsp2p, m) {
         "Tensor out_off) -> ()");
   m.def("codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
+  m.def("hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
+        "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) hinfo, Tensor(b!) hps) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -338,6 +363,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("es_index", &es_index);
   m.impl("remux", &remux);
   m.impl("codec_config", &codec_config);
+  m.impl("hevc_config", &hevc_config);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -372,6 +398,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     return es_::remux_scratch(nseg, max_nal, max_aframes).end;
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
   m.def("codec_config", &codec_config);
+  m.def("hevc_config", &hevc_config);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

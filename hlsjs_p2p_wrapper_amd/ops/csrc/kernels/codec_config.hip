@@ -20,20 +20,19 @@
 //   d. parse      — lane 0 runs es::sps_parse on the RBSP while lane 0 of wave 1 takes the ADTS
 //                   fields.
 //   e. row write  — a lane per cinfo word.
+// Steps a, b and c are ps_dev.h, shared with hevc_config.hip.
 // No workgroup waits for another one.  The emulation-prevention predicate, sps_parse and the
 // ADTS fields are shared/grammar.hpp (namespace es), the same functions runtime/codec.cpp calls.
 #include "common.h"
 #include "grammar.hpp"
 #include "launch.h"
+#include "ps_dev.h"
 
 namespace hlsp2p {
 namespace dev {
 
-constexpr int kCcThreads = 256;
-constexpr int kCcWaves = kCcThreads / 64;
-constexpr int kCcNone = 0x7fffffff;
-static_assert(es::kMaxPsLimit / es::kPsAlign <= 64, "a wave copies a parameter set, a lane per 16 bytes");
-static_assert(es::kPsAlign == 16 && es::kNalWords == 4, "16-byte stores, 16-byte NAL rows");
+constexpr int kCcThreads = kPsThreads;
+constexpr int kCcNone = kPsNone;
 
 __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
     const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
@@ -41,12 +40,10 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
     int64_t max_pes, int64_t max_nal, const int32_t* __restrict__ nal_all, const int32_t* __restrict__ au_all,
     const int32_t* __restrict__ af_all, const int64_t* __restrict__ sinfo, int max_ps, uint8_t* __restrict__ ps_all,
     int32_t* __restrict__ cinfo_all) {
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
-  typedef int v4i __attribute__((ext_vector_type(4)));
   __shared__ __attribute__((aligned(16))) uint8_t s_raw[es::kMaxPsLimit];   // the SPS as stored
   __shared__ __attribute__((aligned(16))) uint8_t s_rbsp[es::kMaxPsLimit];  // ... and without emulation prevention
   __shared__ int s_found[es::kPsRows];
-  __shared__ int s_wave[kCcWaves];
+  __shared__ int s_wave[kPsWaves];
   __shared__ int32_t s_row[es::kCinfoWords];
   const int seg = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,24 +59,9 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
   __syncthreads();
 
   // ---- a. the first SPS and PPS rows
-  const v4i* rows = reinterpret_cast<const v4i*>(ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
-  for (int kb = 0; kb < R; kb += kCcThreads) {  // R is workgroup-uniform
-    const int k = kb + tid;
-    int type = -1;
-    if (k < R) {
-      const v4i row = rows[k];
-      if (row[es::kNalLength] > 0) type = row[es::kNalType];
-    }
-    const unsigned long long m7 = __ballot(type == 7), m8 = __ballot(type == 8);
-    if (lane == 0) {
-      if (m7) atomicMin(&s_found[es::kPsSps], kb + wave * 64 + __builtin_ctzll(m7));
-      if (m8) atomicMin(&s_found[es::kPsPps], kb + wave * 64 + __builtin_ctzll(m8));
-    }
-    __syncthreads();
-    const bool done = s_found[es::kPsSps] != kCcNone && s_found[es::kPsPps] != kCcNone;
-    __syncthreads();  // every wave has read the round's result before the next round may change it
-    if (done) break;
-  }
+  const ps_v4i* rows = reinterpret_cast<const ps_v4i*>(ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
+  const int types[es::kPsRows] = {7, 8};
+  ps_find_rows(rows, R, types, s_found);
   const int found[es::kPsRows] = {s_found[es::kPsSps], s_found[es::kPsPps]};
 
   // ---- b. both NAL units to ps, the SPS to LDS as well
@@ -87,63 +69,22 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
 #pragma unroll
   for (int w = 0; w < es::kPsRows; ++w) {
     if (found[w] == kCcNone) continue;
-    const v4i row = rows[found[w]];
+    const ps_v4i row = rows[found[w]];
     src[w] = static_cast<int>(clamp(row[es::kNalOffset], 0, cap_es));
     len[w] = static_cast<int>(clamp(row[es::kNalLength], 0, cap_es - src[w]));
   }
   if (wave < es::kPsRows && lane * 16 < max_ps) {
     const int64_t off = es_off[seg];
-    const int64_t avail = es_numel - off;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint8_t*>(es + off), 0, static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
-    const int stored = len[wave] < max_ps ? len[wave] : max_ps;
-    const int left = stored - lane * 16;  // bytes of this lane's 16 that are stored
-    v4u q = {0, 0, 0, 0};
-    if (left > 0) {
-      const int sa = src[wave] + lane * 16;
-      const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, sa & ~3, 0, 0);
-      const uint32_t w4 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (sa & ~3) + 16, 0, 0);
-      const uint32_t sh = static_cast<uint32_t>(sa & 3);
-      q = v4u{__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh),
-              __builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(w4, v.w, sh)};
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {  // zero behind the stored bytes
-        const int keep = left - 4 * d;
-        if (keep <= 0) q[d] = 0;
-        else if (keep < 4) q[d] &= (1u << (8 * keep)) - 1u;
-      }
-    }
+    const ps_v4u q = ps_copy_lane(es + off, es_numel - off, src[wave], len[wave], max_ps, lane);
     uint8_t* dst = ps_all + es::ps_bytes(seg, max_ps) + static_cast<int64_t>(wave) * max_ps;
-    *reinterpret_cast<v4u*>(dst + lane * 16) = q;
-    if (wave == es::kPsSps) *reinterpret_cast<v4u*>(s_raw + lane * 16) = q;
+    *reinterpret_cast<ps_v4u*>(dst + lane * 16) = q;
+    if (wave == es::kPsSps) *reinterpret_cast<ps_v4u*>(s_raw + lane * 16) = q;
   }
   __syncthreads();
 
   // ---- c. the SPS without its header byte and emulation prevention
   const bool parse = found[es::kPsSps] != kCcNone && len[es::kPsSps] <= max_ps;  // an overflowed SPS is not parsed
-  const int n = parse ? len[es::kPsSps] : 0;
-  int carry = 0;
-  for (int jb = 0; jb < n; jb += kCcThreads) {  // n is workgroup-uniform
-    const int j = jb + tid;
-    bool keep = false;
-    uint8_t b = 0;
-    if (j >= 1 && j < n) {
-      b = s_raw[j];
-      keep = j < 2 || !es::is_emulation_prevention(s_raw[j - 2], s_raw[j - 1], b);
-    }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int before = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < kCcWaves; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (keep) s_rbsp[before + __popcll(m & ((1ull << lane) - 1ull))] = b;
-    carry += total;
-    __syncthreads();  // s_wave is free again
-  }
+  const int carry = ps_unescape(s_raw, parse ? len[es::kPsSps] : 0, 1, s_rbsp, s_wave);
 
   // ---- d. one lane parses, one of another wave takes the ADTS fields
   if (tid == 0) {

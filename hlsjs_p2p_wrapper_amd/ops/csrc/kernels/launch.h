@@ -134,6 +134,14 @@ struct CodecConfigArgs {
 };
 hipError_t launch_codec_config(const CodecConfigArgs& a);
 
+struct HevcConfigArgs {
+  EsBatch b;       // as CodecConfigArgs
+  int64_t max_ps;  // es::max_ps_ok(max_ps)
+  uint8_t* hps;    // es::hps_bytes(nseg, max_ps)
+  int32_t* hinfo;  // nseg x es::kHinfoWords
+};
+hipError_t launch_hevc_config(const HevcConfigArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

@@ -21,6 +21,7 @@
 #include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
+#include "hevc.hpp"
 #include "locator.hpp"
 #include "planner.hpp"
 #include "remux.hpp"
@@ -63,7 +64,7 @@ void parallel_for(int64_t n, F&& f, int64_t work_bytes = -1) {
   for (auto& x : th) x.join();
 }
 
-// The demuxed and indexed batch index_batch, remux_batch and config_batch take: its sizes are checked here, once
+// The demuxed and indexed batch index_batch, remux_batch, config_batch and hevc_config_batch take: its sizes are checked here, once
 // (`more_ok`: the caller's own sizes, part of the same check), then each segment's ES range and,
 // right behind it, whatever `also(b)` checks of segment b.
 struct EsBatch {
@@ -523,6 +524,67 @@ PYBIND11_MODULE(_runtime, m) {
     st["unsupported_video"] = int(es::kConfigUnsupportedVideo);
     st["no_audio_config"] = int(es::kNoAudioConfig);
     m.attr("ES_CSTATUS") = st;
+  }
+
+  // Batched CPU HEVC configuration with the device kernel's layout (docs/INITSEGMENT.md): the inputs of
+  // config_batch.
+  //   hinfo: int32[B, ES_HINFO_WORDS]; hps: uint8[B, 3, max_ps]
+  m.def("hevc_config_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info,
+                                Arr<int64_t> pes, int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au,
+                                Arr<int32_t> aframes, Arr<int64_t> sinfo, int64_t max_ps, py::array hinfo,
+                                py::array hps) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0)
+      throw std::invalid_argument("hevc_config_batch: max_pes and max_nal must be positive");
+    if (!es::max_ps_ok(max_ps))
+      throw std::invalid_argument("hevc_config_batch: max_ps must be a positive multiple of 16 up to 1024");
+    int32_t* hi = mut_ptr<int32_t>(hinfo, "hinfo");
+    uint8_t* hp = mut_ptr<uint8_t>(hps, "hps");
+    const bool sized = hinfo.size() >= B * es::kHinfoWords && hps.size() >= es::hps_bytes(B, max_ps);
+    const EsBatch batch = es_batch("hevc_config_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
+    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      const es::Segment s = batch.at(b);
+      es::hevc_config_segment(s, es::index_tables_at(ix, s, b), max_ps, hp + es::hps_bytes(b, max_ps),
+                              hi + b * es::kHinfoWords);
+    }, batch.total);
+  });
+  m.attr("ES_HINFO_WORDS") = es::kHinfoWords;
+  m.attr("ES_HPS_ROWS") = es::kHpsRows;
+  {
+    py::dict d, st;
+    d["status"] = int(es::kHStatus);
+    d["vps_nal"] = int(es::kHVpsNal);
+    d["vps_bytes"] = int(es::kHVpsBytes);
+    d["sps_nal"] = int(es::kHSpsNal);
+    d["sps_bytes"] = int(es::kHSpsBytes);
+    d["sps_rbsp_bytes"] = int(es::kHSpsRbspBytes);
+    d["pps_nal"] = int(es::kHPpsNal);
+    d["pps_bytes"] = int(es::kHPpsBytes);
+    d["profile_space"] = int(es::kHProfileSpace);
+    d["tier_flag"] = int(es::kHTierFlag);
+    d["profile_idc"] = int(es::kHProfileIdc);
+    d["profile_compat"] = int(es::kHProfileCompat);
+    d["constraint_hi"] = int(es::kHConstraintHi);
+    d["constraint_lo"] = int(es::kHConstraintLo);
+    d["level_idc"] = int(es::kHLevelIdc);
+    d["num_temporal_layers"] = int(es::kHNumTemporalLayers);
+    d["temporal_id_nested"] = int(es::kHTemporalIdNested);
+    d["chroma_format_idc"] = int(es::kHChromaFormatIdc);
+    d["bit_depth_luma"] = int(es::kHBitDepthLuma);
+    d["bit_depth_chroma"] = int(es::kHBitDepthChroma);
+    d["width"] = int(es::kHWidth);
+    d["height"] = int(es::kHHeight);
+    m.attr("ES_HINFO") = d;
+    st["no_vps"] = int(es::kHNoVps);
+    st["no_sps"] = int(es::kHNoSps);
+    st["no_pps"] = int(es::kHNoPps);
+    st["ps_overflow"] = int(es::kHPsOverflow);
+    st["bad_sps"] = int(es::kHBadSps);
+    st["not_hevc"] = int(es::kHNotHevc);
+    m.attr("ES_HSTATUS") = st;
   }
 
   // ------------------------------------------------------------------ store

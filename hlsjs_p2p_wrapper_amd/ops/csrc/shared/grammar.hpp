@@ -454,6 +454,83 @@ HLSP2P_RULE bool sps_parse(RB rb, int64_t n, SpsFields& f) {
   return true;
 }
 
+// What hevc_sps_parse reads, in the order of the hinfo row (Hinfo kHProfileSpace .. kHHeight).
+// profile_compat holds the 32 general_profile_compatibility_flags as a bit pattern (flag 0 is bit
+// 31), constraint_hi / constraint_lo the upper 16 and lower 32 of the 48 constraint-indicator bits.
+struct HevcSpsFields {
+  int32_t profile_space, tier_flag, profile_idc, profile_compat, constraint_hi, constraint_lo, level_idc;
+  int32_t num_temporal_layers, temporal_id_nested, chroma_format_idc, bit_depth_luma, bit_depth_chroma, width, height;
+};
+constexpr int kHevcSpsFieldWords = 14;
+static_assert(sizeof(HevcSpsFields) == kHevcSpsFieldWords * sizeof(int32_t) &&
+                  kHHeight - kHProfileSpace + 1 == kHevcSpsFieldWords,
+              "HevcSpsFields is the hinfo row's kHProfileSpace .. kHHeight");
+
+// An HEVC sequence parameter set from its RBSP (the NAL without its two header bytes and emulation
+// prevention) up to the bit depths: rb(i) is RBSP byte i < n.  false: an error
+// (docs/INITSEGMENT.md lists them); every field of f is then 0.  Every loop is bounded by a
+// constant of the syntax, so any bytes terminate.
+template <class RB>
+HLSP2P_RULE bool hevc_sps_parse(RB rb, int64_t n, HevcSpsFields& f) {
+  f = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  SpsBits<RB> r = {rb, 8 * n, 0, false};
+  r.u(4);  // sps_video_parameter_set_id
+  const uint32_t L = r.u(3);  // sps_max_sub_layers_minus1
+  const uint32_t nested = r.u(1);
+  if (r.err || L == 7) return false;
+  // profile_tier_level(1, L)
+  const uint32_t space = r.u(2), tier = r.u(1), profile = r.u(5);
+  const uint32_t compat = r.u(32), constraint_hi = r.u(16), constraint_lo = r.u(32), level = r.u(8);
+  uint32_t has_profile = 0, has_level = 0;  // bit i: sub-layer i
+  for (uint32_t i = 0; i < L; ++i) {
+    has_profile |= r.u(1) << i;
+    has_level |= r.u(1) << i;
+  }
+  if (L > 0)
+    for (uint32_t i = L; i < 8; ++i) r.u(2);  // reserved_zero_2bits
+  for (uint32_t i = 0; i < L; ++i) {
+    if ((has_profile >> i) & 1) {  // 88 bits of a sub-layer's profile
+      r.u(32);
+      r.u(32);
+      r.u(24);
+    }
+    if ((has_level >> i) & 1) r.u(8);
+  }
+  const uint32_t sps_id = r.ue();
+  if (r.err || sps_id > 15) return false;
+  const uint32_t chroma = r.ue();
+  if (r.err || chroma > 3) return false;
+  if (chroma == 3) r.u(1);  // separate_colour_plane
+  const int64_t W = r.ue(), H = r.ue();
+  int64_t left = 0, right = 0, top = 0, bottom = 0;
+  if (r.u(1)) {  // conformance_window
+    left = r.ue();
+    right = r.ue();
+    top = r.ue();
+    bottom = r.ue();
+  }
+  const uint32_t depth_luma = r.ue(), depth_chroma = r.ue();
+  if (r.err || depth_luma > 8 || depth_chroma > 8) return false;
+  const int64_t cx = chroma == 1 || chroma == 2 ? 2 : 1, cy = chroma == 1 ? 2 : 1;
+  const int64_t width = W - cx * (left + right), height = H - cy * (top + bottom);
+  if (width < 1 || width > 65535 || height < 1 || height > 65535) return false;
+  f.profile_space = static_cast<int32_t>(space);
+  f.tier_flag = static_cast<int32_t>(tier);
+  f.profile_idc = static_cast<int32_t>(profile);
+  f.profile_compat = static_cast<int32_t>(compat);
+  f.constraint_hi = static_cast<int32_t>(constraint_hi);
+  f.constraint_lo = static_cast<int32_t>(constraint_lo);
+  f.level_idc = static_cast<int32_t>(level);
+  f.num_temporal_layers = static_cast<int32_t>(L + 1);
+  f.temporal_id_nested = static_cast<int32_t>(nested);
+  f.chroma_format_idc = static_cast<int32_t>(chroma);
+  f.bit_depth_luma = static_cast<int32_t>(8 + depth_luma);
+  f.bit_depth_chroma = static_cast<int32_t>(8 + depth_chroma);
+  f.width = static_cast<int32_t>(width);
+  f.height = static_cast<int32_t>(height);
+  return true;
+}
+
 // x - y as a sample duration (unsigned == true: 0 .. 2^31 - 1) or composition offset (the int32
 // range), exact for any int64 pair; fits == false: the caller stores 0 and flags bad_timestamps
 struct Delta32 { int32_t v; bool fits; };

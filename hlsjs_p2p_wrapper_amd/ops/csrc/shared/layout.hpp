@@ -164,6 +164,30 @@ enum Cinfo : int {
 enum ConfigStatus : int32_t {
   kNoSps = 1, kNoPps = 2, kPsOverflow = 4, kBadSps = 8, kConfigUnsupportedVideo = 16, kNoAudioConfig = 32,
 };
+
+// ---- HEVC configuration for the hvc1 init segment (docs/INITSEGMENT.md); max_ps as above
+constexpr int kHinfoWords = 22;
+constexpr int kHpsRows = 3;  // hps [segment][kHpsRows][max_ps] (uint8): the VPS, the SPS, the PPS
+enum HpsRow : int { kHpsVps = 0, kHpsSps = 1, kHpsPps = 2 };
+constexpr int kHevcVps = 32, kHevcSps = 33, kHevcPps = 34;  // nal_unit_type
+constexpr int kHevcNalHeader = 2;                           // header bytes in front of the RBSP
+constexpr int64_t hps_bytes(int64_t nseg, int64_t max_ps) { return nseg * kHpsRows * max_ps; }
+
+// hinfo[] row (int32), identical on host and device; kHProfileSpace .. kHHeight are HevcSpsFields in order
+enum Hinfo : int {
+  kHStatus = 0,
+  kHVpsNal = 1,  // row of the nal table, -1: none
+  kHVpsBytes = 2,
+  kHSpsNal = 3, kHSpsBytes = 4, kHSpsRbspBytes = 5,
+  kHPpsNal = 6, kHPpsBytes = 7,
+  kHProfileSpace = 8, kHTierFlag = 9, kHProfileIdc = 10, kHProfileCompat = 11,
+  kHConstraintHi = 12, kHConstraintLo = 13, kHLevelIdc = 14,
+  kHNumTemporalLayers = 15, kHTemporalIdNested = 16,
+  kHChromaFormatIdc = 17, kHBitDepthLuma = 18, kHBitDepthChroma = 19, kHWidth = 20, kHHeight = 21,
+};
+enum HevcStatus : int32_t {
+  kHNoVps = 1, kHNoSps = 2, kHNoPps = 4, kHPsOverflow = 8, kHBadSps = 16, kHNotHevc = 32,
+};
 }  // namespace es
 
 // ---------------------------------------------------------------- CRC-32

@@ -807,13 +807,16 @@ class StreamController:
             return
         info = r["info"]
         # remuxFmp4: the fragment as fMP4 (ops/remux.py), with the codec configuration its init
-        # segments are built from (ops/codecconfig.py, docs/INITSEGMENT.md)
+        # segments are built from (ops/codecconfig.py, ops/hevcconfig.py for HEVC, docs/INITSEGMENT.md)
         fmp4 = r.get("fmp4") if hls.config.get("remuxFmp4") else None
         announce = frag.level not in self._init_levels
         sig = None
         if fmp4 is not None:
             cfg = fmp4["config"]
             sig = (cfg["sps"], cfg["pps"], cfg["aac_object_type"], cfg["aac_rate_index"], cfg["aac_channel_config"])
+            if cfg["status"] & 16:  # unsupported_video: an HEVC fragment's parameter sets are in ``hevc``
+                hevc = fmp4["hevc"]
+                sig = (hevc["vps"], hevc["sps"], hevc["pps"]) + sig[2:]
             announce = announce or sig != self._init_announced
         if announce:
             self._init_levels.add(frag.level)

@@ -1,7 +1,8 @@
 """Movie fragment boxes for the remuxed samples (``docs/REMUX.md``): the ``moof`` that goes in
 front of an ``mdat`` box written by :func:`..ops.remux.remux_batch`, and the init segment
 (``ftyp`` + ``moov``) of each track from the codec configuration of
-:func:`..ops.codecconfig.config_batch` (``docs/INITSEGMENT.md``).
+:func:`..ops.codecconfig.config_batch` (``docs/INITSEGMENT.md``), or for an HEVC track from
+the configuration of :func:`..ops.hevcconfig.hevc_config_batch`.
 
 Host work on a few KB: the per-sample rows are packed big-endian with numpy in one piece, no
 Python loop per sample.  A fragment is ``moof{ mfhd, traf{ tfhd, tfdt, trun } }`` with
@@ -42,6 +43,7 @@ def _full(kind: bytes, version: int, flags: int, payload: bytes) -> bytes:
 ADTS_RATES = (96000, 88200, 64000, 48000, 44100, 32000, 24000, 22050, 16000, 12000, 11025, 8000, 7350)
 VIDEO_DISQUALIFIED = 1 | 2 | 4 | 8 | 16  # no_sps, no_pps, ps_overflow, bad_sps, unsupported_video
 AUDIO_DISQUALIFIED = 32                  # no_audio_config
+HEVC_DISQUALIFIED = 1 | 2 | 4 | 8 | 16 | 32  # hinfo: no_vps, no_sps, no_pps, ps_overflow, bad_sps, not_hevc
 VIDEO_TREX_FLAGS = 0x01010000            # a non-sync sample; every trun row carries its own flags
 _MATRIX = struct.pack(">9I", 0x10000, 0, 0, 0, 0x10000, 0, 0, 0, 0x40000000)
 
@@ -68,9 +70,9 @@ def audio_channels(cfg) -> int:
 
 
 def _init(track: int, timescale: int, handler: bytes, name: bytes, volume: int, width: int, height: int,
-          media_header: bytes, entry: bytes, trex: bytes) -> bytes:
+          media_header: bytes, entry: bytes, trex: bytes, brand: bytes = b"avc1") -> bytes:
     """``ftyp`` + ``moov`` of one track with empty sample tables and duration 0."""
-    ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 1) + b"isom" + b"avc1")
+    ftyp = _box(b"ftyp", b"isom" + struct.pack(">I", 1) + b"isom" + brand)
     mvhd = _full(b"mvhd", 0, 0, struct.pack(">IIIIIH10x", 0, 0, timescale, 0, 0x00010000, 0x0100) + _MATRIX +
                  bytes(24) + struct.pack(">I", 0xFFFFFFFF))
     tkhd = _full(b"tkhd", 0, 7, struct.pack(">III4xI8xHHH2x", 0, 0, track, 0, 0, 0, volume) + _MATRIX +
@@ -103,6 +105,55 @@ def video_init(cfg):
     vmhd = _full(b"vmhd", 0, 1, bytes(8))
     trex = struct.pack(">IIIII", VIDEO_TRACK, 1, 0, 0, VIDEO_TREX_FLAGS)
     return _init(VIDEO_TRACK, VIDEO_TIMESCALE, b"vide", b"VideoHandler", 0, shown, height << 16, vmhd, avc1, trex)
+
+
+def _hevc_constraint_bytes(hcfg) -> bytes:
+    """The 48 general constraint-indicator bits of an HEVC configuration as six bytes."""
+    return struct.pack(">HI", hcfg["constraint_hi"] & 0xFFFF, hcfg["constraint_lo"] & 0xFFFFFFFF)
+
+
+def _hevc_describable(hcfg) -> bool:
+    """An ``hvcC`` record can describe the configuration: no disqualifying bit, and bit depths its
+    three-bit fields hold (up to 15; the SPS syntax goes up to 16)."""
+    return not hcfg["status"] & HEVC_DISQUALIFIED and max(hcfg["bit_depth_luma"], hcfg["bit_depth_chroma"]) <= 15
+
+
+def hevc_codec(hcfg):
+    """The RFC 6381 codec string of an HEVC configuration (``ops.hevcconfig``) by ISO/IEC 14496-15
+    Annex E: ``hvc1.<space><profile>.<compatibility flags, reversed, hex>.<tier><level>`` and one
+    ``.XX`` per constraint byte up to the last non-zero one.  ``None`` like :func:`hevc_init`."""
+    if not _hevc_describable(hcfg):
+        return None
+    compat = hcfg["profile_compat"] & 0xFFFFFFFF
+    reversed_compat = int(format(compat, "032b")[::-1], 2)
+    out = "hvc1.%s%d.%X.%s%d" % (("", "A", "B", "C")[hcfg["profile_space"]], hcfg["profile_idc"], reversed_compat,
+                                 "H" if hcfg["tier_flag"] else "L", hcfg["level_idc"])
+    return out + "".join(".%X" % b for b in _hevc_constraint_bytes(hcfg).rstrip(b"\x00"))
+
+
+def hevc_init(hcfg):
+    """The video track's init segment from an HEVC configuration (``HevcConfig.segment(i)`` or the
+    pipeline's ``hevc`` mapping): ``ftyp`` (brands ``isom``, ``hvc1``) + ``moov`` with one
+    ``hvc1{ hvcC }`` entry, track 1 at 90 kHz, no ``pasp``.  ``None`` when the configuration cannot
+    describe the track (no VPS, SPS or PPS, an overflowed or unparsable SPS, a codec other than HEVC,
+    a bit depth of 16)."""
+    if not _hevc_describable(hcfg):
+        return None
+    width, height = hcfg["width"], hcfg["height"]
+    record = bytes([1, (hcfg["profile_space"] << 6) | (hcfg["tier_flag"] << 5) | hcfg["profile_idc"]]) + \
+        struct.pack(">I", hcfg["profile_compat"] & 0xFFFFFFFF) + _hevc_constraint_bytes(hcfg) + \
+        bytes([hcfg["level_idc"], 0xF0, 0x00, 0xFC, 0xFC | hcfg["chroma_format_idc"],
+               0xF8 | (hcfg["bit_depth_luma"] - 8), 0xF8 | (hcfg["bit_depth_chroma"] - 8), 0, 0,
+               (hcfg["num_temporal_layers"] << 3) | (hcfg["temporal_id_nested"] << 2) | 3, 3])
+    for nal_type, name in ((32, "vps"), (33, "sps"), (34, "pps")):  # one array per type, one NAL each, complete
+        nal = bytes(hcfg[name])
+        record += bytes([0x80 | nal_type]) + struct.pack(">HH", 1, len(nal)) + nal
+    hvc1 = _box(b"hvc1", struct.pack(">6xH16xHHII4xH32xHh", 1, width, height, 0x00480000, 0x00480000, 1, 0x0018, -1)
+                + _box(b"hvcC", record))
+    vmhd = _full(b"vmhd", 0, 1, bytes(8))
+    trex = struct.pack(">IIIII", VIDEO_TRACK, 1, 0, 0, VIDEO_TREX_FLAGS)
+    return _init(VIDEO_TRACK, VIDEO_TIMESCALE, b"vide", b"VideoHandler", 0, width << 16, height << 16, vmhd, hvc1,
+                 trex, brand=b"hvc1")
 
 
 def audio_specific_config(cfg) -> bytes:

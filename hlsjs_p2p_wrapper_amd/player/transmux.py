@@ -379,6 +379,13 @@ class MediaPipeline:
 
                 g.cfg = cfg = _cfg.config_batch(g.res, ix, c.nb[g.rows])
                 g.cinfo, g.ps = _to_host(cfg.cinfo), _to_host(cfg.ps)
+                # ... and one ``hevc_config_batch`` call behind it for the HEVC segments among them:
+                # the codec is only known on the device, so the launch is unconditional and the
+                # workgroup of any other segment exits at once
+                from ..ops import hevcconfig as _hcfg
+
+                g.hcfg = hcfg = _hcfg.hevc_config_batch(g.res, ix, c.nb[g.rows])
+                g.hvinfo, g.hps = _to_host(hcfg.hinfo), _to_host(hcfg.hps)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
@@ -496,6 +503,7 @@ def _mask(n: int, idx) -> Optional[np.ndarray]:
     return m
 
 
+_UNSUPPORTED_VIDEO = 16  # ops.codecconfig.CSTATUS["unsupported_video"]
 _VB, _AB, _IB = _ts.INFO["video_bytes"], _ts.INFO["audio_bytes"], _ts.INFO["id3_bytes"]
 _AO, _IO = _ts.INFO["audio_es_offset"], _ts.INFO["id3_es_offset"]
 
@@ -625,7 +633,8 @@ class Fmp4Track(_View):
     from the fragment's codec configuration ``init`` (the track's init segment as host bytes, built
     on first access, ``None`` when the configuration cannot describe the track), ``codec`` (the RFC
     6381 string, ``None`` like ``init``), ``container`` and ``width`` / ``height`` (video) or
-    ``channelCount`` / ``samplerate`` (audio)."""
+    ``channelCount`` / ``samplerate`` (audio).  The video track of an HEVC fragment (``config`` says
+    ``unsupported_video`` and ``hevc`` has no disqualifying bit) takes the four from ``hevc``."""
 
     __slots__ = ("_f", "_video", "_moofs", "_init")
     _KEYS = ("mdat", "samples", "nb", "base", "duration", "timescale", "moof", "init", "codec", "container")
@@ -641,12 +650,20 @@ class Fmp4Track(_View):
         from . import fmp4 as _fmp4
 
         cfg = self._f["config"]
+        if name == "container":
+            return "video/mp4" if self._video else "audio/mp4"
+        if self._video and cfg["status"] & _UNSUPPORTED_VIDEO:
+            hevc = self._f["hevc"]
+            if not hevc["status"] & _fmp4.HEVC_DISQUALIFIED:
+                if name == "init":
+                    if self._init is self._UNBUILT:
+                        self._init = _fmp4.hevc_init(hevc)
+                    return self._init
+                return _fmp4.hevc_codec(hevc) if name == "codec" else hevc[name]  # width / height
         if name == "init":
             if self._init is self._UNBUILT:
                 self._init = _fmp4.video_init(cfg) if self._video else _fmp4.audio_init(cfg)
             return self._init
-        if name == "container":
-            return "video/mp4" if self._video else "audio/mp4"
         if name == "codec":
             if cfg["status"] & (_fmp4.VIDEO_DISQUALIFIED if self._video else _fmp4.AUDIO_DISQUALIFIED):
                 return None
@@ -719,9 +736,10 @@ class Fmp4(_View):
     """Read-only mapping of one fragment's remux (``TransmuxJob.remux``): ``video`` and ``audio``
     (:class:`Fmp4Track`), the ``rinfo`` fields by name (:data:`ops.remux.RINFO`) and ``config``: the
     fragment's codec configuration, a read-only mapping of the ``cinfo`` fields by name
-    (:data:`ops.codecconfig.CINFO`) plus ``sps`` / ``pps`` as bytes."""
+    (:data:`ops.codecconfig.CINFO`) plus ``sps`` / ``pps`` as bytes, and ``hevc``: the same of the
+    ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``."""
 
-    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config")
+    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc")
 
     def __init__(self, group, k: int, sinfo_row) -> None:
         from ..ops.esindex import SINFO
@@ -731,6 +749,7 @@ class Fmp4(_View):
         self._rate = sinfo_row[SINFO["audio_sample_rate"]]
         self._tracks: Dict[str, Fmp4Track] = {}
         self._config: Any = None
+        self._hevc: Any = None
 
     def _rinfo(self, name: str) -> int:
         from ..ops.remux import RINFO
@@ -756,15 +775,24 @@ class Fmp4(_View):
                 g, k = self._g, self._k
                 self._config = MappingProxyType(segment_view(_np(g.cinfo)[k], _np(g.ps)[k]))
             return self._config
+        if name == "hevc":
+            if self._hevc is None:
+                from types import MappingProxyType
+
+                from ..ops.hevcconfig import segment_view
+
+                g, k = self._g, self._k
+                self._hevc = MappingProxyType(segment_view(_np(g.hvinfo)[k], _np(g.hps)[k]))
+            return self._hevc
         raise KeyError(name)
 
     def keys(self):
         from ..ops.remux import RINFO
 
-        return ["video", "audio", *RINFO, "config"]
+        return ["video", "audio", *RINFO, "config", "hevc"]
 
     def __repr__(self) -> str:
-        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config')} })"
+        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config', 'hevc')} })"
 
 
 @dataclass(eq=False)
@@ -783,6 +811,9 @@ class _Group:
     cfg: Any = None  # CodecConfig, behind the remux, with ...
     cinfo: Any = None  # ... its two tensors on the host
     ps: Any = None
+    hcfg: Any = None  # HevcConfig, behind the codec configuration, with ...
+    hvinfo: Any = None  # ... its two tensors on the host
+    hps: Any = None
 
 
 @dataclass(eq=False)

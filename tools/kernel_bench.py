@@ -1,7 +1,7 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
 index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
-and the MFMA CRC with HIP events and reports us / GB/s of input.
+(H.264 and HEVC) and the MFMA CRC with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, remux, segment, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, hevcconfig, remux, segment, tsdemux
 
 
 def timed(fn, iters):
@@ -85,6 +85,25 @@ def main():
     hc = codecconfig.config_batch(cpu, hx, [len(ref)])
     assert all(torch.equal(getattr(cfg, k)[0].cpu(), getattr(hc, k)[0]) for k in ("cinfo", "ps")), \
         "codecconfig mismatch"
+    # the HEVC configuration launched behind it: on this H.264 batch every workgroup exits at once,
+    # which is what the launch adds to a remuxFmp4 group ...
+    hv = hevcconfig.hevc_config_batch(r, ix, caps)
+    res["hevcconfig_us"] = timed(lambda: hevcconfig.hevc_config_batch(r, ix, caps), args.iters)
+    hh = hevcconfig.hevc_config_batch(cpu, hx, [len(ref)])
+    assert all(torch.equal(getattr(hv, k)[0].cpu(), getattr(hh, k)[0]) for k in ("hinfo", "hps")), \
+        "hevcconfig mismatch"
+    # ... and with the same bytes declared HEVC and indexed as such: the row search runs over every
+    # recorded NAL of a segment that holds no parameter set, the longest path the kernel has
+    r24 = tsdemux.DemuxResult(r.info.clone(), r.pes, r.es, r.es_offs)
+    r24.info[:, tsdemux.INFO["video_type"]] = 0x24
+    ix24 = esindex.index_batch(r24, caps)
+    hv = hevcconfig.hevc_config_batch(r24, ix24, caps)
+    res["hevcconfig_search_us"] = timed(lambda: hevcconfig.hevc_config_batch(r24, ix24, caps), args.iters)
+    cpu24 = tsdemux.DemuxResult(cpu.info.clone(), cpu.pes, cpu.es, cpu.es_offs)
+    cpu24.info[:, tsdemux.INFO["video_type"]] = 0x24
+    hh = hevcconfig.hevc_config_batch(cpu24, esindex.index_batch(cpu24, [len(ref)]), [len(ref)])
+    assert all(torch.equal(getattr(hv, k)[0].cpu(), getattr(hh, k)[0]) for k in ("hinfo", "hps")), \
+        "hevcconfig (HEVC) mismatch"
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
@@ -93,7 +112,8 @@ def main():
     res["copy_us"] = timed(lambda: segment.copy_segments(src, cp, offs, offs, lens), args.iters)
     assert torch.equal(cp[offs[5]:offs[5] + lens[5]], src[offs[5]:offs[5] + lens[5]]), "copy mismatch"
     res["torch_copy_us"] = timed(lambda: cp.copy_(src), args.iters)
-    for k in ("aes", "demux", "esindex", "remux", "codecconfig", "crc", "copy", "torch_copy"):
+    for k in ("aes", "demux", "esindex", "remux", "codecconfig", "hevcconfig", "hevcconfig_search", "crc", "copy",
+              "torch_copy"):
         res[f"{k}_GBps"] = round(total / (res[f"{k}_us"] * 1e-6) / 1e9, 1)
         res[f"{k}_us"] = round(res[f"{k}_us"], 1)
     res["bytes"] = total
