@@ -1,14 +1,16 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
-``codecconfig``, ``hevcconfig``): import the submodule you need.  The entry points of the sample
-index, of the remux and of the two codec configurations are also reachable from the package
-(``ops.index_batch``, ``ops.EsIndex``, ``ops.remux_batch``, ``ops.Remuxed``, ``ops.config_batch``,
-``ops.CodecConfig``, ``ops.hevc_config_batch``, ``ops.HevcConfig``), resolved on first use."""
+``codecconfig``, ``hevcconfig``, ``sampleaes``): import the submodule you need.  The entry points
+of the sample index, of the remux, of the two codec configurations and of the SAMPLE-AES decrypt
+are also reachable from the package (``ops.index_batch``, ``ops.EsIndex``, ``ops.remux_batch``,
+``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
+``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
 _CODECCONFIG = ("config_batch", "CodecConfig")
 _HEVCCONFIG = ("hevc_config_batch", "HevcConfig")
-__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG)
+_SAMPLEAES = ("sample_decrypt_batch", "SampleAes")
+__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES)
 
 
 def __getattr__(name):
@@ -28,4 +30,8 @@ def __getattr__(name):
         from . import hevcconfig
 
         return getattr(hevcconfig, name)
+    if name in _SAMPLEAES:
+        from . import sampleaes
+
+        return getattr(sampleaes, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

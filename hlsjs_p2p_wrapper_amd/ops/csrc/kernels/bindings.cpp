@@ -219,6 +219,36 @@ void hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, 
   hip_ok(D::launch_hevc_config(a), "hevc_config launch");
 }
 
+// SAMPLE-AES decryption of a demuxed and indexed batch in place (sample_aes.hip): the inputs of
+// codec_config, of which es and the length column of nal are rewritten; per segment 44 round-key
+// words (little-endian), a 16-byte IV and an enable byte; td / isb are ops.aes.device_tables.
+void sample_aes_decrypt(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
+                        Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor round_keys, Tensor iv, Tensor enable,
+                        Tensor td, Tensor isb, Tensor sainfo) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0, "sample_aes_decrypt: max_pes / max_nal out of range");
+  TORCH_CHECK(B <= 65535, "sample_aes_decrypt: at most 65535 segments per call");
+  const D::SampleAesArgs a{
+      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .es = check<uint8_t>(es, "es"),
+      .round_keys = check<uint32_t>(round_keys, "round_keys", B * es_::kAesRoundKeyWords),
+      .iv = check<uint8_t>(iv, "iv", B * es_::kAesBlock),
+      .enable = check<uint8_t>(enable, "enable", B),
+      .td = check<uint32_t>(td, "td", 256),
+      .isb = check<uint8_t>(isb, "isb", 256),
+      .sainfo = check<int64_t>(sainfo, "sainfo", B * es_::kSaWords)};
+  TORCH_CHECK(es.device() == nal.device() && es.device() == sainfo.device() && es.device() == es_off.device() &&
+                  es.device() == cap.device() && es.device() == info.device() && es.device() == pes.device() &&
+                  es.device() == sinfo.device() && es.device() == au.device() && es.device() == aframes.device() &&
+                  es.device() == round_keys.device() && es.device() == iv.device() && es.device() == enable.device() &&
+                  es.device() == td.device() && es.device() == isb.device(),
+              "tensors on different devices");
+  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
+                  (reinterpret_cast<uintptr_t>(iv.data_ptr()) & 15) == 0,
+              "es / iv must be 16-byte aligned");
+  hip_ok(D::launch_sample_aes(a), "sample_aes_decrypt launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -352,6 +382,9 @@ TORCH_LIBRARY(hlsp2p, m) {
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
   m.def("hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) hinfo, Tensor(b!) hps) -> ()");
+  m.def("sample_aes_decrypt(Tensor(a!) es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, "
+        "int max_nal, Tensor(b!) nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor round_keys, Tensor iv, "
+        "Tensor enable, Tensor td, Tensor isb, Tensor(c!) sainfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -364,6 +397,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("remux", &remux);
   m.impl("codec_config", &codec_config);
   m.impl("hevc_config", &hevc_config);
+  m.impl("sample_aes_decrypt", &sample_aes_decrypt);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -399,6 +433,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
   m.def("codec_config", &codec_config);
   m.def("hevc_config", &hevc_config);
+  m.def("sample_aes_decrypt", &sample_aes_decrypt);
+  m.def("sample_aes_round_bytes", &D::sample_aes_round_bytes);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

@@ -142,6 +142,19 @@ struct HevcConfigArgs {
 };
 hipError_t launch_hevc_config(const HevcConfigArgs& a);
 
+struct SampleAesArgs {
+  EsBatch b;                   // no tile space: the grid is max_pes x nseg x 2 (access units, audio PES)
+  uint8_t* es;                 // b.es, rewritten in place; b.ix.nal's length column is rewritten too
+  const uint32_t* round_keys;  // nseg x es::kAesRoundKeyWords, little-endian words of the equivalent inverse cipher
+  const uint8_t* iv;           // nseg x es::kAesBlock, 16-byte aligned
+  const uint8_t* enable;       // nseg; 0: the segment is left alone, its sainfo row is zero
+  const uint32_t* td;          // 256 words: TdL
+  const uint8_t* isb;          // 256 bytes: the inverse S-box
+  int64_t* sainfo;             // nseg x es::kSaWords
+};
+int sample_aes_round_bytes();
+hipError_t launch_sample_aes(const SampleAesArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

@@ -25,6 +25,7 @@
 #include "locator.hpp"
 #include "planner.hpp"
 #include "remux.hpp"
+#include "sampleaes.hpp"
 #include "shm_control.hpp"
 #include "store.hpp"
 #include "ts.hpp"
@@ -585,6 +586,60 @@ PYBIND11_MODULE(_runtime, m) {
     st["bad_sps"] = int(es::kHBadSps);
     st["not_hevc"] = int(es::kHNotHevc);
     m.attr("ES_HSTATUS") = st;
+  }
+
+  // Batched CPU SAMPLE-AES decryption in place with the device kernel's result (docs/SAMPLEAES.md): the
+  // inputs of remux_batch, of which es and the length column of nal are rewritten.
+  //   drk: uint32[B, 44] (expand_key_dec); iv: uint8[B, 16]; enable: uint8[B], 0 = the segment is left alone
+  //   sainfo: int64[B, ES_SAINFO_WORDS]
+  m.def("sample_decrypt_batch", [](py::array es_rw, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info,
+                                   Arr<int64_t> pes, int64_t max_pes, int64_t max_nal, py::array nal_rw,
+                                   Arr<int32_t> au, Arr<int32_t> aframes, Arr<int64_t> sinfo, Arr<uint32_t> drk,
+                                   Arr<uint8_t> iv, Arr<uint8_t> enable, py::array sainfo) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0)
+      throw std::invalid_argument("sample_decrypt_batch: max_pes and max_nal must be positive");
+    uint8_t* ep = mut_ptr<uint8_t>(es_rw, "es");
+    int32_t* np = mut_ptr<int32_t>(nal_rw, "nal");
+    int64_t* sa = mut_ptr<int64_t>(sainfo, "sainfo");
+    const Arr<uint8_t> es(es_rw);  // the same bytes: es_rw is contiguous uint8
+    if (es.data() != ep) throw std::invalid_argument("sample_decrypt_batch: es must be a contiguous uint8 array");
+    const bool sized = drk.size() >= B * es::kAesRoundKeyWords && iv.size() >= B * es::kAesBlock &&
+                       enable.size() >= B && sainfo.size() >= B * es::kSaWords;
+    const EsBatch batch = es_batch("sample_decrypt_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal_rw, &au, &aframes, &sinfo}, sized, [](int64_t) {});
+    const es::IndexTables<int32_t, const int64_t> ix{np, const_cast<int32_t*>(au.data()),
+                                                     const_cast<int32_t*>(aframes.data()), sinfo.data()};
+    const uint32_t* rk = drk.data();
+    const uint8_t *ivp = iv.data(), *en = enable.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      int64_t* row = sa + b * es::kSaWords;
+      if (!en[b]) {
+        std::fill(row, row + es::kSaWords, 0);
+        return;
+      }
+      const es::Segment s = batch.at(b);
+      es::sample_decrypt_segment(s, ep + batch.es_off[b], es::index_tables_at(ix, s, b), rk + b * es::kAesRoundKeyWords,
+                                 ivp + b * es::kAesBlock, row);
+    }, batch.total);
+  });
+  m.attr("ES_SAINFO_WORDS") = es::kSaWords;
+  m.attr("ES_SA_ROUND") = es::kSaRound;
+  {
+    py::dict d, st;
+    d["status"] = int(es::kSaStatus);
+    d["protected_nals"] = int(es::kSaProtectedNals);
+    d["removed_bytes"] = int(es::kSaRemovedBytes);
+    d["video_blocks"] = int(es::kSaVideoBlocks);
+    d["audio_frames"] = int(es::kSaAudioFrames);
+    d["audio_blocks"] = int(es::kSaAudioBlocks);
+    m.attr("ES_SAINFO") = d;
+    st["truncated"] = int64_t(es::kSaTruncated);
+    st["unsupported_video"] = int64_t(es::kSaUnsupportedVideo);
+    st["unsupported_audio"] = int64_t(es::kSaUnsupportedAudio);
+    st["partial_audio"] = int64_t(es::kSaPartialAudio);
+    m.attr("ES_SASTATUS") = st;
   }
 
   // ------------------------------------------------------------------ store

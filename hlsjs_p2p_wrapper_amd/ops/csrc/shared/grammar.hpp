@@ -1,7 +1,7 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
-// runtime/codec.cpp) and by the gfx950 kernels (kernels/ts_demux.hip, kernels/es_index.hip,
-// kernels/remux.hip, kernels/codec_config.hip).  Plain inline
+// runtime/codec.cpp, runtime/sampleaes.cpp) and by the gfx950 kernels (kernels/ts_demux.hip,
+// kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip, kernels/sample_aes.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -22,7 +22,10 @@ HLSP2P_RULE int64_t clamp(int64_t v, int64_t lo, int64_t hi) { return v < lo ? l
 namespace ts {
 constexpr int kSync = 0x47;
 constexpr int kPusi = 0x40;  // payload_unit_start_indicator, in header byte 1
-enum StreamType : int { kMpeg1Audio = 0x03, kMpeg2Audio = 0x04, kAdtsAac = 0x0F, kId3 = 0x15, kAvc = 0x1B, kHevc = 0x24 };
+enum StreamType : int {
+  kMpeg1Audio = 0x03, kMpeg2Audio = 0x04, kAdtsAac = 0x0F, kId3 = 0x15, kAvc = 0x1B, kHevc = 0x24,
+  kSampleAesAdts = 0xCF, kSampleAesAvc = 0xDB,  // HLS SAMPLE-AES: reported as kAdtsAac / kAvc
+};
 
 HLSP2P_RULE int packet_pid(int b1, int b2) { return ((b1 & 0x1f) << 8) | b2; }
 HLSP2P_RULE bool has_adaptation(int b3) { return (b3 & 0x20) != 0; }
@@ -88,12 +91,13 @@ HLSP2P_RULE Psi parse_psi(const uint8_t* data, int64_t n_packets) {
       const int type = p[q];
       const int epid = packet_pid(p[q + 1], p[q + 2]);
       const int eil = ((p[q + 3] & 0x0f) << 8) | p[q + 4];
-      if ((type == kAvc || type == kHevc) && r.pid[0] < 0) {
+      if ((type == kAvc || type == kHevc || type == kSampleAesAvc) && r.pid[0] < 0) {
         r.pid[0] = epid;
-        r.video_type = type;
-      } else if ((type == kAdtsAac || type == kMpeg1Audio || type == kMpeg2Audio) && r.pid[1] < 0) {
+        r.video_type = type == kSampleAesAvc ? kAvc : type;
+      } else if ((type == kAdtsAac || type == kMpeg1Audio || type == kMpeg2Audio || type == kSampleAesAdts) &&
+                 r.pid[1] < 0) {
         r.pid[1] = epid;
-        r.audio_type = type;
+        r.audio_type = type == kSampleAesAdts ? kAdtsAac : type;
       } else if (type == kId3 && r.pid[2] < 0) {
         r.pid[2] = epid;
       }
@@ -302,6 +306,40 @@ HLSP2P_RULE bool adts_config_usable(const AdtsConfig& c) { return c.rate_index <
 // Byte j >= 2 of a NAL unit is an emulation-prevention byte iff it is 03 behind two raw zeros
 // (p2 = b[j - 2], p1 = b[j - 1], b = b[j]).  Equal to the sequential rule: a dropped byte is never zero.
 HLSP2P_RULE bool is_emulation_prevention(int p2, int p1, int b) { return b == 3 && p1 == 0 && p2 == 0; }
+
+// ---- HLS SAMPLE-AES (docs/SAMPLEAES.md)
+// NAL row of an H.264 video ES with m access units: a slice (type 1 or 5) of an access unit the
+// remux keeps, with n > 0 clamped bytes, is unescaped and measured.
+HLSP2P_RULE bool sample_nal_candidate(int type, int64_t au, int64_t m, int64_t n) {
+  return (type == 1 || type == 5) && au >= 0 && au < m && n > 0;
+}
+// A candidate of u unescaped bytes is protected iff it is longer than the clear lead plus one block.
+HLSP2P_RULE bool sample_nal_protected(int64_t u) { return u > kSaClearLead + kAesBlock; }
+// Block j = 0, 1, .. of a protected NAL starts here in the unescaped NAL ...
+HLSP2P_RULE int64_t sample_block_at(int64_t j) { return kSaClearLead + kSaBlockStride * j; }
+// ... and is a cipher block iff more than 16 bytes remain at its start (strictly: a block that
+// ends exactly at u stays clear).
+HLSP2P_RULE bool sample_is_cipher_block(int64_t j, int64_t u) { return sample_block_at(j) + kAesBlock < u; }
+// cipher blocks of a NAL of u unescaped bytes
+HLSP2P_RULE int64_t sample_video_blocks(int64_t u) {
+  return sample_nal_protected(u) ? (u - kSaClearLead - kAesBlock - 1) / kSaBlockStride + 1 : 0;
+}
+// Cipher blocks of an ADTS frame, back to back from q + hdr + kSaAudioLead: the whole blocks of
+// the payload behind the 16-byte leader, none for a payload below 32 bytes.
+HLSP2P_RULE int64_t sample_audio_blocks(const AdtsFrame& f) {
+  const int64_t payload = f.len - f.hdr;
+  return payload < kSaAudioLead + kAesBlock ? 0 : (payload - kSaAudioLead) / kAesBlock;
+}
+// The status bits of a segment, from its demux and index rows alone.
+HLSP2P_RULE int64_t sample_status(const Segment& s, const int64_t* sinfo) {
+  const int64_t vtype = s.info[ts::kVideoType];
+  int64_t st = 0;
+  if (sinfo[kStatus] & kNalOverflow) st |= kSaTruncated;
+  if (vtype != ts::kAvc && clamp(s.info[ts::kVideoBytes], 0, s.cap) > 0) st |= kSaUnsupportedVideo;
+  if (!is_adts(s.info[ts::kAudioType]) && clamp(s.info[ts::kNumAudioPes], 0, s.max_pes) > 0) st |= kSaUnsupportedAudio;
+  if (sinfo[kStatus] & kAdtsError) st |= kSaPartialAudio;
+  return st;
+}
 
 // What sps_parse reads, in the order of the cinfo row (Cinfo kCProfileIdc .. kCSarHeight).
 struct SpsFields {

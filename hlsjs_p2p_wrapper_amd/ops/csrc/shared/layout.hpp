@@ -188,6 +188,25 @@ enum Hinfo : int {
 enum HevcStatus : int32_t {
   kHNoVps = 1, kHNoSps = 2, kHNoPps = 4, kHPsOverflow = 8, kHBadSps = 16, kHNotHevc = 32,
 };
+
+// ---- HLS SAMPLE-AES decryption of the indexed ES in place (docs/SAMPLEAES.md)
+constexpr int kSaWords = 6;
+// sainfo[] row (int64), identical on host and device; the counts are integer sums
+enum Sainfo : int {
+  kSaStatus = 0,
+  kSaProtectedNals = 1,
+  kSaRemovedBytes = 2,  // emulation-prevention bytes taken out of protected NALs
+  kSaVideoBlocks = 3,   // 16-byte cipher blocks
+  kSaAudioFrames = 4,   // ADTS frames with at least one cipher block
+  kSaAudioBlocks = 5,
+};
+enum SaStatus : int64_t { kSaTruncated = 1, kSaUnsupportedVideo = 2, kSaUnsupportedAudio = 4, kSaPartialAudio = 8 };
+constexpr int kSaRound = 4096;       // raw NAL bytes a workgroup unescapes per round
+constexpr int kSaClearLead = 32;     // unescaped bytes in front of a NAL's first cipher block
+constexpr int kSaBlockStride = 160;  // one cipher block in ten: 16 encrypted, 144 clear
+constexpr int kSaAudioLead = 16;     // clear payload bytes of an ADTS frame behind its header
+constexpr int kAesBlock = 16;
+constexpr int kAesRoundKeyWords = 44;  // equivalent-inverse-cipher round keys of one AES-128 key
 }  // namespace es
 
 // ---------------------------------------------------------------- CRC-32

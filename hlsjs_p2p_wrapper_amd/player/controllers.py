@@ -757,8 +757,13 @@ class StreamController:
             return  # aborted / stale
         self.stats = data["stats"]
         dd = frag.decryptdata
-        key = dd.key if (dd is not None and dd.method == "AES-128") else None
+        method = dd.method if dd is not None else None
+        key = dd.key if method == "AES-128" else None
         iv = frag.iv_for_decrypt() if key is not None else None
+        # METHOD=SAMPLE-AES: the segment is clear TS whose NAL units and ADTS frames are encrypted;
+        # the key goes to the step behind the sample index (ops/sampleaes.py), not to the CBC decrypt
+        sample_key = dd.key if method == "SAMPLE-AES" else None
+        sample_iv = frag.iv_for_decrypt() if sample_key is not None else None
         stats = data["stats"]
         payload = data["payload"]
         if type(payload) is RemoteSegment:  # fleet player: the node process already transmuxed it
@@ -770,7 +775,8 @@ class StreamController:
         ticket = getattr(payload, "swarm_verify", None)
         pipeline_for(dev, self.loop).submit(
             TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
-                        bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4"))))
+                        bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
+                        sample_key, sample_iv))
 
     def _on_parsed(self, frag: Fragment, stats: Any, r: Any) -> None:  # r: dict-like transmux result
         hls = self.hls
@@ -784,17 +790,22 @@ class StreamController:
             log.warning("fragment sn=%s level=%s: peer copy failed its CRC check; reloading", frag.sn, frag.level)
             self._kick()
             return
-        if r.get("error") is not None or r.get("status", 0) & 0b111111:
+        # a SAMPLE-AES fragment whose video or audio codec has no sample encryption format here
+        # (ops.sampleaes.SASTATUS unsupported_video | unsupported_audio) would buffer ciphertext
+        sample = r.get("sample_aes")
+        undecrypted = sample is not None and bool(sample["status"] & 0b110)
+        if r.get("error") is not None or r.get("status", 0) & 0b111111 or undecrypted:
             self.inflight.pop(key, None)
-            details = (ErrorDetails.FRAG_DECRYPT_ERROR if r.get("plain_bytes", 0) < 0
+            details = (ErrorDetails.FRAG_DECRYPT_ERROR if r.get("plain_bytes", 0) < 0 or undecrypted
                        else ErrorDetails.FRAG_PARSING_ERROR)
             # retried like a load error: back-off, up to fragLoadingMaxRetry, then fatal.  An
             # immediate reload of bytes that fail the same way (a cached copy) would spin this
             # loop without time advancing; the wrapper drops the cached copy on this event
             cfg = hls.config
             n = self._retry.get(key, 0) + 1
+            reason = f"SAMPLE-AES status {sample['status']}" if undecrypted else r.get("status")
             data = {"type": ErrorTypes.MEDIA_ERROR, "details": details, "fatal": n > cfg.fragLoadingMaxRetry,
-                    "frag": frag, "reason": str(r.get("error") or r.get("status"))}
+                    "frag": frag, "reason": str(r.get("error") or reason)}
             hls.trigger(Events.ERROR, data)
             if data["fatal"]:
                 log.error("fragment sn=%s level=%s failed: %s", frag.sn, frag.level, details)

@@ -20,7 +20,7 @@ class DecryptData:
 
     @property
     def needs_key(self) -> bool:
-        return self.method == "AES-128" and self.uri is not None and self.key is None
+        return self.method in ("AES-128", "SAMPLE-AES") and self.uri is not None and self.key is None
 
 
 # Bumped whenever a Fragment's ``start`` is REWRITTEN after construction: consumers that
@@ -82,7 +82,7 @@ class Fragment:
 
     def iv_for_decrypt(self) -> Optional[bytes]:
         dd = self.decryptdata
-        if dd is None or dd.method != "AES-128":
+        if dd is None or dd.method not in ("AES-128", "SAMPLE-AES"):
             return None
         if dd.iv is not None:
             return dd.iv

@@ -41,15 +41,18 @@ ALIGN = 256
 
 class TransmuxJob:
     """One fragment to transmux: ``payload`` (torch uint8 tensor on any device / numpy /
-    bytes), the AES-128 ``key`` and ``iv`` (``None``: clear), ``callback(result)``.  A plain
+    bytes), the AES-128 ``key`` and ``iv`` (``None``: clear), ``callback(result)``.  A
+    ``METHOD=SAMPLE-AES`` fragment is not CBC-encrypted as a whole: its ``key`` and ``iv`` stay
+    ``None`` and ``sample_key`` / ``sample_iv`` (16 bytes each) are set instead.  A plain
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
     code inside the compiled module."""
 
-    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux")
+    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
-                 index: bool = False, remux: bool = False) -> None:
+                 index: bool = False, remux: bool = False, sample_key: Optional[bytes] = None,
+                 sample_iv: Optional[bytes] = None) -> None:
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -59,7 +62,13 @@ class TransmuxJob:
         # a received segment's pending CRC check (agent/node.py VerifyTicket: ``expect``,
         # ``report(ok)``): the batch verifies the bytes -- fused into the decrypt -- reports the
         # outcome, and a fragment that fails gets a ``verify_failed`` error result
-        self.index = index or remux
+        if (sample_key is None) != (sample_iv is None):
+            raise ValueError("TransmuxJob: sample_key and sample_iv go together")
+        self.sample_key = sample_key
+        self.sample_iv = sample_iv
+        # set: the batch decrypts this fragment's protected NAL units and ADTS frames in its ES
+        # behind the sample index (ops/sampleaes.py) and its result gains ``sample_aes``
+        self.index = index or remux or sample_key is not None
         # True: the batch also indexes this fragment's NAL units, access units and ADTS frames
         # (ops/esindex.py) and its result gains ``samples``
         self.remux = remux
@@ -111,13 +120,16 @@ class _Columns:
     round keys ``drk[i]`` (``ops.aes.round_keys_le``) or, for the host, the raw key
     ``keys[i]``; ``expect`` (``None``: no checks) holds the CRC-32 fragment i's bytes must
     have, ``-1`` for no check; ``index`` (``None``: nobody) marks the fragments whose samples
-    are to be indexed, ``remux`` those to be remuxed as well."""
+    are to be indexed, ``remux`` those to be remuxed as well, ``sample`` (a subset of ``index``)
+    those whose ES is SAMPLE-AES protected, with ``sample_keys[i]`` / ``sample_ivs[i]``."""
 
-    __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index", "remux")
+    __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index", "remux", "sample", "sample_keys",
+                 "sample_ivs")
 
     def __init__(self, src: torch.Tensor, offs: np.ndarray, nb: np.ndarray, enc: np.ndarray, iv: np.ndarray,
                  drk: Optional[np.ndarray] = None, keys: Any = None, expect: Optional[np.ndarray] = None,
-                 index: Optional[np.ndarray] = None, remux: Optional[np.ndarray] = None) -> None:
+                 index: Optional[np.ndarray] = None, remux: Optional[np.ndarray] = None,
+                 sample: Optional[np.ndarray] = None, sample_keys: Any = None, sample_ivs: Any = None) -> None:
         self.src = src      # uint8 tensor on the pipeline's device
         self.offs = offs    # int64[n]
         self.nb = nb        # int64[n]
@@ -128,6 +140,9 @@ class _Columns:
         self.expect = expect  # int64[n]
         self.index = index  # bool[n]
         self.remux = remux  # bool[n], a subset of index
+        self.sample = sample  # bool[n], a subset of index
+        self.sample_keys = sample_keys  # n raw 16-byte keys (None where sample is not set)
+        self.sample_ivs = sample_ivs
 
 
 class MediaPipeline:
@@ -268,7 +283,9 @@ class MediaPipeline:
         cols = _Columns(src, np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64), enc, iv, drk=drk,
                         keys=None if cuda else [j.key for j in jobs], expect=expect,
                         index=_mask(n, [i for i, j in enumerate(jobs) if j.index]),
-                        remux=_mask(n, [i for i, j in enumerate(jobs) if j.remux]))
+                        remux=_mask(n, [i for i, j in enumerate(jobs) if j.remux]),
+                        sample=_mask(n, [i for i, j in enumerate(jobs) if j.sample_key is not None]),
+                        sample_keys=[j.sample_key for j in jobs], sample_ivs=[j.sample_iv for j in jobs])
         self.timer.add("stage", time.perf_counter() - t0)
         return cols
 
@@ -283,7 +300,8 @@ class MediaPipeline:
         fragment is taken as clear.  ``expect[i] >= 0``: fragment i's bytes must have that
         CRC-32 (a peer's trailer, verified here instead of by the node); :meth:`complete_columns`
         reports the outcome.  ``tag`` comes back from :meth:`complete_columns`.  No fragment is
-        indexed or remuxed (``TransmuxJob.index`` / ``.remux`` are the job form's)."""
+        indexed, sample-decrypted or remuxed (``TransmuxJob.index`` / ``.sample_key`` / ``.remux``
+        are the job form's)."""
         n = len(offs)
         if n == 0:
             return None
@@ -363,6 +381,17 @@ class MediaPipeline:
 
             g.ix = ix = _esx.index_batch(g.res, c.nb[g.rows])
             g.sinfo = _to_host(ix.sinfo)
+            # ... and the SAMPLE-AES decrypt of a group in which any row asked: one
+            # ``sample_decrypt_batch`` call behind the index and in front of the remux and the two
+            # configuration calls, which then read the decrypted ES; rows that did not ask are not
+            # enabled and stay as they are
+            if c.sample is not None and c.sample[g.rows].any():
+                from ..ops import sampleaes as _sa
+
+                il = g.rows.tolist()
+                g.sa = sa = _sa.sample_decrypt_batch(g.res, ix, c.nb[g.rows], [c.sample_keys[i] for i in il],
+                                                     [c.sample_ivs[i] for i in il], c.sample[g.rows].tolist())
+                g.sainfo = _to_host(sa.sainfo)
             # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
             # the index, its three tables on the same way to the host
             if c.remux is not None and c.remux[g.rows].any():
@@ -490,6 +519,12 @@ class MediaPipeline:
                         results[i]["samples"] = Samples(srows[k], g.ix, k)
                     if g.rx is not None and b.jobs[i].remux:  # ... and those that asked for the remux
                         results[i]["fmp4"] = Fmp4(g, k, srows[k])
+                    if g.sa is not None and b.jobs[i].sample_key is not None:  # ... and for the SAMPLE-AES decrypt
+                        from types import MappingProxyType
+
+                        from ..ops.sampleaes import segment_view
+
+                        results[i]["sample_aes"] = MappingProxyType(segment_view(_np(g.sainfo)[k]))
         self.timer.add("results", time.perf_counter() - t4)
         return results
 
@@ -804,6 +839,8 @@ class _Group:
     hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
     ix: Any = None  # EsIndex, when a job of the group asked for it, with ...
     sinfo: Any = None  # ... its sinfo rows on the host
+    sa: Any = None  # SampleAes, when a job of the group asked for it, with ...
+    sainfo: Any = None  # ... its sainfo rows on the host
     rx: Any = None  # Remuxed, when a job of the group asked for it, with ...
     rinfo: Any = None  # ... its three tables on the host
     vsamples: Any = None

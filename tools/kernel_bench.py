@@ -1,8 +1,8 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
 index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
-(H.264 and HEVC) and the MFMA CRC with HIP events and reports us / GB/s of input.
-Checks results against the host oracles once.
+(H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, and the MFMA CRC with
+HIP events and reports us / GB/s of input.  Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
 """
@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, hevcconfig, remux, segment, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, hevcconfig, remux, sampleaes, segment, tsdemux
 
 
 def timed(fn, iters):
@@ -26,6 +26,53 @@ def timed(fn, iters):
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e3 / iters  # us
+
+
+def timed_each(setup, fn, iters):
+    """``fn`` alone, with ``setup`` in front of every call and outside the timed intervals."""
+    setup()
+    fn()
+    torch.cuda.synchronize()
+    pairs = []
+    for _ in range(iters):
+        setup()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        pairs.append((a, b))
+    torch.cuda.synchronize()
+    return sum(a.elapsed_time(b) for a, b in pairs) * 1e3 / iters  # us
+
+
+def protect_es(es, es_offs, info, pes, nal, sinfo, aframes, key, iv):
+    """The tool's packager: the demuxed ES (host array, changed in place) with every block the
+    SAMPLE-AES format encrypts encrypted, one CBC chain per slice NAL and per ADTS frame.  No
+    emulation prevention is inserted (the ES keeps its size): where ciphertext happens to hold
+    ``00 00 03`` the decrypt drops a byte, a few times in a million blocks."""
+    I, S = tsdemux.INFO, esindex.SINFO
+    blocks = 0
+
+    def chain(at):  # the 16-byte blocks at the ascending byte offsets ``at``, as one CBC chain
+        idx = (at[:, None] + np.arange(16)[None, :]).reshape(-1)
+        es[idx] = aes.cbc_encrypt(key, iv, es[idx])[:len(idx)]
+        return len(at)
+
+    for i, base in enumerate(es_offs):
+        m = int(sinfo[i, S["n_au"]])
+        for off, n, typ, au in nal[i, :min(int(sinfo[i, S["n_nal"]]), nal.shape[1])]:
+            if typ in (1, 5) and 0 <= au < m and n > 48:
+                blocks += chain(base + off + np.arange(32, n - 16, 160))
+        a0 = base + int(info[i, I["audio_es_offset"]])
+        for k in range(int(info[i, I["n_audio_pes"]])):
+            q = a0 + int(pes[i, 1, k, 0])
+            for _ in range(int(aframes[i, k, 0])):
+                ln = ((int(es[q + 3]) & 3) << 11) | (int(es[q + 4]) << 3) | (int(es[q + 5]) >> 5)
+                hdr = 7 if es[q + 1] & 1 else 9
+                if ln - hdr >= 32:
+                    blocks += chain(q + hdr + 16 + 16 * np.arange((ln - hdr - 16) // 16))
+                q += ln
+    return blocks
 
 
 def main():
@@ -104,6 +151,36 @@ def main():
     hh = hevcconfig.hevc_config_batch(cpu24, esindex.index_batch(cpu24, [len(ref)]), [len(ref)])
     assert all(torch.equal(getattr(hv, k)[0].cpu(), getattr(hh, k)[0]) for k in ("hinfo", "hps")), \
         "hevcconfig (HEVC) mismatch"
+    # the SAMPLE-AES decrypt of the same ES, protected here with the batch's key (plan + decrypt).  The
+    # call rewrites es and nal, so every timed call sees protected input again: the restore from
+    # device copies runs in front of it, outside the timed interval, and is reported next to it
+    skeys, sivs = [origin.key] * args.segs, [origin.iv] * args.segs
+    es_host = r.es.cpu().numpy().copy()
+    n_blocks = protect_es(es_host, r.es_offs, r.info.cpu().numpy(), r.pes.cpu().numpy(), ix.nal.cpu().numpy(),
+                          ix.sinfo.cpu().numpy(), ix.aframes.cpu().numpy(), origin.key, origin.iv)
+    es_prot, nal0 = torch.from_numpy(es_host).to(dev), ix.nal.clone()
+    rs = tsdemux.DemuxResult(r.info, r.pes, torch.empty_like(es_prot), r.es_offs)
+    sx = esindex.EsIndex(torch.empty_like(nal0), ix.au, ix.aframes, ix.sinfo)
+
+    def restore():
+        rs.es.copy_(es_prot)
+        sx.nal.copy_(nal0)
+
+    decrypt = lambda: sampleaes.sample_decrypt_batch(rs, sx, caps, skeys, sivs)  # noqa: E731
+    res["sampleaes_us"] = timed_each(restore, decrypt, args.iters)
+    res["sampleaes_restore_us"] = round(timed(restore, args.iters), 1)
+    restore()
+    sa = sampleaes.sample_decrypt_batch(rs, sx, caps, skeys, sivs)
+    res["sampleaes_blocks"] = int(sa.sainfo[:, 3].sum() + sa.sainfo[:, 5].sum())
+    assert abs(res["sampleaes_blocks"] - n_blocks) <= 64, "sampleaes block count"
+    o0 = int(r.es_offs[0])
+    hs = tsdemux.DemuxResult(cpu.info, cpu.pes, torch.from_numpy(es_host[o0:o0 + len(ref) + 256].copy()), cpu.es_offs)
+    hsx = esindex.EsIndex(hx.nal.clone(), hx.au, hx.aframes, hx.sinfo)
+    hsa = sampleaes.sample_decrypt_batch(hs, hsx, [len(ref)], skeys[:1], sivs[:1])
+    assert torch.equal(sa.sainfo[0].cpu(), hsa.sainfo[0]) and torch.equal(sx.nal[0].cpu(), hsx.nal[0]) and \
+        torch.equal(rs.es[o0:o0 + len(ref)].cpu(), hs.es[:len(ref)]), "sampleaes mismatch"
+    if int(sa.sainfo[0, 2]) == 0:  # no ciphertext looked like emulation prevention: the clear ES is back
+        assert torch.equal(rs.es[o0:o0 + len(ref)], r.es[o0:o0 + len(ref)]), "sampleaes does not invert the packager"
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
@@ -112,8 +189,8 @@ def main():
     res["copy_us"] = timed(lambda: segment.copy_segments(src, cp, offs, offs, lens), args.iters)
     assert torch.equal(cp[offs[5]:offs[5] + lens[5]], src[offs[5]:offs[5] + lens[5]]), "copy mismatch"
     res["torch_copy_us"] = timed(lambda: cp.copy_(src), args.iters)
-    for k in ("aes", "demux", "esindex", "remux", "codecconfig", "hevcconfig", "hevcconfig_search", "crc", "copy",
-              "torch_copy"):
+    for k in ("aes", "demux", "esindex", "remux", "codecconfig", "hevcconfig", "hevcconfig_search", "sampleaes", "crc",
+              "copy", "torch_copy"):
         res[f"{k}_GBps"] = round(total / (res[f"{k}_us"] * 1e-6) / 1e9, 1)
         res[f"{k}_us"] = round(res[f"{k}_us"], 1)
     res["bytes"] = total
