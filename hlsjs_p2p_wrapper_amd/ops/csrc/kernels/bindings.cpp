@@ -249,6 +249,36 @@ void sample_aes_decrypt(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tenso
   hip_ok(D::launch_sample_aes(a), "sample_aes_decrypt launch");
 }
 
+// Caption extraction of a demuxed and indexed batch (captions.hip): the inputs of codec_config, all
+// only read, an enable byte per segment, es::cc_scratch(B, max_nal) words of scratch, and the five
+// caption tables of max_cc rows per segment.
+void cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
+                Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor enable, int64_t max_cc, Tensor scratch,
+                Tensor ccsamples, Tensor ccpts, Tensor ccbytes, Tensor cc608, Tensor ccinfo) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0 && max_nal <= 0x7fffffff,
+              "cc_extract: max_pes / max_nal out of range");
+  TORCH_CHECK(es_::max_cc_ok(max_cc), "cc_extract: max_cc must be 1 to 2048");
+  TORCH_CHECK(B <= 65535, "cc_extract: at most 65535 segments per call");
+  const D::CcExtractArgs a{
+      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .enable = check<uint8_t>(enable, "enable", B),
+      .max_cc = max_cc,
+      .scratch = check<int32_t>(scratch, "scratch", es_::cc_scratch(B, max_nal).end),
+      .t = {check<int32_t>(ccsamples, "ccsamples", hlsp2p::table_words(B, max_cc, es_::kCcRowWords)),
+            check<int64_t>(ccpts, "ccpts", B * max_cc),
+            check<uint8_t>(ccbytes, "ccbytes", B * max_cc * es_::kCcSlotBytes),
+            check<uint8_t>(cc608, "cc608", B * max_cc * 2 * es_::kCcFieldBytes),
+            check<int64_t>(ccinfo, "ccinfo", B * es_::kCcInfoWords)}};
+  for (const Tensor* t : {&es_off, &cap, &info, &pes, &nal, &au, &aframes, &sinfo, &enable, &scratch, &ccsamples, &ccpts,
+                          &ccbytes, &cc608, &ccinfo})
+    TORCH_CHECK(es.device() == t->device(), "tensors on different devices");
+  for (const Tensor* t : {&es, &nal, &scratch, &ccsamples, &ccbytes, &cc608})
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0,
+                "es / nal / scratch / ccsamples / ccbytes / cc608 must be 16-byte aligned");
+  hip_ok(D::launch_cc_extract(a), "cc_extract launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -385,6 +415,9 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("sample_aes_decrypt(Tensor(a!) es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, "
         "int max_nal, Tensor(b!) nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor round_keys, Tensor iv, "
         "Tensor enable, Tensor td, Tensor isb, Tensor(c!) sainfo) -> ()");
+  m.def("cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
+        "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor enable, int max_cc, Tensor(a!) scratch, "
+        "Tensor(b!) ccsamples, Tensor(c!) ccpts, Tensor(d!) ccbytes, Tensor(e!) cc608, Tensor(f!) ccinfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -398,6 +431,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("codec_config", &codec_config);
   m.impl("hevc_config", &hevc_config);
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
+  m.impl("cc_extract", &cc_extract);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -435,6 +469,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("hevc_config", &hevc_config);
   m.def("sample_aes_decrypt", &sample_aes_decrypt);
   m.def("sample_aes_round_bytes", &D::sample_aes_round_bytes);
+  m.def("cc_extract", &cc_extract);
+  m.def("cc_scratch_words", [](int64_t nseg, int64_t max_nal) { return es_::cc_scratch(nseg, max_nal).end; },
+        py::arg("nseg"), py::arg("max_nal"));
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

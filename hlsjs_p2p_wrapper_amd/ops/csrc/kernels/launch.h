@@ -155,6 +155,15 @@ struct SampleAesArgs {
 int sample_aes_round_bytes();
 hipError_t launch_sample_aes(const SampleAesArgs& a);
 
+struct CcExtractArgs {
+  EsBatch b;              // no tile space: cc_scan_kernel's grid is ceil(max_nal / 64) x nseg, cc_pack_kernel's nseg; ix is only read
+  const uint8_t* enable;  // nseg; 0: the segment gets the fill values and an all-zero ccinfo row
+  int64_t max_cc;         // es::max_cc_ok(max_cc)
+  int32_t* scratch;       // es::cc_scratch(nseg, max_nal), 16-byte aligned
+  es::CcTables t;         // 16-byte aligned each
+};
+hipError_t launch_cc_extract(const CcExtractArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "aes_host.hpp"
+#include "captions.hpp"
 #include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
@@ -640,6 +641,68 @@ PYBIND11_MODULE(_runtime, m) {
     st["unsupported_audio"] = int64_t(es::kSaUnsupportedAudio);
     st["partial_audio"] = int64_t(es::kSaPartialAudio);
     m.attr("ES_SASTATUS") = st;
+  }
+
+  // Batched CPU caption extraction with the device kernels' layout (docs/CAPTIONS.md): the inputs of
+  // config_batch and an enable byte per segment (0: fill values and an all-zero ccinfo row).
+  //   ccsamples: int32[B, max_cc, ES_CCROW_WORDS]; ccpts: int64[B, max_cc]; ccbytes: uint8[B, max_cc, ES_CC_SLOT_BYTES]
+  //   cc608: uint8[B, max_cc, 2, ES_CC_FIELD_BYTES]; ccinfo: int64[B, ES_CCINFO_WORDS]
+  m.def("caption_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info,
+                            Arr<int64_t> pes, int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au,
+                            Arr<int32_t> aframes, Arr<int64_t> sinfo, Arr<uint8_t> enable, int64_t max_cc,
+                            py::array ccsamples, py::array ccpts, py::array ccbytes, py::array cc608,
+                            py::array ccinfo) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("caption_batch: max_pes and max_nal must be positive");
+    if (!es::max_cc_ok(max_cc)) throw std::invalid_argument("caption_batch: max_cc must be 1 to 2048");
+    const es::CcTables t{mut_ptr<int32_t>(ccsamples, "ccsamples"), mut_ptr<int64_t>(ccpts, "ccpts"),
+                         mut_ptr<uint8_t>(ccbytes, "ccbytes"), mut_ptr<uint8_t>(cc608, "cc608"),
+                         mut_ptr<int64_t>(ccinfo, "ccinfo")};
+    const bool sized = enable.size() >= B && ccsamples.size() >= table_words(B, max_cc, es::kCcRowWords) &&
+                       ccpts.size() >= B * max_cc && ccbytes.size() >= B * max_cc * es::kCcSlotBytes &&
+                       cc608.size() >= B * max_cc * 2 * es::kCcFieldBytes && ccinfo.size() >= B * es::kCcInfoWords;
+    const EsBatch batch = es_batch("caption_batch", es, es_off, cap, info, pes, max_pes, max_nal,
+                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
+    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
+    const uint8_t* en = enable.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      const es::Segment s = batch.at(b);
+      es::caption_segment(s, es::index_tables_at(ix, s, b), en[b] != 0, max_cc, es::cc_tables_at(t, max_cc, b));
+    }, batch.total);
+  });
+  m.attr("ES_CCINFO_WORDS") = es::kCcInfoWords;
+  m.attr("ES_CCROW_WORDS") = es::kCcRowWords;
+  m.attr("ES_CC_NAL_BYTES") = es::kCcNalBytes;
+  m.attr("ES_CC_SLOT_BYTES") = es::kCcSlotBytes;
+  m.attr("ES_CC_FIELD_BYTES") = es::kCcFieldBytes;
+  m.attr("ES_CC_DEFAULT_MAX") = es::kDefaultMaxCc;
+  m.attr("ES_CC_MAX_LIMIT") = es::kMaxCcLimit;
+  {
+    py::dict d, row, st;
+    d["status"] = int(es::kCiStatus);
+    d["n_sei"] = int(es::kCiNumSei);
+    d["n_samples"] = int(es::kCiNumSamples);
+    d["n_triples"] = int(es::kCiNumTriples);
+    d["field1_pairs"] = int(es::kCiField1Pairs);
+    d["field2_pairs"] = int(es::kCiField2Pairs);
+    d["first_pts"] = int(es::kCiFirstPts);
+    d["last_pts"] = int(es::kCiLastPts);
+    m.attr("ES_CCINFO") = d;
+    row["nal"] = int(es::kCrNal);
+    row["au"] = int(es::kCrAu);
+    row["size"] = int(es::kCrSize);
+    row["cc_count"] = int(es::kCrCount);
+    row["order"] = int(es::kCrOrder);
+    row["field1_pairs"] = int(es::kCrField1Pairs);
+    row["field2_pairs"] = int(es::kCrField2Pairs);
+    row["flags"] = int(es::kCrFlags);
+    m.attr("ES_CCROW") = row;
+    st["truncated"] = int64_t(es::kCcTruncated);
+    st["unsupported_video"] = int64_t(es::kCcUnsupportedVideo);
+    st["cc_overflow"] = int64_t(es::kCcOverflow);
+    st["sei_clipped"] = int64_t(es::kCcSeiClipped);
+    m.attr("ES_CCSTATUS") = st;
   }
 
   // ------------------------------------------------------------------ store

@@ -1,7 +1,7 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
-// runtime/codec.cpp, runtime/sampleaes.cpp) and by the gfx950 kernels (kernels/ts_demux.hip,
-// kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip, kernels/sample_aes.hip).  Plain inline
+// runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp) and by the gfx950 kernels (kernels/ts_demux.hip,
+// kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip, kernels/sample_aes.hip, kernels/captions.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -581,6 +581,74 @@ HLSP2P_RULE Delta32 delta32(int64_t x, int64_t y, bool non_negative) {
   const uint64_t d = uy - ux;
   if (non_negative || d > 0x80000000u) return {0, false};
   return {static_cast<int32_t>(-static_cast<int64_t>(d)), true};
+}
+
+// ---- CEA-608/708 caption data in SEI NAL units (docs/CAPTIONS.md)
+// header bytes of a NAL unit in front of its RBSP
+HLSP2P_RULE int nal_header_bytes(bool hevc) { return hevc ? kHevcNalHeader : 1; }
+// NAL row of a video ES with m access units: an SEI (H.264) or a prefix SEI (HEVC) of an access
+// unit, with more clamped bytes than its header, is unescaped and walked.
+HLSP2P_RULE bool cc_nal_candidate(bool hevc, int type, int64_t au, int64_t m, int64_t n) {
+  return type == (hevc ? kSeiHevcPrefix : kSeiH264) && au >= 0 && au < m && n > nal_header_bytes(hevc);
+}
+// One sei_message header at p of the u unescaped bytes ub(0 .. u), u - p >= 2: payloadType T and
+// payloadSize S with their FF extension bytes; p moves behind the header.  false: the header or
+// the S payload bytes behind it run off the bytes, the walk ends.
+template <class UB>
+HLSP2P_RULE bool cc_message_header(UB ub, int u, int& p, int& T, int& S) {
+  T = 0;
+  while (p < u && ub(p) == 0xFF) {
+    T += 255;
+    ++p;
+  }
+  if (p >= u) return false;
+  T += ub(p++);
+  S = 0;
+  while (p < u && ub(p) == 0xFF) {
+    S += 255;
+    ++p;
+  }
+  if (p >= u) return false;
+  S += ub(p++);
+  return S <= u - p;
+}
+// cc_count of the ATSC A/53 caption payload a message (T, S) at p holds, -1 for any other message:
+// itu_t_t35 country 0xB5, provider 0x0031, 'GA94', user_data_type_code 3, and 10 + 3 cc_count <= S.
+template <class UB>
+HLSP2P_RULE int cc_ga94_match(UB ub, int p, int T, int S) {
+  if (T != kSeiUserDataT35 || S < kCcHeadBytes + 2) return -1;
+  if (ub(p) != 0xB5 || ub(p + 1) != 0x00 || ub(p + 2) != 0x31 || ub(p + 3) != 'G' || ub(p + 4) != 'A' ||
+      ub(p + 5) != '9' || ub(p + 6) != '4' || ub(p + 7) != 3)
+    return -1;
+  const int c = ub(p + kCcHeadBytes) & kCcMaxTriples;
+  return kCcHeadBytes + 2 + 3 * c <= S ? c : -1;
+}
+// The first caption message of the u unescaped bytes of an SEI: its sample is
+// ub(at .. at + 2 + 3 count).  count < 0: none.  Every step consumes at least two bytes.
+struct CcMatch { int at, count; };
+template <class UB>
+HLSP2P_RULE CcMatch cc_find(UB ub, int u) {
+  int p = 0;
+  while (u - p >= 2) {
+    int T, S;
+    if (!cc_message_header(ub, u, p, T, S)) break;
+    const int c = cc_ga94_match(ub, p, T, S);
+    if (c >= 0) return {p + kCcHeadBytes, c};
+    p += S;
+  }
+  return {0, -1};
+}
+// Triple (f, b1, b2) of a sample gives a 608 byte pair to field 0 or 1, or to none (-1): cc_valid
+// set, cc_type 0 or 1, and the two bytes without their parity bits not both zero.
+HLSP2P_RULE int cc_608_field(int f, int b1, int b2) {
+  return (f & 4) && (f & 3) < 2 && ((b1 | b2) & 0x7f) != 0 ? (f & 3) : -1;
+}
+// The status bits of a segment, from its demux and index rows alone.
+HLSP2P_RULE int64_t cc_status(const Segment& s, const int64_t* sinfo) {
+  int64_t st = 0;
+  if (sinfo[kStatus] & kNalOverflow) st |= kCcTruncated;
+  if (!video_supported(s.info[ts::kVideoType]) && clamp(s.info[ts::kVideoBytes], 0, s.cap) > 0) st |= kCcUnsupportedVideo;
+  return st;
 }
 }  // namespace es
 }  // namespace hlsp2p

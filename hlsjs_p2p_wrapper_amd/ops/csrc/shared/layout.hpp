@@ -207,6 +207,60 @@ constexpr int kSaBlockStride = 160;  // one cipher block in ten: 16 encrypted, 1
 constexpr int kSaAudioLead = 16;     // clear payload bytes of an ADTS frame behind its header
 constexpr int kAesBlock = 16;
 constexpr int kAesRoundKeyWords = 44;  // equivalent-inverse-cipher round keys of one AES-128 key
+
+// ---- CEA-608/708 caption data of SEI NAL units (docs/CAPTIONS.md)
+constexpr int kCcInfoWords = 8;
+constexpr int kCcRowWords = 8;
+constexpr int64_t kDefaultMaxCc = 512;
+constexpr int64_t kMaxCcLimit = 2048;  // max_cc: 1 .. this
+constexpr bool max_cc_ok(int64_t max_cc) { return max_cc >= 1 && max_cc <= kMaxCcLimit; }
+constexpr int kCcNalBytes = 1024;   // raw bytes of a candidate NAL that are looked at
+constexpr int kCcSlotBytes = 96;    // ccbytes slot: cc_count byte, em_data, at most 31 triples (95 bytes)
+constexpr int kCcMaxTriples = 31;   // cc_count is five bits
+constexpr int kCcFieldBytes = 64;   // cc608 [segment][max_cc][2][kCcFieldBytes]: at most 31 pairs of two bytes per field
+constexpr int kCcHeadBytes = 8;     // of a matched message: country, provider (2), 'GA94', type code; the sample starts behind
+constexpr int kSeiH264 = 6, kSeiHevcPrefix = 39;  // nal_unit_type of a candidate
+constexpr int kSeiUserDataT35 = 4;                // payloadType user_data_registered_itu_t_t35
+
+// ccsamples[] row (int32) [segment][max_cc], -1 rows beyond the recorded samples
+enum CcRow : int {
+  kCrNal = 0, kCrAu = 1,
+  kCrSize = 2,   // 2 + 3 cc_count
+  kCrCount = 3,  // cc_count
+  kCrOrder = 4,  // presentation rank among the recorded samples
+  kCrField1Pairs = 5, kCrField2Pairs = 6,
+  kCrFlags = 7,  // CcFlags
+};
+enum CcFlags : int { kCcProcess = 1 };  // process_cc_data_flag, bytes[0] & 0x40
+
+// ccinfo[] row (int64), identical on host and device; the counts are integer sums
+enum Ccinfo : int {
+  kCiStatus = 0,
+  kCiNumSei = 1,      // candidates walked
+  kCiNumSamples = 2,  // true total, also when the table overflowed
+  kCiNumTriples = 3,  // of the recorded samples, as the two pair counts
+  kCiField1Pairs = 4, kCiField2Pairs = 5,
+  kCiFirstPts = 6, kCiLastPts = 7,  // min / max over the recorded samples, -1 without one
+};
+enum CcStatus : int64_t { kCcTruncated = 1, kCcUnsupportedVideo = 2, kCcOverflow = 4, kCcSeiClipped = 8 };
+// One segment's five caption tables, or a batch's.
+struct CcTables {
+  int32_t* samples;  // [max_cc][kCcRowWords]
+  int64_t* pts;      // [max_cc]
+  uint8_t* bytes;    // [max_cc][kCcSlotBytes]
+  uint8_t* cc608;    // [max_cc][2][kCcFieldBytes]
+  int64_t* info;     // [kCcInfoWords]
+};
+
+// scratch (int32) between the two caption kernels, element offsets:
+// [flag: nseg x max_nal | hit: nseg x max_nal x kCcSlotBytes / 4], hit 16-byte aligned.
+// flag of row k < R = CcScratchFlag bits | size << 8; hit holds the slot of a row whose flag has kCfHit
+enum CcScratchFlag : int { kCfCandidate = 1, kCfClipped = 2, kCfHit = 4 };
+constexpr int kCfSizeShift = 8;
+struct CcScratch { int64_t flag, hit, end; };
+constexpr CcScratch cc_scratch(int64_t nseg, int64_t max_nal) {
+  return {0, (nseg * max_nal + 3) / 4 * 4, (nseg * max_nal + 3) / 4 * 4 + nseg * max_nal * (kCcSlotBytes / 4)};
+}
 }  // namespace es
 
 // ---------------------------------------------------------------- CRC-32

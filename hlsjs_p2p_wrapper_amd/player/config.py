@@ -99,6 +99,10 @@ def _default_config() -> Dict[str, Any]:
         # "startDTS" / "endDTS" and the sample count in "nb"; FRAG_PARSING_INIT_SEGMENT carries each
         # track's init segment, codec and container (docs/INITSEGMENT.md)
         "remuxFmp4": False,
+        # extract the CEA-608/708 caption data of every fragment's SEI NAL units on the transmux
+        # device (docs/CAPTIONS.md; implies the index) and emit it on FRAG_PARSING_USERDATA; hls.js's
+        # name, off by default here like every device feature
+        "enableCEA708Captions": False,
     }
 
 

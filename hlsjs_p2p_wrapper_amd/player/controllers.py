@@ -776,7 +776,7 @@ class StreamController:
         pipeline_for(dev, self.loop).submit(
             TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
                         bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
-                        sample_key, sample_iv))
+                        sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions"))))
 
     def _on_parsed(self, frag: Fragment, stats: Any, r: Any) -> None:  # r: dict-like transmux result
         hls = self.hls
@@ -846,6 +846,12 @@ class StreamController:
         listening = hls.listening
         if listening(Events.FRAG_PARSING_METADATA) and r["id3"].numel():
             hls.trigger(Events.FRAG_PARSING_METADATA, {"frag": frag, "samples": r["id3"]})
+        # enableCEA708Captions: the caption data of the fragment's SEI NAL units (ops/captions.py), where
+        # hls.js's remuxer emits it: behind the metadata and in front of the data events
+        if hls.config.get("enableCEA708Captions") and listening(Events.FRAG_PARSING_USERDATA):
+            captions = r.get("captions")
+            if captions is not None and captions["n_samples"] > 0:
+                hls.trigger(Events.FRAG_PARSING_USERDATA, {"frag": frag, "samples": captions})
         vfirst, vlast, nv = info["video_first_pts"], info["video_last_pts"], info["n_video_pes"]
         if vfirst >= 0 and vlast >= vfirst and nv > 1:
             frame = (vlast - vfirst) / (nv - 1)

@@ -47,12 +47,13 @@ class TransmuxJob:
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
     code inside the compiled module."""
 
-    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv")
+    __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
+                 "captions")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
                  index: bool = False, remux: bool = False, sample_key: Optional[bytes] = None,
-                 sample_iv: Optional[bytes] = None) -> None:
+                 sample_iv: Optional[bytes] = None, captions: bool = False) -> None:
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -68,12 +69,15 @@ class TransmuxJob:
         self.sample_iv = sample_iv
         # set: the batch decrypts this fragment's protected NAL units and ADTS frames in its ES
         # behind the sample index (ops/sampleaes.py) and its result gains ``sample_aes``
-        self.index = index or remux or sample_key is not None
+        self.index = index or remux or sample_key is not None or captions
         # True: the batch also indexes this fragment's NAL units, access units and ADTS frames
         # (ops/esindex.py) and its result gains ``samples``
         self.remux = remux
         # True (implies ``index``): the batch also remuxes this fragment to fMP4 samples and mdat
         # boxes (ops/remux.py) and its result gains ``fmp4``
+        self.captions = captions
+        # True (implies ``index``): the batch also extracts the CEA-608/708 caption data of this
+        # fragment's SEI NAL units (ops/captions.py) and its result gains ``captions``
 
     def __repr__(self) -> str:
         return f"TransmuxJob(key={'set' if self.key else None}, frag={self.frag!r})"
@@ -121,15 +125,17 @@ class _Columns:
     ``keys[i]``; ``expect`` (``None``: no checks) holds the CRC-32 fragment i's bytes must
     have, ``-1`` for no check; ``index`` (``None``: nobody) marks the fragments whose samples
     are to be indexed, ``remux`` those to be remuxed as well, ``sample`` (a subset of ``index``)
-    those whose ES is SAMPLE-AES protected, with ``sample_keys[i]`` / ``sample_ivs[i]``."""
+    those whose ES is SAMPLE-AES protected, with ``sample_keys[i]`` / ``sample_ivs[i]``, ``captions``
+    (a subset of ``index``) those whose caption data is to be extracted."""
 
     __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index", "remux", "sample", "sample_keys",
-                 "sample_ivs")
+                 "sample_ivs", "captions")
 
     def __init__(self, src: torch.Tensor, offs: np.ndarray, nb: np.ndarray, enc: np.ndarray, iv: np.ndarray,
                  drk: Optional[np.ndarray] = None, keys: Any = None, expect: Optional[np.ndarray] = None,
                  index: Optional[np.ndarray] = None, remux: Optional[np.ndarray] = None,
-                 sample: Optional[np.ndarray] = None, sample_keys: Any = None, sample_ivs: Any = None) -> None:
+                 sample: Optional[np.ndarray] = None, sample_keys: Any = None, sample_ivs: Any = None,
+                 captions: Optional[np.ndarray] = None) -> None:
         self.src = src      # uint8 tensor on the pipeline's device
         self.offs = offs    # int64[n]
         self.nb = nb        # int64[n]
@@ -143,6 +149,7 @@ class _Columns:
         self.sample = sample  # bool[n], a subset of index
         self.sample_keys = sample_keys  # n raw 16-byte keys (None where sample is not set)
         self.sample_ivs = sample_ivs
+        self.captions = captions  # bool[n], a subset of index
 
 
 class MediaPipeline:
@@ -285,7 +292,8 @@ class MediaPipeline:
                         index=_mask(n, [i for i, j in enumerate(jobs) if j.index]),
                         remux=_mask(n, [i for i, j in enumerate(jobs) if j.remux]),
                         sample=_mask(n, [i for i, j in enumerate(jobs) if j.sample_key is not None]),
-                        sample_keys=[j.sample_key for j in jobs], sample_ivs=[j.sample_iv for j in jobs])
+                        sample_keys=[j.sample_key for j in jobs], sample_ivs=[j.sample_iv for j in jobs],
+                        captions=_mask(n, [i for i, j in enumerate(jobs) if j.captions]))
         self.timer.add("stage", time.perf_counter() - t0)
         return cols
 
@@ -300,8 +308,8 @@ class MediaPipeline:
         fragment is taken as clear.  ``expect[i] >= 0``: fragment i's bytes must have that
         CRC-32 (a peer's trailer, verified here instead of by the node); :meth:`complete_columns`
         reports the outcome.  ``tag`` comes back from :meth:`complete_columns`.  No fragment is
-        indexed, sample-decrypted or remuxed (``TransmuxJob.index`` / ``.sample_key`` / ``.remux``
-        are the job form's)."""
+        indexed, sample-decrypted, remuxed or searched for captions (``TransmuxJob.index`` /
+        ``.sample_key`` / ``.remux`` / ``.captions`` are the job form's)."""
         n = len(offs)
         if n == 0:
             return None
@@ -392,6 +400,14 @@ class MediaPipeline:
                 g.sa = sa = _sa.sample_decrypt_batch(g.res, ix, c.nb[g.rows], [c.sample_keys[i] for i in il],
                                                      [c.sample_ivs[i] for i in il], c.sample[g.rows].tolist())
                 g.sainfo = _to_host(sa.sainfo)
+            # ... and the caption data of a group in which any row asked: one ``caption_batch`` call
+            # behind the SAMPLE-AES step and in front of the remux, its ``ccinfo`` rows on the same
+            # way to the host; rows that did not ask are not enabled
+            if c.captions is not None and c.captions[g.rows].any():
+                from ..ops import captions as _cc
+
+                g.cc = cc = _cc.caption_batch(g.res, ix, c.nb[g.rows], enable=c.captions[g.rows].tolist())
+                g.ccinfo = _to_host(cc.ccinfo)
             # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
             # the index, its three tables on the same way to the host
             if c.remux is not None and c.remux[g.rows].any():
@@ -525,6 +541,8 @@ class MediaPipeline:
                         from ..ops.sampleaes import segment_view
 
                         results[i]["sample_aes"] = MappingProxyType(segment_view(_np(g.sainfo)[k]))
+                    if g.cc is not None and b.jobs[i].captions:  # ... and for the caption data
+                        results[i]["captions"] = CaptionData(g, k)
         self.timer.add("results", time.perf_counter() - t4)
         return results
 
@@ -658,6 +676,49 @@ class Samples(_View):
     def __repr__(self) -> str:
         fields = {k: self[k] for k in self.keys() if k not in self._TABLES}
         return f"Samples({fields})"
+
+
+class CaptionData(_View):
+    """Read-only mapping of one fragment's caption data (``TransmuxJob.captions``): the ``ccinfo``
+    fields by name (:data:`ops.captions.CCINFO`), ``samples`` / ``pts`` / ``bytes`` / ``cc608`` (the
+    fragment's rows of the batch's device tables, viewed on first access) and ``host()``: the
+    host view of :func:`ops.captions.segment_view` (``samples`` as hls.js's user-data samples and
+    ``field1`` / ``field2``, in presentation order), which syncs and is built on first call."""
+
+    __slots__ = ("_g", "_k", "_host")
+    _TABLES = {"samples": "ccsamples", "pts": "ccpts", "bytes": "ccbytes", "cc608": "cc608"}
+
+    def __init__(self, group, k: int) -> None:
+        self._g = group
+        self._k = k
+        self._host: Any = None
+
+    def host(self) -> Dict[str, Any]:
+        if self._host is None:
+            self._host = self._g.cc.segment(self._k)
+        return self._host
+
+    def __getitem__(self, name: str):
+        from ..ops.captions import CCINFO
+
+        slot = CCINFO.get(name)
+        if slot is not None:
+            return int(_np(self._g.ccinfo)[self._k, slot])
+        if name in self._TABLES:
+            return getattr(self._g.cc, self._TABLES[name])[self._k]
+        if name == "host":
+            return self.host
+        raise KeyError(name)
+
+    def keys(self):
+        from ..ops.captions import CCINFO
+
+        return [*CCINFO, *self._TABLES, "host"]
+
+    def __repr__(self) -> str:
+        from ..ops.captions import CCINFO
+
+        return f"CaptionData({ {k: self[k] for k in CCINFO} })"
 
 
 class Fmp4Track(_View):
@@ -841,6 +902,8 @@ class _Group:
     sinfo: Any = None  # ... its sinfo rows on the host
     sa: Any = None  # SampleAes, when a job of the group asked for it, with ...
     sainfo: Any = None  # ... its sainfo rows on the host
+    cc: Any = None  # Captions, when a job of the group asked for it, with ...
+    ccinfo: Any = None  # ... its ccinfo rows on the host
     rx: Any = None  # Remuxed, when a job of the group asked for it, with ...
     rinfo: Any = None  # ... its three tables on the host
     vsamples: Any = None

@@ -1,8 +1,9 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
 index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
-(H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, and the MFMA CRC with
-HIP events and reports us / GB/s of input.  Checks results against the host oracles once.
+(H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
+on a video ES the tool writes itself, and the MFMA CRC with HIP events and reports us / GB/s of input.
+Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
 """
@@ -13,7 +14,8 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import aes, codecconfig, crc, esindex, hevcconfig, remux, sampleaes, segment, tsdemux
+from hlsjs_p2p_wrapper_amd.ops import (aes, captions, codecconfig, crc, esindex, hevcconfig, remux, sampleaes, segment,
+                                       tsdemux)
 
 
 def timed(fn, iters):
@@ -73,6 +75,38 @@ def protect_es(es, es_offs, info, pes, nal, sinfo, aframes, key, iv):
                     blocks += chain(q + hdr + 16 + 16 * np.arange((ln - hdr - 16) // 16))
                 q += ln
     return blocks
+
+
+def caption_batch_inputs(offs, lens, size, dev, n_au=120, seed=5):
+    """A demuxed batch written by hand for the caption row: per segment ``n_au`` access units of an
+    AUD, one caption SEI of 20 triples and a slice of random bytes free of start codes, sized to the
+    shortest segment; the demux tables filled by hand.  ``(DemuxResult, caps, host DemuxResult of
+    segment 0)``."""
+    I = tsdemux.INFO
+    B, body = len(offs), (min(lens) - 256) // n_au
+    tri = b"".join(bytes([0xFC | (t & 1), 0x20 + t, 0x40 + t]) for t in range(20))
+    payload = b"\xb5\x00\x31GA94\x03" + bytes([0x40 | 20, 0xFF]) + tri + b"\xff"
+    head = b"\x00\x00\x00\x01\x09\xf0\x00\x00\x01\x06\x04" + bytes([len(payload)]) + payload + b"\x80\x00\x00\x01\x41"
+    units = np.random.default_rng(seed).integers(1, 256, (n_au, body), dtype=np.uint8)
+    units[:, :len(head)] = np.frombuffer(head, np.uint8)
+    ves = units.reshape(-1)
+    max_pes = 256
+    info = np.zeros((B, tsdemux.INFO_WORDS), np.int64)
+    info[:, I["video_bytes"]] = info[:, I["audio_es_offset"]] = info[:, I["id3_es_offset"]] = len(ves)
+    info[:, I["payload_bytes"]] = len(ves)
+    info[:, I["n_video_pes"]], info[:, I["video_type"]] = n_au, 0x1B
+    pes = np.full((B, 3, max_pes, 3), -1, np.int64)
+    a = np.arange(n_au)
+    pes[:, 0, :n_au, 0], pes[:, 0, :n_au, 2] = a * body, 90000 + 3000 * a
+    pes[:, 0, :n_au, 1] = 90000 + 3000 * (a ^ 1) + 6000  # pairs of access units swap their presentation order
+    es = np.zeros(size, np.uint8)
+    for o in offs:
+        es[o:o + len(ves)] = ves
+    dres = tsdemux.DemuxResult(torch.from_numpy(info).to(dev), torch.from_numpy(pes).to(dev),
+                               torch.from_numpy(es).to(dev), np.asarray(offs, np.int64))
+    hres = tsdemux.DemuxResult(torch.from_numpy(info[:1].copy()), torch.from_numpy(pes[:1].copy()),
+                               torch.from_numpy(np.concatenate([ves, np.zeros(256, np.uint8)])), np.zeros(1, np.int64))
+    return dres, [len(ves)] * B, hres
 
 
 def main():
@@ -181,6 +215,17 @@ def main():
         torch.equal(rs.es[o0:o0 + len(ref)].cpu(), hs.es[:len(ref)]), "sampleaes mismatch"
     if int(sa.sainfo[0, 2]) == 0:  # no ciphertext looked like emulation prevention: the clear ES is back
         assert torch.equal(rs.es[o0:o0 + len(ref)], r.es[o0:o0 + len(ref)]), "sampleaes does not invert the packager"
+    # the caption extraction (scan + pack) on a batch of the tool's own: 120 caption SEI per segment,
+    # indexed here; the ES is only read, so the call repeats as it is
+    cr, ccaps, hcr = caption_batch_inputs(offs, lens, src.numel(), dev)
+    cix = esindex.index_batch(cr, ccaps)
+    cc = captions.caption_batch(cr, cix, ccaps)
+    res["captions_us"] = round(timed(lambda: captions.caption_batch(cr, cix, ccaps), args.iters), 1)
+    res["captions_samples"] = int(cc.ccinfo[:, captions.CCINFO["n_samples"]].sum())
+    assert res["captions_samples"] == 120 * args.segs and not int(cc.ccinfo[:, 0].sum()), "captions sample count"
+    hcc = captions.caption_batch(hcr, esindex.index_batch(hcr, ccaps[:1]), ccaps[:1])
+    assert all(torch.equal(getattr(cc, k)[0].cpu(), getattr(hcc, k)[0])
+               for k in ("ccinfo", "ccsamples", "ccpts", "ccbytes", "cc608")), "captions mismatch"
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
