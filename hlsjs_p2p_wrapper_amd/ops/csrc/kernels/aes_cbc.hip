@@ -41,8 +41,6 @@ constexpr int kAesThreads = kAesImageThreads;
 constexpr int kAesWgPerCu = 1;
 constexpr int kBlk = 4;  // blocks per lane per chunk (chunk = 64 * kBlk blocks): independent chains
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef unsigned int v4u __attribute__((ext_vector_type(4)));
 constexpr uint32_t kOutOfRange = 0x80000000u;  // a buffer offset past every segment (reads 0)
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));

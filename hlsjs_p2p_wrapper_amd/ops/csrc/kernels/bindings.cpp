@@ -1,6 +1,8 @@
 // torch binding module `_C`: argument checking + current-HIP-stream launch of the gfx950
 // kernels, as pybind functions and as dispatcher ops (torch.ops.hlsp2p.*).  Host-only
 // translation unit; kernels live in *.hip objects.
+#include <functional>
+#include <initializer_list>
 #include <type_traits>
 
 #include "host_util.h"
@@ -28,6 +30,19 @@ T* check(const Tensor& t, const char* name, int64_t min_numel = 0) {
 }
 
 hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
+
+// The checks every op on a demuxed batch (es_batch below) makes of the tensors it names.
+void same_device(const Tensor& first, std::initializer_list<std::reference_wrapper<const Tensor>> rest) {
+  for (const Tensor& t : rest) TORCH_CHECK(first.device() == t.device(), "tensors on different devices");
+}
+struct NamedTensor {
+  const Tensor& t;
+  const char* name;
+};
+void aligned16(std::initializer_list<NamedTensor> ts) {
+  for (const NamedTensor& n : ts)
+    TORCH_CHECK((reinterpret_cast<uintptr_t>(n.t.data_ptr()) & 15) == 0, n.name, " must be 16-byte aligned");
+}
 
 void aes128_cbc_decrypt(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor blk_prefix,
                         Tensor chunk_prefix, Tensor drk, Tensor iv, Tensor td0, Tensor isb, Tensor out_len,
@@ -144,8 +159,8 @@ void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t 
   a.b = es_batch(es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [&] {
     a.scratch = check<int32_t>(scratch, "scratch", es_::index_scratch(total_tiles, es_off.numel(), max_nal).end);
   });
-  TORCH_CHECK(es.device() == sinfo.device(), "tensors on different devices");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0, "es must be 16-byte aligned");
+  same_device(es, {sinfo});
+  aligned16({{es, "es"}});
   hip_ok(D::launch_es_index(a), "es_index launch");
 }
 
@@ -167,10 +182,8 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
             check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
       .out = check<uint8_t>(out, "out"),
       .out_off = check<int64_t>(out_off, "out_off", B)};
-  TORCH_CHECK(es.device() == out.device() && es.device() == rinfo.device(), "tensors on different devices");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(out.data_ptr()) & 15) == 0,
-              "es / out must be 16-byte aligned");
+  same_device(es, {out, rinfo});
+  aligned16({{es, "es"}, {out, "out"}});
   TORCH_CHECK(es.data_ptr() != out.data_ptr(), "remux cannot run in place");
   hip_ok(D::launch_remux(a), "remux launch");
 }
@@ -187,12 +200,8 @@ void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes,
       .max_ps = max_ps,
       .ps = check<uint8_t>(ps, "ps", es_::ps_bytes(B, max_ps)),
       .cinfo = check<int32_t>(cinfo, "cinfo", B * es_::kCinfoWords)};
-  TORCH_CHECK(es.device() == ps.device() && es.device() == cinfo.device() && es.device() == nal.device(),
-              "tensors on different devices");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(ps.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(nal.data_ptr()) & 15) == 0,
-              "es / ps / nal must be 16-byte aligned");
+  same_device(es, {ps, cinfo, nal});
+  aligned16({{es, "es"}, {ps, "ps"}, {nal, "nal"}});
   hip_ok(D::launch_codec_config(a), "codec_config launch");
 }
 
@@ -208,14 +217,8 @@ void hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, 
       .max_ps = max_ps,
       .hps = check<uint8_t>(hps, "hps", es_::hps_bytes(B, max_ps)),
       .hinfo = check<int32_t>(hinfo, "hinfo", B * es_::kHinfoWords)};
-  TORCH_CHECK(es.device() == hps.device() && es.device() == hinfo.device() && es.device() == nal.device() &&
-                  es.device() == es_off.device() && es.device() == cap.device() && es.device() == info.device() &&
-                  es.device() == pes.device() && es.device() == sinfo.device(),
-              "tensors on different devices");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(hps.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(nal.data_ptr()) & 15) == 0,
-              "es / hps / nal must be 16-byte aligned");
+  same_device(es, {hps, hinfo, nal, es_off, cap, info, pes, sinfo});
+  aligned16({{es, "es"}, {hps, "hps"}, {nal, "nal"}});
   hip_ok(D::launch_hevc_config(a), "hevc_config launch");
 }
 
@@ -237,15 +240,8 @@ void sample_aes_decrypt(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tenso
       .td = check<uint32_t>(td, "td", 256),
       .isb = check<uint8_t>(isb, "isb", 256),
       .sainfo = check<int64_t>(sainfo, "sainfo", B * es_::kSaWords)};
-  TORCH_CHECK(es.device() == nal.device() && es.device() == sainfo.device() && es.device() == es_off.device() &&
-                  es.device() == cap.device() && es.device() == info.device() && es.device() == pes.device() &&
-                  es.device() == sinfo.device() && es.device() == au.device() && es.device() == aframes.device() &&
-                  es.device() == round_keys.device() && es.device() == iv.device() && es.device() == enable.device() &&
-                  es.device() == td.device() && es.device() == isb.device(),
-              "tensors on different devices");
-  TORCH_CHECK((reinterpret_cast<uintptr_t>(es.data_ptr()) & 15) == 0 &&
-                  (reinterpret_cast<uintptr_t>(iv.data_ptr()) & 15) == 0,
-              "es / iv must be 16-byte aligned");
+  same_device(es, {nal, sainfo, es_off, cap, info, pes, sinfo, au, aframes, round_keys, iv, enable, td, isb});
+  aligned16({{es, "es"}, {iv, "iv"}});
   hip_ok(D::launch_sample_aes(a), "sample_aes_decrypt launch");
 }
 
@@ -270,12 +266,10 @@ void cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, i
             check<uint8_t>(ccbytes, "ccbytes", B * max_cc * es_::kCcSlotBytes),
             check<uint8_t>(cc608, "cc608", B * max_cc * 2 * es_::kCcFieldBytes),
             check<int64_t>(ccinfo, "ccinfo", B * es_::kCcInfoWords)}};
-  for (const Tensor* t : {&es_off, &cap, &info, &pes, &nal, &au, &aframes, &sinfo, &enable, &scratch, &ccsamples, &ccpts,
-                          &ccbytes, &cc608, &ccinfo})
-    TORCH_CHECK(es.device() == t->device(), "tensors on different devices");
-  for (const Tensor* t : {&es, &nal, &scratch, &ccsamples, &ccbytes, &cc608})
-    TORCH_CHECK((reinterpret_cast<uintptr_t>(t->data_ptr()) & 15) == 0,
-                "es / nal / scratch / ccsamples / ccbytes / cc608 must be 16-byte aligned");
+  same_device(es, {es_off, cap, info, pes, nal, au, aframes, sinfo, enable, scratch, ccsamples, ccpts, ccbytes, cc608,
+                   ccinfo});
+  aligned16({{es, "es"}, {nal, "nal"}, {scratch, "scratch"}, {ccsamples, "ccsamples"}, {ccbytes, "ccbytes"},
+             {cc608, "cc608"}});
   hip_ok(D::launch_cc_extract(a), "cc_extract launch");
 }
 

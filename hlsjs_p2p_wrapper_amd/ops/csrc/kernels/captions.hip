@@ -12,22 +12,21 @@
 //      64 NAL rows, a lane per row (one 16-byte load), runs the candidate test and comes to the same
 //      ballot; the chunk's candidates go to the four waves in turn, and a wave takes its own one by
 //      one with no workgroup barrier (the next candidate's load in flight meanwhile): ps_copy_lane
-//      brings the stored bytes (at most
-//      kCcNalBytes, 16 per lane) through a buffer range that ends with the ES tensor into the
-//      wave's 1 KiB of LDS, a ballot / popcount prefix compacts the RBSP into a second KiB, every
-//      lane runs es::cc_find over it (wave-uniform, LDS broadcast reads), and on a match six lanes
-//      store the sample's 96-byte slot into scratch.  Every row k < R gets its flag word.
+//      brings the stored bytes (at most kCcNalBytes, 16 per lane) through the segment's buffer
+//      resource (es_dev.h es_segment_rsrc: it ends with the ES tensor) into the wave's 1 KiB of
+//      LDS, a ballot / popcount prefix compacts the RBSP into a second KiB, every lane runs
+//      es::cc_find over it (wave-uniform, LDS broadcast reads), and on a match six lanes store the
+//      sample's 96-byte slot into scratch.  Every row k < R gets its flag word.
 //   2. cc_pack_kernel — one workgroup per segment.  A workgroup scan of the hit flags in rounds of
 //      256 rows with a carry ranks the samples; the lane of a hit row moves its slot, splits the
 //      608 pairs by field and writes its row; the pts go to LDS and, behind a barrier, a lane per
 //      sample counts its presentation rank; then the fills beyond the recorded count and ccinfo.
 // A disabled segment, another codec and a chunk past R leave cc_scan_kernel in front of any work;
 // cc_pack_kernel computes the same R and reads no flag the scan did not write.
+// The batch view and the head of both kernels (clamped cap, R rows, m access units) are es_dev.h.
 // The candidate test, the emulation-prevention predicate, cc_find and the 608 pair rule are
 // shared/grammar.hpp (namespace es), the same functions runtime/captions.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 #include "ps_dev.h"
 
 namespace hlsp2p {
@@ -49,36 +48,6 @@ __device__ __forceinline__ void cc_wave_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// The device side of launch.h's EsBatch: what both kernels read, passed by value.
-struct EsBatchView {
-  const uint8_t* es;
-  int64_t es_numel;
-  const int64_t *es_off, *cap, *info, *pes;
-  int64_t max_pes, max_nal;
-  const int32_t *nal, *au, *aframes;
-  const int64_t* sinfo;
-};
-
-// What both kernels take from a segment's rows: R NAL rows, m access units, the codec.
-struct CcSegment {
-  es::Segment sg;
-  es::IndexTables<const int32_t, const int64_t> ix;
-  int R, m, cap;
-  bool hevc;
-};
-__device__ __forceinline__ CcSegment cc_segment(const EsBatchView& b, int seg) {
-  CcSegment c;
-  c.sg = es::segment_at(b.es, b.es_off, b.cap, b.info, b.pes, b.max_pes, b.max_nal, seg);
-  c.sg.cap = clamp(c.sg.cap, 0, 0x7fffffff);
-  c.ix = es::index_tables_at<const int32_t, const int64_t>({b.nal, b.au, b.aframes, b.sinfo}, c.sg, seg);
-  const es::VideoSpan video = es::video_span(c.sg);
-  c.R = static_cast<int>(es::video_rows(video, c.ix.sinfo[es::kNumNal], b.max_nal));
-  c.m = static_cast<int>(es::video_rows(video, c.ix.sinfo[es::kNumAu], b.max_pes));
-  c.cap = static_cast<int>(c.sg.cap);
-  c.hevc = video.hevc;
-  return c;
-}
-
 __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, const uint8_t* __restrict__ enable,
                                                              int32_t* __restrict__ flag_all,
                                                              uint8_t* __restrict__ hit_all) {
@@ -87,10 +56,12 @@ __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, cons
   const int seg = blockIdx.y, chunk = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (!enable[seg]) return;
-  const CcSegment c = cc_segment(b, seg);
-  if (chunk * kCcChunkRows >= c.R) return;
-  const int h = es::nal_header_bytes(c.hevc);
-  const ps_v4i* rows = reinterpret_cast<const ps_v4i*>(c.ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
+  const auto c = es_segment(b, seg);
+  const int R = static_cast<int>(c.R), m = static_cast<int>(c.m);
+  const bool hevc = c.video.hevc;
+  if (chunk * kCcChunkRows >= R) return;
+  const int h = es::nal_header_bytes(hevc);
+  const v4i* rows = reinterpret_cast<const v4i*>(c.ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
   int32_t* flag_seg = flag_all + static_cast<int64_t>(seg) * b.max_nal;
   uint8_t* hit_seg = hit_all + static_cast<int64_t>(seg) * b.max_nal * es::kCcSlotBytes;
 
@@ -98,16 +69,16 @@ __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, cons
   const int k = chunk * kCcChunkRows + lane;
   int off = 0, n = 0;
   bool cand = false;
-  if (k < c.R) {
-    const ps_v4i row = rows[k];
+  if (k < R) {
+    const v4i row = rows[k];
     off = static_cast<int>(clamp(row[es::kNalOffset], 0, c.cap));
     n = static_cast<int>(clamp(row[es::kNalLength], 0, c.cap - off));
-    cand = es::cc_nal_candidate(c.hevc, row[es::kNalType], row[es::kNalAu], c.m, n);
+    cand = es::cc_nal_candidate(hevc, row[es::kNalType], row[es::kNalAu], m, n);
   }
   int flag = cand ? es::kCfCandidate | (n > es::kCcNalBytes ? es::kCfClipped : 0) : 0;
 
   // ---- b. the chunk's candidates go to the four waves in turn; a wave takes its own one by one
-  const int64_t base = b.es_off[seg];
+  const __amdgpu_buffer_rsrc_t rsrc = es_segment_rsrc(b, seg);
   uint8_t* raw = s_raw[wave];
   uint8_t* U = s_rbsp[wave];
   const unsigned long long all = __ballot(cand);
@@ -118,19 +89,19 @@ __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, cons
   auto fetch = [&](int at, int& len) {
     const int c_off = __builtin_amdgcn_readfirstlane(__shfl(off, at));
     len = __builtin_amdgcn_readfirstlane(__shfl(n, at));
-    return ps_copy_lane(b.es + base, b.es_numel - base, c_off, len, es::kCcNalBytes, lane);
+    return ps_copy_lane(rsrc, c_off, len, es::kCcNalBytes, lane);
   };
   int next_n = 0;
-  ps_v4u next = {0, 0, 0, 0};
+  v4u next = {0, 0, 0, 0};
   if (todo) next = fetch(__builtin_ctzll(todo), next_n);
   while (todo) {
     const int from = __builtin_ctzll(todo);
     todo &= todo - 1;
-    const ps_v4u mine = next;
+    const v4u mine = next;
     const int c_n = next_n;
     if (todo) next = fetch(__builtin_ctzll(todo), next_n);
     const int stored = c_n < es::kCcNalBytes ? c_n : es::kCcNalBytes;
-    *reinterpret_cast<ps_v4u*>(raw + lane * 16) = mine;
+    *reinterpret_cast<v4u*>(raw + lane * 16) = mine;
     cc_wave_sync();
     int u = 0;
     for (int jb = 0; jb < stored; jb += 64) {
@@ -152,7 +123,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, cons
       const int size = 2 + 3 * hit.count;
       if (lane == from) flag |= es::kCfHit | (size << es::kCfSizeShift);
       if (lane < es::kCcSlotBytes / 16) {
-        ps_v4u q = {0, 0, 0, 0};
+        v4u q = {0, 0, 0, 0};
 #pragma unroll
         for (int d = 0; d < 4; ++d) {
           uint32_t w = 0;
@@ -164,13 +135,13 @@ __global__ __launch_bounds__(kCcThreads) void cc_scan_kernel(EsBatchView b, cons
           q[d] = w;
         }
         const int64_t row_k = chunk * kCcChunkRows + from;
-        *reinterpret_cast<ps_v4u*>(hit_seg + row_k * es::kCcSlotBytes + lane * 16) = q;
+        *reinterpret_cast<v4u*>(hit_seg + row_k * es::kCcSlotBytes + lane * 16) = q;
       }
     }
     cc_wave_sync();  // raw and U are free for the next candidate
   }
   // a candidate's flag comes from the wave that walked it, every other row's from wave 0
-  if (k < c.R && (mine || (!cand && wave == 0))) flag_seg[k] = flag;
+  if (k < R && (mine || (!cand && wave == 0))) flag_seg[k] = flag;
 }
 
 __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, const uint8_t* __restrict__ enable,
@@ -185,11 +156,11 @@ __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, cons
   __shared__ int s_wave[kCcWaves];
   __shared__ int s_tot[5];  // candidates, clipped ones, triples, field 1 pairs, field 2 pairs
   const int seg = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const bool on = enable[seg] != 0;
-  const CcSegment c = cc_segment(b, seg);
-  const int R = on ? c.R : 0;
-  const ps_v4i* rows = reinterpret_cast<const ps_v4i*>(c.ix.nal);
+  const auto c = es_segment(b, seg);
+  const int R = on ? static_cast<int>(c.R) : 0;
+  const v4i* rows = reinterpret_cast<const v4i*>(c.ix.nal);
   const int64_t* vp = es::pes_rows(c.sg).video;
   const int32_t* flag_seg = flag_all + static_cast<int64_t>(seg) * b.max_nal;
   const uint8_t* hit_seg = hit_all + static_cast<int64_t>(seg) * b.max_nal * es::kCcSlotBytes;
@@ -212,35 +183,28 @@ __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, cons
     const bool hit = (f & es::kCfHit) != 0;
     n_cand += (f & es::kCfCandidate) ? 1 : 0;
     n_clip += (f & es::kCfClipped) ? 1 : 0;
-    const unsigned long long mk = __ballot(hit);
-    if (lane == 0) s_wave[wave] = __popcll(mk);
-    __syncthreads();
-    int before = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < kCcWaves; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    const int rank = before + __popcll(mk & ((1ull << lane) - 1ull));
+    const int inc = __popcll(__ballot(hit) & (~0ull >> (63 - lane)));  // hits up to this lane's
+    const WgPrefix<int> p = wg_exclusive_prefix<kCcWaves>(inc, hit ? 1 : 0, s_wave);
+    const int rank = carry + p.before;
     if (hit && rank < max_cc) {
       int size = (f >> es::kCfSizeShift) & 0xff;
       size = size < 2 ? 2 : size > 2 + 3 * es::kCcMaxTriples ? 2 + 3 * es::kCcMaxTriples : size;
       const int count = (size - 2) / 3;
       const int au = rows[k][es::kNalAu];
       const int64_t pts = es::pes_at(vp, clamp(au, 0, b.max_pes - 1), ts::kPesPts);
-      const ps_v4u* src = reinterpret_cast<const ps_v4u*>(hit_seg + static_cast<int64_t>(k) * es::kCcSlotBytes);
-      ps_v4u* dst = reinterpret_cast<ps_v4u*>(bytes + static_cast<int64_t>(rank) * es::kCcSlotBytes);
+      const v4u* src = reinterpret_cast<const v4u*>(hit_seg + static_cast<int64_t>(k) * es::kCcSlotBytes);
+      v4u* dst = reinterpret_cast<v4u*>(bytes + static_cast<int64_t>(rank) * es::kCcSlotBytes);
       uint32_t w[es::kCcSlotBytes / 4];
 #pragma unroll
       for (int i = 0; i < es::kCcSlotBytes / 16; ++i) {
-        const ps_v4u v = src[i];
+        const v4u v = src[i];
         dst[i] = v;
         w[4 * i] = v.x, w[4 * i + 1] = v.y, w[4 * i + 2] = v.z, w[4 * i + 3] = v.w;
       }
       uint16_t* f608 = reinterpret_cast<uint16_t*>(cc608 + static_cast<int64_t>(rank) * 2 * es::kCcFieldBytes);
       int p0 = 0, p1 = 0;
 #pragma unroll
-      for (int i = 0; i < 2 * es::kCcFieldBytes / 16; ++i) reinterpret_cast<ps_v4u*>(f608)[i] = ps_v4u{0, 0, 0, 0};
+      for (int i = 0; i < 2 * es::kCcFieldBytes / 16; ++i) reinterpret_cast<v4u*>(f608)[i] = v4u{0, 0, 0, 0};
 #pragma unroll
       for (int t = 0; t < es::kCcMaxTriples; ++t) {
         if (t < count) {
@@ -270,7 +234,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, cons
       n_f1 += p0;
       n_f2 += p1;
     }
-    carry += total;
+    carry += p.total;
     __syncthreads();  // s_wave is free again
   }
   if (n_cand) atomicAdd(&s_tot[0], n_cand);
@@ -293,14 +257,14 @@ __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, cons
   }
 
   // ---- c. the rows beyond the recorded count, 16 bytes per store
-  const ps_v4i minus = {-1, -1, -1, -1};
-  const ps_v4u zero = {0, 0, 0, 0};
-  for (int v = n_rec * 2 + tid; v < max_cc * 2; v += kCcThreads) reinterpret_cast<ps_v4i*>(samples)[v] = minus;
+  const v4i minus = {-1, -1, -1, -1};
+  const v4u zero = {0, 0, 0, 0};
+  for (int v = n_rec * 2 + tid; v < max_cc * 2; v += kCcThreads) reinterpret_cast<v4i*>(samples)[v] = minus;
   for (int v = n_rec + tid; v < max_cc; v += kCcThreads) pts_out[v] = -1;
   for (int v = n_rec * (es::kCcSlotBytes / 16) + tid; v < max_cc * (es::kCcSlotBytes / 16); v += kCcThreads)
-    reinterpret_cast<ps_v4u*>(bytes)[v] = zero;
+    reinterpret_cast<v4u*>(bytes)[v] = zero;
   for (int v = n_rec * (es::kCcFieldBytes / 8) + tid; v < max_cc * (es::kCcFieldBytes / 8); v += kCcThreads)
-    reinterpret_cast<ps_v4u*>(cc608)[v] = zero;
+    reinterpret_cast<v4u*>(cc608)[v] = zero;
 
   // ---- d. the info row
   if (tid == 0) {
@@ -325,8 +289,7 @@ __global__ __launch_bounds__(kCcThreads) void cc_pack_kernel(EsBatchView b, cons
 hipError_t launch_cc_extract(const CcExtractArgs& a) {
   const EsBatch& b = a.b;
   if (b.nseg <= 0) return hipSuccess;
-  const EsBatchView view{b.es, b.es_numel, b.es_off, b.cap, b.info, b.pes, b.max_pes, b.max_nal,
-                         b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo};
+  const EsBatchView view = es_batch_view(b);
   const es::CcScratch sc = es::cc_scratch(b.nseg, b.max_nal);
   int32_t* flag = a.scratch + sc.flag;
   uint8_t* hit = reinterpret_cast<uint8_t*>(a.scratch + sc.hit);

@@ -11,9 +11,9 @@
 //                   types 7 and 8 with a length, the lowest row of each through LDS; the round
 //                   loop is workgroup-uniform and ends once both are found.
 //   b. byte copy  — wave 0 the SPS, wave 1 the PPS, a lane per 16 stored bytes: five dwords
-//                   through the segment's buffer resource funnelled to the NAL's alignment
-//                   (v_alignbyte), masked to the stored length, one 16-byte store to ps and, for
-//                   the SPS, one to LDS.
+//                   through the segment's buffer resource (es_dev.h es_segment_rsrc) funnelled to
+//                   the NAL's alignment (common.h load16_unaligned), masked to the stored length,
+//                   one 16-byte store to ps and, for the SPS, one to LDS.
 //   c. unescape   — a lane per SPS byte flags emulation prevention from its two raw
 //                   predecessors in LDS; a ballot and popcount prefix with a carry across waves
 //                   and rounds compacts the RBSP into a second LDS array.
@@ -23,23 +23,15 @@
 // Steps a, b and c are ps_dev.h, shared with hevc_config.hip.
 // No workgroup waits for another one.  The emulation-prevention predicate, sps_parse and the
 // ADTS fields are shared/grammar.hpp (namespace es), the same functions runtime/codec.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 #include "ps_dev.h"
 
 namespace hlsp2p {
 namespace dev {
 
-constexpr int kCcThreads = kPsThreads;
-constexpr int kCcNone = kPsNone;
-
-__global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
-    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
-    const int64_t* __restrict__ cap, const int64_t* __restrict__ info, const int64_t* __restrict__ pes,
-    int64_t max_pes, int64_t max_nal, const int32_t* __restrict__ nal_all, const int32_t* __restrict__ au_all,
-    const int32_t* __restrict__ af_all, const int64_t* __restrict__ sinfo, int max_ps, uint8_t* __restrict__ ps_all,
-    int32_t* __restrict__ cinfo_all) {
+__global__ __launch_bounds__(kPsThreads) void codec_config_kernel(EsBatchView b, int max_ps,
+                                                                  uint8_t* __restrict__ ps_all,
+                                                                  int32_t* __restrict__ cinfo_all) {
   __shared__ __attribute__((aligned(16))) uint8_t s_raw[es::kMaxPsLimit];   // the SPS as stored
   __shared__ __attribute__((aligned(16))) uint8_t s_rbsp[es::kMaxPsLimit];  // ... and without emulation prevention
   __shared__ int s_found[es::kPsRows];
@@ -47,19 +39,17 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
   __shared__ int32_t s_row[es::kCinfoWords];
   const int seg = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
-  sg.cap = clamp(sg.cap, 0, 0x7fffffff);
-  const es::IndexTables<const int32_t, const int64_t> ix =
-      es::index_tables_at<const int32_t, const int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
-  const int cap_es = static_cast<int>(sg.cap);
+  const auto c = es_segment(b, seg);
+  const es::Segment& sg = c.sg;
+  const int cap_es = c.cap;
   const bool avc = sg.info[ts::kVideoType] == ts::kAvc;
-  const int R = avc ? static_cast<int>(es::video_rows(es::video_span(sg), ix.sinfo[es::kNumNal], max_nal)) : 0;
-  if (tid < es::kPsRows) s_found[tid] = kCcNone;
+  const int R = avc ? static_cast<int>(c.R) : 0;
+  if (tid < es::kPsRows) s_found[tid] = kPsNone;
   if (tid < es::kCinfoWords) s_row[tid] = 0;
   __syncthreads();
 
   // ---- a. the first SPS and PPS rows
-  const ps_v4i* rows = reinterpret_cast<const ps_v4i*>(ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
+  const v4i* rows = reinterpret_cast<const v4i*>(c.ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
   const int types[es::kPsRows] = {7, 8};
   ps_find_rows(rows, R, types, s_found);
   const int found[es::kPsRows] = {s_found[es::kPsSps], s_found[es::kPsPps]};
@@ -68,32 +58,31 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
   int len[es::kPsRows] = {0, 0}, src[es::kPsRows] = {0, 0};
 #pragma unroll
   for (int w = 0; w < es::kPsRows; ++w) {
-    if (found[w] == kCcNone) continue;
-    const ps_v4i row = rows[found[w]];
+    if (found[w] == kPsNone) continue;
+    const v4i row = rows[found[w]];
     src[w] = static_cast<int>(clamp(row[es::kNalOffset], 0, cap_es));
     len[w] = static_cast<int>(clamp(row[es::kNalLength], 0, cap_es - src[w]));
   }
   if (wave < es::kPsRows && lane * 16 < max_ps) {
-    const int64_t off = es_off[seg];
-    const ps_v4u q = ps_copy_lane(es + off, es_numel - off, src[wave], len[wave], max_ps, lane);
+    const v4u q = ps_copy_lane(es_segment_rsrc(b, seg), src[wave], len[wave], max_ps, lane);
     uint8_t* dst = ps_all + es::ps_bytes(seg, max_ps) + static_cast<int64_t>(wave) * max_ps;
-    *reinterpret_cast<ps_v4u*>(dst + lane * 16) = q;
-    if (wave == es::kPsSps) *reinterpret_cast<ps_v4u*>(s_raw + lane * 16) = q;
+    *reinterpret_cast<v4u*>(dst + lane * 16) = q;
+    if (wave == es::kPsSps) *reinterpret_cast<v4u*>(s_raw + lane * 16) = q;
   }
   __syncthreads();
 
   // ---- c. the SPS without its header byte and emulation prevention
-  const bool parse = found[es::kPsSps] != kCcNone && len[es::kPsSps] <= max_ps;  // an overflowed SPS is not parsed
+  const bool parse = found[es::kPsSps] != kPsNone && len[es::kPsSps] <= max_ps;  // an overflowed SPS is not parsed
   const int carry = ps_unescape(s_raw, parse ? len[es::kPsSps] : 0, 1, s_rbsp, s_wave);
 
   // ---- d. one lane parses, one of another wave takes the ADTS fields
   if (tid == 0) {
     int32_t status = 0;
     if (!avc) status |= es::kConfigUnsupportedVideo;
-    else status |= (found[es::kPsSps] == kCcNone ? es::kNoSps : 0) | (found[es::kPsPps] == kCcNone ? es::kNoPps : 0);
+    else status |= (found[es::kPsSps] == kPsNone ? es::kNoSps : 0) | (found[es::kPsPps] == kPsNone ? es::kNoPps : 0);
     if (len[es::kPsSps] > max_ps || len[es::kPsPps] > max_ps) status |= es::kPsOverflow;
-    s_row[es::kCSpsNal] = found[es::kPsSps] == kCcNone ? -1 : found[es::kPsSps];
-    s_row[es::kCPpsNal] = found[es::kPsPps] == kCcNone ? -1 : found[es::kPsPps];
+    s_row[es::kCSpsNal] = found[es::kPsSps] == kPsNone ? -1 : found[es::kPsSps];
+    s_row[es::kCPpsNal] = found[es::kPsPps] == kPsNone ? -1 : found[es::kPsPps];
     s_row[es::kCSpsBytes] = len[es::kPsSps];
     s_row[es::kCPpsBytes] = len[es::kPsPps];
     if (parse) {
@@ -116,7 +105,7 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
   } else if (tid == 64) {
     const es::AudioSpan audio = es::audio_span(sg);
     bool usable = false;
-    if (audio.n_adts >= 1 && ix.aframes[es::kApesFrames] >= 1) {
+    if (audio.n_adts >= 1 && c.ix.aframes[es::kApesFrames] >= 1) {
       const es::ByteRange r = es::audio_pes_range(es::pes_rows(sg).audio, 0, audio);
       if (r.start + 7 <= r.end) {
         const es::AdtsConfig c = es::adts_config_at(sg.es + audio.off, r.start);
@@ -137,8 +126,7 @@ __global__ __launch_bounds__(kCcThreads) void codec_config_kernel(
 hipError_t launch_codec_config(const CodecConfigArgs& a) {
   const EsBatch& b = a.b;
   if (b.nseg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(codec_config_kernel, dim3(b.nseg), dim3(kCcThreads), 0, b.stream, b.es, b.es_numel, b.es_off,
-                     b.cap, b.info, b.pes, b.max_pes, b.max_nal, b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo,
+  hipLaunchKernelGGL(codec_config_kernel, dim3(b.nseg), dim3(kPsThreads), 0, b.stream, es_batch_view(b),
                      static_cast<int>(a.max_ps), a.ps, a.cinfo);
   return hipGetLastError();
 }

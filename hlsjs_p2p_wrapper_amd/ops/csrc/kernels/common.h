@@ -49,6 +49,45 @@ __device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t v) {
   return v;
 }
 
+// Exclusive prefix over a workgroup, called by every one of its 64 * kWaves threads (blockDim.x is
+// exactly that, all lanes active): `inc` is the caller's inclusive scan of `own` inside the wave
+// (DPP, ballot / popcount or shuffles).  Lane 63 leaves the wave's total in s_wave, kWaves words
+// of LDS; one barrier stands between that store and the reads.  The barrier that frees s_wave for
+// the next call is the caller's.
+template <typename T>
+struct WgPrefix {
+  T before, total;  // the sum of `own` over the threads in front of this one, and over all
+};
+template <int kWaves, typename T>
+__device__ __forceinline__ WgPrefix<T> wg_exclusive_prefix(T inc, T own, T* s_wave) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 63) s_wave[wave] = inc;
+  __syncthreads();
+  WgPrefix<T> p = {inc - own, 0};
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    if (w < wave) p.before += s_wave[w];
+    p.total += s_wave[w];
+  }
+  return p;
+}
+
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+
+// Bytes [sh, sh + 16) of the five dwords v.x v.y v.z v.w w4, sh in 0..3: four v_alignbyte.
+__device__ __forceinline__ v4u funnel16(v4u v, uint32_t w4, uint32_t sh) {
+  return v4u{__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh),
+             __builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(w4, v.w, sh)};
+}
+// 16 bytes at any byte offset of a buffer resource: the five dwords around them, funnelled; a
+// dword beyond the resource's range reads as zero.
+__device__ __forceinline__ v4u load16_unaligned(__amdgpu_buffer_rsrc_t rsrc, int off) {
+  const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off & ~3, 0, 0);
+  const uint32_t w4 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (off & ~3) + 16, 0, 0);
+  return funnel16(v, w4, static_cast<uint32_t>(off & 3));
+}
+
 // Workgroup copy of `count` elements global -> LDS with every load of the thread issued
 // before its first LDS store (kIters >= ceil(count / nthreads)).  The plain strided loop
 // compiles to load / s_waitcnt vmcnt(0) / ds_write per element: one L2 round trip per

@@ -35,7 +35,6 @@
 namespace hlsp2p {
 namespace dev {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 // 8 waves share one 64 KiB LDS copy of W: 2 workgroups per CU = 4 waves per SIMD, so one

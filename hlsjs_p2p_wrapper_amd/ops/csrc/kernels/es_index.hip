@@ -25,9 +25,7 @@
 // No workgroup waits for another one: the order comes from the launches alone.
 // The codec, NAL-type and ADTS byte rules are shared/grammar.hpp (namespace es), the same
 // functions runtime/es.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -49,11 +47,11 @@ __device__ __forceinline__ uint32_t es_zero_bytes(uint32_t x) {
 }
 
 // Bit j set: a start code begins at byte b + j of the video ES (00 00 01 with the NAL header
-// byte inside the n bytes).  The ES is read through a buffer resource that ends with the ES
-// tensor, so a load can never leave it; bytes at or past n (audio, slack) may take part in
-// the flags, and the limit below drops every position whose header byte is not inside.
+// byte inside the n bytes).  The ES is read through the segment's buffer resource (es_dev.h
+// es_segment_rsrc), which ends with the ES tensor, so a load can never leave it; bytes at or
+// past n (audio, slack) may take part in the flags, and the limit below drops every position
+// whose header byte is not inside.
 __device__ __forceinline__ uint32_t es_match16(__amdgpu_buffer_rsrc_t rsrc, int b, int n) {
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   const int lim = n - 3 - b;  // positions j < lim have b + j + 3 < n
   if (lim <= 0) return 0;
   const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, b, 0, 0);
@@ -81,29 +79,21 @@ struct EsTile {
   __amdgpu_buffer_rsrc_t rsrc;
 };
 
-__device__ __forceinline__ EsTile es_tile(const uint8_t* __restrict__ es, int64_t es_numel,
-                                          const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
-                                          const int64_t* __restrict__ tile_prefix, int nseg,
-                                          const int64_t* __restrict__ info) {
+__device__ __forceinline__ EsTile es_tile(const EsBatchView& b, const int64_t* __restrict__ tile_prefix, int nseg) {
   EsTile t;
   const int64_t gt = blockIdx.x;
   t.seg = find_seg_wave(tile_prefix, nseg, gt);
   t.base = static_cast<int>(gt - tile_prefix[t.seg]) * kEsTile;
-  t.n = static_cast<int>(es_video_len(info + static_cast<int64_t>(t.seg) * ts::kInfoWords, cap[t.seg]));
-  const int64_t off = es_off[t.seg];
-  const int64_t avail = es_numel - off;
-  t.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(es + off), 0,
-                                             static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+  t.n = static_cast<int>(es_video_len(b.info + static_cast<int64_t>(t.seg) * ts::kInfoWords, b.cap[t.seg]));
+  t.rsrc = es_segment_rsrc(b, t.seg);
   return t;
 }
 
 // ---------------------------------------------------------------- 1. count
-__global__ __launch_bounds__(kEsThreads) void es_count_kernel(
-    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
-    const int64_t* __restrict__ cap, const int64_t* __restrict__ tile_prefix, int nseg,
-    const int64_t* __restrict__ info, int32_t* __restrict__ tile_cnt) {
+__global__ __launch_bounds__(kEsThreads) void es_count_kernel(EsBatchView b, const int64_t* __restrict__ tile_prefix,
+                                                              int nseg, int32_t* __restrict__ tile_cnt) {
   __shared__ uint32_t s_cnt[kEsThreads / 64];
-  const EsTile t = es_tile(es, es_numel, es_off, cap, tile_prefix, nseg, info);
+  const EsTile t = es_tile(b, tile_prefix, nseg);
   const int tid = threadIdx.x;
   uint32_t c = 0;
   if (t.base < t.n) {
@@ -144,13 +134,12 @@ __global__ __launch_bounds__(64) void es_prefix_kernel(const int64_t* __restrict
 }
 
 // ---------------------------------------------------------------- 3. emit
-__global__ __launch_bounds__(kEsThreads) void es_emit_kernel(
-    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
-    const int64_t* __restrict__ cap, const int64_t* __restrict__ tile_prefix, int nseg,
-    const int64_t* __restrict__ info, const int32_t* __restrict__ tile_pre, int64_t max_nal,
-    int32_t* __restrict__ pos) {
+__global__ __launch_bounds__(kEsThreads) void es_emit_kernel(EsBatchView b, const int64_t* __restrict__ tile_prefix,
+                                                             int nseg, const int32_t* __restrict__ tile_pre,
+                                                             int32_t* __restrict__ pos) {
   __shared__ uint32_t s_w[kEsIters][kEsThreads / 64];
-  const EsTile t = es_tile(es, es_numel, es_off, cap, tile_prefix, nseg, info);
+  const int64_t max_nal = b.max_nal;
+  const EsTile t = es_tile(b, tile_prefix, nseg);
   if (t.base >= t.n) return;  // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   uint32_t m[kEsIters], inc[kEsIters];
@@ -187,15 +176,16 @@ __device__ __forceinline__ int es_first_nal_at(const int32_t* __restrict__ pos, 
   return lo;
 }
 
-__global__ __launch_bounds__(kEsThreads) void es_finish_kernel(
-    const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
-    const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
-    const int32_t* __restrict__ pos_all, int32_t* __restrict__ nal_all, int32_t* __restrict__ au_all,
-    int32_t* __restrict__ af_all, int64_t* __restrict__ sinfo) {
+using EsIndexView = EsBatchViewOf<int32_t, int64_t>;  // this kernel writes the four tables
+
+// The view serves for its pointers only: no es_segment here (see the two comments below).
+__global__ __launch_bounds__(kEsThreads) void es_finish_kernel(EsIndexView b, const int32_t* __restrict__ pos_all) {
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
-  const es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);  // cap as the wrapper checked it
-  const es::IndexTables<int32_t, int64_t> tb = es::index_tables_at<int32_t, int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
+  const int64_t max_pes = b.max_pes, max_nal = b.max_nal;
+  // cap as the wrapper checked it
+  const es::Segment sg = es::segment_at(b.es, b.es_off, b.cap, b.info, b.pes, max_pes, max_nal, seg);
+  const es::IndexTables<int32_t, int64_t> tb = es::index_tables_at(b.ix, sg, seg);
   int64_t* si = tb.sinfo;
   const uint8_t* V = sg.es;
   const es::VideoSpan video = es::video_span(sg);
@@ -314,10 +304,10 @@ hipError_t launch_es_index(const EsIndexArgs& args) {
   int32_t* tile_pre = args.scratch + part.tile_pre;
   int32_t* pos = args.scratch + part.pos;
   const dim3 tiles(static_cast<unsigned>(a.total_tiles));
+  const EsBatchView view = es_batch_view(a);
   hipError_t e = hipSuccess;
   if (a.total_tiles > 0) {
-    hipLaunchKernelGGL(es_count_kernel, tiles, dim3(kEsThreads), 0, a.stream, a.es, a.es_numel, a.es_off, a.cap,
-                       a.tile_prefix, a.nseg, a.info, tile_cnt);
+    hipLaunchKernelGGL(es_count_kernel, tiles, dim3(kEsThreads), 0, a.stream, view, a.tile_prefix, a.nseg, tile_cnt);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
@@ -326,13 +316,13 @@ hipError_t launch_es_index(const EsIndexArgs& args) {
   e = hipGetLastError();
   if (e != hipSuccess) return e;
   if (a.total_tiles > 0) {
-    hipLaunchKernelGGL(es_emit_kernel, tiles, dim3(kEsThreads), 0, a.stream, a.es, a.es_numel, a.es_off, a.cap,
-                       a.tile_prefix, a.nseg, a.info, tile_pre, a.max_nal, pos);
+    hipLaunchKernelGGL(es_emit_kernel, tiles, dim3(kEsThreads), 0, a.stream, view, a.tile_prefix, a.nseg, tile_pre,
+                       pos);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(es_finish_kernel, dim3(a.nseg), dim3(kEsThreads), 0, a.stream, a.es, a.es_off, a.cap, a.info,
-                     a.pes, a.max_pes, a.max_nal, pos, a.ix.nal, a.ix.au, a.ix.aframes, a.ix.sinfo);
+  hipLaunchKernelGGL(es_finish_kernel, dim3(a.nseg), dim3(kEsThreads), 0, a.stream,
+                     es_batch_view<int32_t, int64_t>(a), pos);
   return hipGetLastError();
 }
 

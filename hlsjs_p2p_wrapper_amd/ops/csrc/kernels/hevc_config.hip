@@ -17,9 +17,7 @@
 // Steps a, b and c are ps_dev.h, shared with codec_config.hip.  No workgroup waits for another
 // one.  The emulation-prevention predicate and hevc_sps_parse are shared/grammar.hpp (namespace
 // es), the same functions runtime/hevc.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 #include "ps_dev.h"
 
 namespace hlsp2p {
@@ -28,12 +26,9 @@ namespace dev {
 static_assert(es::kHpsRows <= kPsWaves, "a wave per parameter set");
 static_assert(es::kHinfoWords <= kPsThreads, "a lane per hinfo word");
 
-__global__ __launch_bounds__(kPsThreads) void hevc_config_kernel(
-    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
-    const int64_t* __restrict__ cap, const int64_t* __restrict__ info, const int64_t* __restrict__ pes,
-    int64_t max_pes, int64_t max_nal, const int32_t* __restrict__ nal_all, const int32_t* __restrict__ au_all,
-    const int32_t* __restrict__ af_all, const int64_t* __restrict__ sinfo, int max_ps, uint8_t* __restrict__ hps_all,
-    int32_t* __restrict__ hinfo_all) {
+__global__ __launch_bounds__(kPsThreads) void hevc_config_kernel(EsBatchView b, int max_ps,
+                                                                 uint8_t* __restrict__ hps_all,
+                                                                 int32_t* __restrict__ hinfo_all) {
   __shared__ __attribute__((aligned(16))) uint8_t s_raw[es::kMaxPsLimit];   // the SPS as stored
   __shared__ __attribute__((aligned(16))) uint8_t s_rbsp[es::kMaxPsLimit];  // ... and without emulation prevention
   __shared__ int s_found[es::kHpsRows];
@@ -41,30 +36,28 @@ __global__ __launch_bounds__(kPsThreads) void hevc_config_kernel(
   __shared__ int32_t s_row[es::kHinfoWords];
   const int seg = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
-  sg.cap = clamp(sg.cap, 0, 0x7fffffff);
+  const es::Segment sg = es_segment_clamped(b, seg);
   uint8_t* hps = hps_all + es::hps_bytes(seg, max_ps);
   int32_t* hinfo = hinfo_all + static_cast<int64_t>(seg) * es::kHinfoWords;
   const bool copies = wave < es::kHpsRows && lane * 16 < max_ps;  // this lane holds 16 bytes of hps
 
   // ---- 0. any other codec (workgroup-uniform, in front of the first barrier)
   if (!es::is_hevc(sg.info[ts::kVideoType])) {
-    if (copies) *reinterpret_cast<ps_v4u*>(hps + static_cast<int64_t>(wave) * max_ps + lane * 16) = ps_v4u{0, 0, 0, 0};
+    if (copies) *reinterpret_cast<v4u*>(hps + static_cast<int64_t>(wave) * max_ps + lane * 16) = v4u{0, 0, 0, 0};
     if (tid < es::kHinfoWords)
       hinfo[tid] = tid == es::kHStatus ? static_cast<int32_t>(es::kHNotHevc)
                    : tid == es::kHVpsNal || tid == es::kHSpsNal || tid == es::kHPpsNal ? -1 : 0;
     return;
   }
-  const es::IndexTables<const int32_t, const int64_t> ix =
-      es::index_tables_at<const int32_t, const int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
-  const int cap_es = static_cast<int>(sg.cap);
-  const int R = static_cast<int>(es::video_rows(es::video_span(sg), ix.sinfo[es::kNumNal], max_nal));
+  const auto c = es_segment(b, seg);
+  const int cap_es = c.cap;
+  const int R = static_cast<int>(c.R);
   if (tid < es::kHpsRows) s_found[tid] = kPsNone;
   if (tid < es::kHinfoWords) s_row[tid] = 0;
   __syncthreads();
 
   // ---- a. the first VPS, SPS and PPS rows
-  const ps_v4i* rows = reinterpret_cast<const ps_v4i*>(ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
+  const v4i* rows = reinterpret_cast<const v4i*>(c.ix.nal);  // a table row is 16 bytes of a 16-byte aligned table
   const int types[es::kHpsRows] = {es::kHevcVps, es::kHevcSps, es::kHevcPps};
   ps_find_rows(rows, R, types, s_found);
   const int found[es::kHpsRows] = {s_found[es::kHpsVps], s_found[es::kHpsSps], s_found[es::kHpsPps]};
@@ -74,17 +67,16 @@ __global__ __launch_bounds__(kPsThreads) void hevc_config_kernel(
 #pragma unroll
   for (int w = 0; w < es::kHpsRows; ++w) {
     if (found[w] == kPsNone) continue;
-    const ps_v4i row = rows[found[w]];
+    const v4i row = rows[found[w]];
     src[w] = static_cast<int>(clamp(row[es::kNalOffset], 0, cap_es));
     len[w] = static_cast<int>(clamp(row[es::kNalLength], 0, cap_es - src[w]));
   }
   if (copies) {
-    const int64_t off = es_off[seg];
     const int mine_src = wave == 0 ? src[0] : wave == 1 ? src[1] : src[2];
     const int mine_len = wave == 0 ? len[0] : wave == 1 ? len[1] : len[2];
-    const ps_v4u q = ps_copy_lane(es + off, es_numel - off, mine_src, mine_len, max_ps, lane);
-    *reinterpret_cast<ps_v4u*>(hps + static_cast<int64_t>(wave) * max_ps + lane * 16) = q;
-    if (wave == es::kHpsSps) *reinterpret_cast<ps_v4u*>(s_raw + lane * 16) = q;
+    const v4u q = ps_copy_lane(es_segment_rsrc(b, seg), mine_src, mine_len, max_ps, lane);
+    *reinterpret_cast<v4u*>(hps + static_cast<int64_t>(wave) * max_ps + lane * 16) = q;
+    if (wave == es::kHpsSps) *reinterpret_cast<v4u*>(s_raw + lane * 16) = q;
   }
   __syncthreads();
 
@@ -134,8 +126,7 @@ __global__ __launch_bounds__(kPsThreads) void hevc_config_kernel(
 hipError_t launch_hevc_config(const HevcConfigArgs& a) {
   const EsBatch& b = a.b;
   if (b.nseg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(hevc_config_kernel, dim3(b.nseg), dim3(kPsThreads), 0, b.stream, b.es, b.es_numel, b.es_off,
-                     b.cap, b.info, b.pes, b.max_pes, b.max_nal, b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo,
+  hipLaunchKernelGGL(hevc_config_kernel, dim3(b.nseg), dim3(kPsThreads), 0, b.stream, es_batch_view(b),
                      static_cast<int>(a.max_ps), a.hps, a.hinfo);
   return hipGetLastError();
 }

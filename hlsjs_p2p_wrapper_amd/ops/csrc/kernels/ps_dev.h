@@ -15,22 +15,19 @@ constexpr int kPsNone = 0x7fffffff;
 static_assert(es::kMaxPsLimit / es::kPsAlign <= 64, "a wave copies a parameter set, a lane per 16 bytes");
 static_assert(es::kPsAlign == 16 && es::kNalWords == 4, "16-byte stores, 16-byte NAL rows");
 
-typedef unsigned int ps_v4u __attribute__((ext_vector_type(4)));
-typedef int ps_v4i __attribute__((ext_vector_type(4)));
-
 // a. The lowest row k < R of each of the N NAL types that has a length: rounds of 256 rows, one
 // 16-byte load per lane, a wave ballot per type, the lowest row of each through s_found[N] (LDS,
 // kPsNone in every slot and a barrier behind that before the call).  R is workgroup-uniform; the
 // round loop ends once every type is found.  s_found is readable by every thread on return.
 template <int N>
-__device__ __forceinline__ void ps_find_rows(const ps_v4i* __restrict__ rows, int R, const int (&types)[N],
+__device__ __forceinline__ void ps_find_rows(const v4i* __restrict__ rows, int R, const int (&types)[N],
                                              int* s_found) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int kb = 0; kb < R; kb += kPsThreads) {
     const int k = kb + tid;
     int type = -1;
     if (k < R) {
-      const ps_v4i row = rows[k];
+      const v4i row = rows[k];
       if (row[es::kNalLength] > 0) type = row[es::kNalType];
     }
     unsigned long long m[N];
@@ -51,24 +48,16 @@ __device__ __forceinline__ void ps_find_rows(const ps_v4i* __restrict__ rows, in
 }
 
 // b. This lane's 16 bytes of one stored NAL unit: bytes [src + 16 lane, ..) of the segment's ES
-// through a buffer resource that ends with the ES tensor (`avail` bytes from es_seg; a load beyond
-// them yields zeros), five dwords funnelled to the NAL's alignment (v_alignbyte) and masked to
-// the stored length min(len, max_ps).  Lanes behind the stored length get zeros.  For the lanes of
-// one wave with 16 lane < max_ps.
-__device__ __forceinline__ ps_v4u ps_copy_lane(const uint8_t* es_seg, int64_t avail, int src, int len, int max_ps,
-                                               int lane) {
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(es_seg), 0, static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+// through its buffer resource (es_dev.h es_segment_rsrc: a load beyond the ES tensor yields
+// zeros), at the NAL's alignment (load16_unaligned) and masked to the stored length
+// min(len, max_ps).  Lanes behind the stored length get zeros.  For the lanes of one wave with
+// 16 lane < max_ps.
+__device__ __forceinline__ v4u ps_copy_lane(__amdgpu_buffer_rsrc_t rsrc, int src, int len, int max_ps, int lane) {
   const int stored = len < max_ps ? len : max_ps;
   const int left = stored - lane * 16;  // bytes of this lane's 16 that are stored
-  ps_v4u q = {0, 0, 0, 0};
+  v4u q = {0, 0, 0, 0};
   if (left > 0) {
-    const int sa = src + lane * 16;
-    const ps_v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, sa & ~3, 0, 0);
-    const uint32_t w4 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (sa & ~3) + 16, 0, 0);
-    const uint32_t sh = static_cast<uint32_t>(sa & 3);
-    q = ps_v4u{__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh),
-               __builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(w4, v.w, sh)};
+    q = load16_unaligned(rsrc, src + lane * 16);
 #pragma unroll
     for (int d = 0; d < 4; ++d) {  // zero behind the stored bytes
       const int keep = left - 4 * d;
@@ -84,7 +73,7 @@ __device__ __forceinline__ ps_v4u ps_copy_lane(const uint8_t* es_seg, int64_t av
 // carry across waves (s_wave[kPsWaves], LDS) and rounds compacts the kept bytes into s_rbsp.
 // n is workgroup-uniform; returns the RBSP's length.  A barrier stands behind the last store.
 __device__ __forceinline__ int ps_unescape(const uint8_t* s_raw, int n, int header, uint8_t* s_rbsp, int* s_wave) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   int carry = 0;
   for (int jb = 0; jb < n; jb += kPsThreads) {
     const int j = jb + tid;
@@ -94,17 +83,10 @@ __device__ __forceinline__ int ps_unescape(const uint8_t* s_raw, int n, int head
       b = s_raw[j];
       keep = j < 2 || !es::is_emulation_prevention(s_raw[j - 2], s_raw[j - 1], b);
     }
-    const unsigned long long m = __ballot(keep);
-    if (lane == 0) s_wave[wave] = __popcll(m);
-    __syncthreads();
-    int before = carry, total = 0;
-#pragma unroll
-    for (int w = 0; w < kPsWaves; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (keep) s_rbsp[before + __popcll(m & ((1ull << lane) - 1ull))] = b;
-    carry += total;
+    const int inc = __popcll(__ballot(keep) & (~0ull >> (63 - lane)));  // kept bytes up to this lane's
+    const WgPrefix<int> p = wg_exclusive_prefix<kPsWaves>(inc, keep ? 1 : 0, s_wave);
+    if (keep) s_rbsp[carry + p.before] = b;
+    carry += p.total;
     __syncthreads();  // s_wave is free again
   }
   return carry;

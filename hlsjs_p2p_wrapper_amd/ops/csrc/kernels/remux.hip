@@ -22,15 +22,13 @@
 //                          region, a lane per 16 aligned output bytes.  The lane finds the NAL
 //                          (or frame) that covers its bytes by binary search of the payload
 //                          offsets, narrowed to the rows the tile touches; 16 bytes inside one
-//                          body are funnelled out of five source dwords (v_alignbyte) and stored
+//                          body are funnelled out of five source dwords (common.h funnel16) and stored
 //                          as one vector, every other chunk goes byte by byte and stores only
 //                          payload bytes.  Tiles past the real output exit at once.
 // No workgroup waits for another one: the order comes from the launches alone.
 // The keep rule, the ADTS frame rule and the timestamp differences are shared/grammar.hpp
 // (namespace es), the same functions runtime/remux.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -42,31 +40,28 @@ constexpr int kRxIters = es::kRemuxTile / kRxIterBytes;
 static_assert(kRxIters * kRxIterBytes == es::kRemuxTile, "the tile is a whole number of iterations");
 int remux_tile_bytes() { return es::kRemuxTile; }
 
-// Exclusive prefix sum over the workgroup (every thread calls it); total: the sum of all.
+// Exclusive prefix sum of 64-bit values over the workgroup (every thread calls it); total: the sum
+// of all.  The wave step is a shuffle ladder (DPP moves 32 bits), the rest common.h wg_exclusive_prefix.
 __device__ __forceinline__ int64_t rx_block_scan(int64_t v, int64_t* s_w, int64_t& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   int64_t inc = v;
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) {
     const int64_t t = __shfl_up(inc, d);
     if (lane >= d) inc += t;
   }
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  int64_t pre = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < kRxWaves; ++w) {
-    if (w < wave) pre += s_w[w];
-    total += s_w[w];
-  }
+  const WgPrefix<int64_t> p = wg_exclusive_prefix<kRxWaves>(inc, v, s_w);
+  total = p.total;
   __syncthreads();  // s_w is free again
-  return pre + inc - v;
+  return p.before;
 }
 
 __device__ __forceinline__ int32_t rx_sat32(int64_t v) { return v < 0x7fffffff ? static_cast<int32_t>(v) : 0x7fffffff; }
 
 // ---------------------------------------------------------------- 1. plan
+// The batch arrives as separate parameters here and becomes a view in the kernel: only a kernel
+// argument carries readonly and noalias, which keep the uniform loads behind the first global
+// store scalar.  With the view by value this kernel takes 85 VGPRs (occupancy 5) against 75 (6).
 __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
     const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
     const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
@@ -79,21 +74,19 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
   __shared__ int s_bad, s_nrec, s_q, s_aover;
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
-  es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
-  sg.cap = clamp(sg.cap, 0, 0x7fffffff);  // offsets inside the segment are kept in int32 scratch rows
-  const es::IndexTables<const int32_t, const int64_t> ix =
-      es::index_tables_at<const int32_t, const int64_t>({nal_all, au_all, af_all, sinfo}, sg, seg);
+  // no buffer resource here: es_numel stays unused
+  const EsBatchView b{es, 0, es_off, cap, info, pes, max_pes, max_nal, {nal_all, au_all, af_all, sinfo}};
+  const auto c = es_segment(b, seg);  // the clamped cap: offsets inside the segment are kept in int32 scratch rows
+  const es::Segment& sg = c.sg;
   const es::RemuxTables tb = es::remux_tables_at({vs_all, as_all, rinfo}, sg, max_aframes, seg);
-  const int64_t* si = ix.sinfo;
+  const int64_t* si = c.ix.sinfo;
   const int64_t room_es = sg.cap;
   const uint8_t* V = sg.es;
-  const es::VideoSpan video = es::video_span(sg);
-  const bool supported = video.supported, hevc = video.hevc;
-  const int64_t R = es::video_rows(video, si[es::kNumNal], max_nal);
-  const int64_t m = es::video_rows(video, si[es::kNumAu], max_pes);  // the index's count, not the demux's
+  const bool supported = c.video.supported, hevc = c.video.hevc;
+  const int64_t R = c.R, m = c.m;  // the index's counts, not the demux's
   const es::PesRows rows = es::pes_rows(sg);
   const int64_t *vp = rows.video, *ap = rows.audio;
-  const int32_t *nal = ix.nal, *au = ix.au, *af = ix.aframes;
+  const int32_t *nal = c.ix.nal, *au = c.ix.au, *af = c.ix.aframes;
   int32_t *vs = tb.vsamples, *as = tb.asamples;
   const es::RemuxScratch part = es::remux_scratch(1, max_nal, max_aframes);
   int32_t* sc = scratch + static_cast<int64_t>(seg) * part.stride;
@@ -287,7 +280,6 @@ __device__ __forceinline__ void rx_copy_stream(__amdgpu_buffer_rsrc_t rsrc, cons
                                                uint8_t* __restrict__ o, int b0, int lo, int hi,
                                                const int32_t* __restrict__ start, const int32_t* __restrict__ src,
                                                int cnt) {
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   const int t_lo = lo > b0 ? lo : b0;
   const int t_hi = hi < b0 + es::kRemuxTile ? hi : b0 + es::kRemuxTile;
   if (t_lo >= t_hi || cnt <= 0) return;  // workgroup-uniform
@@ -322,10 +314,7 @@ __device__ __forceinline__ void rx_copy_stream(__amdgpu_buffer_rsrc_t rsrc, cons
 #pragma unroll
   for (int it = 0; it < kRxIters; ++it) {
     if (fast[it]) {
-      const uint32_t sh = static_cast<uint32_t>(sa[it] & 3);
-      const v4u q = {__builtin_amdgcn_alignbyte(v[it].y, v[it].x, sh), __builtin_amdgcn_alignbyte(v[it].z, v[it].y, sh),
-                     __builtin_amdgcn_alignbyte(v[it].w, v[it].z, sh), __builtin_amdgcn_alignbyte(w4[it], v[it].w, sh)};
-      *reinterpret_cast<v4u*>(o + c_lo[it]) = q;
+      *reinterpret_cast<v4u*>(o + c_lo[it]) = funnel16(v[it], w4[it], static_cast<uint32_t>(sa[it] & 3));
       continue;
     }
     int jj = j[it];
@@ -346,8 +335,7 @@ __device__ __forceinline__ void rx_copy_stream(__amdgpu_buffer_rsrc_t rsrc, cons
 }
 
 __global__ __launch_bounds__(kRxThreads) void remux_copy_kernel(
-    const uint8_t* __restrict__ es, int64_t es_numel, const int64_t* __restrict__ es_off,
-    const int64_t* __restrict__ tile_prefix, int nseg, int64_t max_nal, int64_t max_aframes,
+    EsBatchView b, const int64_t* __restrict__ tile_prefix, int nseg, int64_t max_aframes,
     const int32_t* __restrict__ scratch, const int64_t* __restrict__ rinfo, uint8_t* __restrict__ out,
     const int64_t* __restrict__ out_off) {
   const int64_t gt = blockIdx.x;
@@ -358,28 +346,26 @@ __global__ __launch_bounds__(kRxThreads) void remux_copy_kernel(
   const int A0 = static_cast<int>(ri[es::kAudioBoxOffset]);
   const int Q = static_cast<int>(ri[es::kAudioPayloadBytes]);
   if (b0 >= A0 + 8 + Q) return;  // past the real output (A0 + 8 >= 8 + P)
-  const es::RemuxScratch part = es::remux_scratch(1, max_nal, max_aframes);
+  const es::RemuxScratch part = es::remux_scratch(1, b.max_nal, max_aframes);
   const int32_t* sc = scratch + static_cast<int64_t>(seg) * part.stride;
-  const int64_t off = es_off[seg];
-  const int64_t avail = es_numel - off;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<uint8_t*>(es + off), 0, static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = es_segment_rsrc(b, seg);
+  const uint8_t* V = b.es + b.es_off[seg];
   uint8_t* o = out + out_off[seg];
-  rx_copy_stream<4>(rsrc, es + off, o, b0, 8, 8 + P, sc + part.vstart, sc + part.vsrc, sc[0]);
-  rx_copy_stream<0>(rsrc, es + off, o, b0, A0 + 8, A0 + 8 + Q, sc + part.astart, sc + part.asrc, sc[1]);
+  rx_copy_stream<4>(rsrc, V, o, b0, 8, 8 + P, sc + part.vstart, sc + part.vsrc, sc[0]);
+  rx_copy_stream<0>(rsrc, V, o, b0, A0 + 8, A0 + 8 + Q, sc + part.astart, sc + part.asrc, sc[1]);
 }
 
 hipError_t launch_remux(const RemuxArgs& a) {
   const EsBatch& b = a.b;
   if (b.nseg <= 0) return hipSuccess;
+  const EsBatchView view = es_batch_view(b);
   hipLaunchKernelGGL(remux_plan_kernel, dim3(b.nseg), dim3(kRxThreads), 0, b.stream, b.es, b.es_off, b.cap, b.info,
                      b.pes, b.max_pes, b.max_nal, b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo, a.max_aframes, a.scratch,
                      a.t.vsamples, a.t.asamples, a.t.rinfo, a.out, a.out_off);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || b.total_tiles <= 0) return e;
   hipLaunchKernelGGL(remux_copy_kernel, dim3(static_cast<unsigned>(b.total_tiles)), dim3(kRxThreads), 0, b.stream,
-                     b.es, b.es_numel, b.es_off, b.tile_prefix, b.nseg, b.max_nal, a.max_aframes, a.scratch, a.t.rinfo,
-                     a.out, a.out_off);
+                     view, b.tile_prefix, b.nseg, a.max_aframes, a.scratch, a.t.rinfo, a.out, a.out_off);
   return hipGetLastError();
 }
 

@@ -18,11 +18,13 @@
 //                               segments that did not ask and of other codecs exit before the
 //                               first barrier.
 //      video: the workgroup walks the NAL rows of its access unit.  A candidate longer than 48 raw
-//             bytes is walked twice in rounds of kSaRound raw bytes, 16 per lane through a buffer
-//             resource that ends with the ES tensor: first only counted (the NAL sits in L2 for
+//             bytes is walked twice in rounds of kSaRound raw bytes, 16 per lane (common.h
+//             load16_unaligned) through the segment's buffer resource (es_dev.h es_segment_rsrc:
+//             it ends with the ES tensor): first only counted (the NAL sits in L2 for
 //             the second walk), then, if it is protected, compacted into an LDS staging area
 //             (emulation-prevention flags from the two raw predecessors, popcount prefix in the
-//             wave by DPP, four wave totals through LDS, a carry across rounds), a lane per
+//             wave by DPP, four wave totals through LDS (common.h wg_exclusive_prefix), a carry
+//             across rounds), a lane per
 //             cipher block decrypts there, and the staged bytes go back to global in 16-byte
 //             vectors.  Compaction only moves bytes towards lower addresses inside the
 //             workgroup's own NAL, and a round stores only behind a barrier that follows its loads.
@@ -35,9 +37,7 @@
 // frame rule and the segment view are shared/grammar.hpp (namespace es), the same functions
 // runtime/sampleaes.cpp calls.
 #include "aes_small_dev.h"
-#include "common.h"
-#include "grammar.hpp"
-#include "launch.h"
+#include "es_dev.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -54,17 +54,10 @@ static_assert((es::kSaRound + 16) / es::kSaBlockStride + 2 <= kSaThreads, "a lan
 static_assert(es::kAesBlock == 16 && es::kSaWords <= 8, "16-byte blocks, a short sainfo row");
 int sample_aes_round_bytes() { return es::kSaRound; }
 
-typedef unsigned int sa_v4u __attribute__((ext_vector_type(4)));
+using SaBatchView = EsBatchViewOf<int32_t, const int64_t>;  // the length column of nal is rewritten
 
-// 16 bytes at byte offset sa of the segment (any alignment) through the segment's buffer resource:
-// five dwords funnelled by v_alignbyte; a dword beyond the resource's range reads as zero.
-__device__ __forceinline__ uint4 sa_load16(__amdgpu_buffer_rsrc_t rsrc, int sa) {
-  const sa_v4u v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, sa & ~3, 0, 0);
-  const uint32_t w4 = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (sa & ~3) + 16, 0, 0);
-  const uint32_t sh = static_cast<uint32_t>(sa & 3);
-  return uint4{__builtin_amdgcn_alignbyte(v.y, v.x, sh), __builtin_amdgcn_alignbyte(v.z, v.y, sh),
-               __builtin_amdgcn_alignbyte(v.w, v.z, sh), __builtin_amdgcn_alignbyte(w4, v.w, sh)};
-}
+// load16_unaligned's 16 bytes as the AES helpers take them
+__device__ __forceinline__ uint4 sa_u4(v4u q) { return uint4{q.x, q.y, q.z, q.w}; }
 __device__ __forceinline__ uint32_t sa_word(const uint4& q, int d) { return d == 0 ? q.x : d == 1 ? q.y : d == 2 ? q.z : q.w; }
 __device__ __forceinline__ int sa_byte(const uint4& q, int j) { return (sa_word(q, j >> 2) >> (8 * (j & 3))) & 0xff; }
 __device__ __forceinline__ uint4 sa_xor(const uint4& a, const uint4& b) { return uint4{a.x ^ b.x, a.y ^ b.y, a.z ^ b.z, a.w ^ b.w}; }
@@ -83,6 +76,8 @@ __device__ __forceinline__ void sa_put16(uint8_t* p, const uint4& q) {
 }
 
 // ---------------------------------------------------------------- 1. plan
+// Both kernels take the batch as separate parameters and make the view themselves: see
+// sample_aes_kernel.  This one reads no index table but sinfo.
 __global__ __launch_bounds__(kSaThreads) void sample_aes_plan_kernel(
     const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
     const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
@@ -91,9 +86,8 @@ __global__ __launch_bounds__(kSaThreads) void sample_aes_plan_kernel(
   if (seg >= nseg) return;
   int64_t status = 0;
   if (enable[seg]) {
-    es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
-    sg.cap = clamp(sg.cap, 0, 0x7fffffff);
-    status = es::sample_status(sg, sinfo + static_cast<int64_t>(seg) * es::kSinfoWords);
+    const EsBatchView b{es, 0, es_off, cap, info, pes, max_pes, max_nal, {nullptr, nullptr, nullptr, sinfo}};
+    status = es::sample_status(es_segment_clamped(b, seg), sinfo + static_cast<int64_t>(seg) * es::kSinfoWords);
   }
   int64_t* row = sainfo + static_cast<int64_t>(seg) * es::kSaWords;
 #pragma unroll
@@ -115,11 +109,11 @@ struct SaScan {
 // bytes in front of the round, left there by the round before (hazard 1).
 __device__ __forceinline__ SaScan sa_scan_round(__amdgpu_buffer_rsrc_t rsrc, int nal_off, int n, int t, uint8_t* s_raw,
                                                 int* s_wave) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t p = static_cast<int64_t>(t) * es::kSaRound + tid * 16;  // this lane's first raw byte
   const int nv = static_cast<int>(clamp(n - p, 0, 16));
   SaScan r = {uint4{0, 0, 0, 0}, 0, 0, 0};
-  if (nv > 0) r.q = sa_load16(rsrc, nal_off + static_cast<int>(p));
+  if (nv > 0) r.q = sa_u4(load16_unaligned(rsrc, nal_off + static_cast<int>(p)));
   *reinterpret_cast<uint4*>(s_raw + 16 + tid * 16) = r.q;
   // every load of the round has returned (its data is in LDS) before any thread goes on to store
   __syncthreads();
@@ -131,17 +125,10 @@ __device__ __forceinline__ SaScan sa_scan_round(__amdgpu_buffer_rsrc_t rsrc, int
     p2 = p1;
     p1 = b;
   }
-  const uint32_t cnt = __popc(r.keep);
-  const uint32_t inc = wave_scan_dpp(cnt);
-  if (lane == 63) s_wave[wave] = static_cast<int>(inc);
-  __syncthreads();
-  int pre = 0;
-#pragma unroll
-  for (int w = 0; w < kSaWaves; ++w) {
-    if (w < wave) pre += s_wave[w];
-    r.total += s_wave[w];
-  }
-  r.before = pre + static_cast<int>(inc - cnt);
+  const int cnt = __popc(r.keep);
+  const WgPrefix<int> pre = wg_exclusive_prefix<kSaWaves>(static_cast<int>(wave_scan_dpp(cnt)), cnt, s_wave);
+  r.before = pre.before;
+  r.total = pre.total;
   // hazard 1: the round's last two raw bytes are the next round's predecessors, and this round's
   // own write-back may overwrite them in global memory: they stay in LDS.  Every thread has read
   // its predecessors in front of the barrier above.
@@ -152,6 +139,9 @@ __device__ __forceinline__ SaScan sa_scan_round(__amdgpu_buffer_rsrc_t rsrc, int
   return r;
 }
 
+// The batch arrives as separate parameters here and becomes a view in the kernel: only a kernel
+// argument carries readonly and noalias, which keep the uniform loads of the unit loops scalar
+// while the kernel stores to es and nal.  es is read and written, nal_all written: no qualifier.
 __global__ __launch_bounds__(kSaThreads) void sample_aes_kernel(
     uint8_t* es, int64_t es_numel, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
     const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
@@ -169,16 +159,14 @@ __global__ __launch_bounds__(kSaThreads) void sample_aes_kernel(
   const bool is_audio = blockIdx.z != 0;
   const int tid = threadIdx.x;
   if (!enable[seg]) return;
-  es::Segment sg = es::segment_at(es, es_off, cap, info, pes, max_pes, max_nal, seg);
-  sg.cap = clamp(sg.cap, 0, 0x7fffffff);
-  const int cap_es = static_cast<int>(sg.cap);
-  const es::IndexTables<int32_t, const int64_t> ix = es::index_tables_at<int32_t, const int64_t>(
-      {nal_all, const_cast<int32_t*>(au_all), const_cast<int32_t*>(af_all), sinfo}, sg, seg);
-  const int64_t seg_off = es_off[seg];
-  uint8_t* E = es + seg_off;  // 16-byte aligned: the tensor is, and so is every segment offset
-  const int64_t avail = es_numel - seg_off;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc(E, 0, static_cast<int>(avail < 0x7fffffff ? avail : 0x7fffffff), 0x00020000);
+  const SaBatchView b{es, es_numel, es_off, cap, info, pes, max_pes, max_nal,
+                      {nal_all, const_cast<int32_t*>(au_all), const_cast<int32_t*>(af_all), sinfo}};
+  const auto sv = es_segment(b, seg);
+  const es::Segment& sg = sv.sg;
+  const es::IndexTables<int32_t, const int64_t>& ix = sv.ix;
+  const int cap_es = sv.cap;
+  uint8_t* E = es + b.es_off[seg];  // es is b.es, writable; 16-byte aligned: the tensor is, and so is every offset
+  const __amdgpu_buffer_rsrc_t rsrc = es_segment_rsrc(b, seg);
   const uint4 iv = *reinterpret_cast<const uint4*>(iv_all + static_cast<int64_t>(seg) * es::kAesBlock);
   const uint32_t* rk = rk_all + static_cast<int64_t>(seg) * es::kAesRoundKeyWords;
   unsigned long long* sainfo = reinterpret_cast<unsigned long long*>(sainfo_all + static_cast<int64_t>(seg) * es::kSaWords);
@@ -186,9 +174,7 @@ __global__ __launch_bounds__(kSaThreads) void sample_aes_kernel(
   if (!is_audio) {
     // ------------------------------------------------------------ video: one access unit
     if (sg.info[ts::kVideoType] != ts::kAvc) return;
-    const es::VideoSpan video = es::video_span(sg);
-    const int64_t R = es::video_rows(video, ix.sinfo[es::kNumNal], max_nal);
-    const int64_t m = es::video_rows(video, ix.sinfo[es::kNumAu], max_pes);
+    const int64_t R = sv.R, m = sv.m;
     if (static_cast<int64_t>(blockIdx.x) >= m) return;
     aes_small_fill(s_aes, tdl, isb, rk, tid);
     __syncthreads();
@@ -321,8 +307,8 @@ __global__ __launch_bounds__(kSaThreads) void sample_aes_kernel(
         const bool mine = i < nb;
         uint4 p4 = {0, 0, 0, 0};
         if (mine) {
-          const uint4 c4 = sa_load16(rsrc, base + es::kAesBlock * i);
-          const uint4 chain = i == 0 ? iv : sa_load16(rsrc, base + es::kAesBlock * (i - 1));
+          const uint4 c4 = sa_u4(load16_unaligned(rsrc, base + es::kAesBlock * i));
+          const uint4 chain = i == 0 ? iv : sa_u4(load16_unaligned(rsrc, base + es::kAesBlock * (i - 1)));
           p4 = sa_xor(aes_small_decrypt(s_aes, c4), chain);  // consumes the loads: they have returned
         }
         __syncthreads();

@@ -395,7 +395,6 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   // ES stores go through a buffer resource: buffer_store_dwordx4 at a dword-aligned offset
   // (a plain 16-byte store at 4-byte alignment is split by the compiler into dwordx3 + dword)
-  typedef unsigned int v4u __attribute__((ext_vector_type(4)));
   const __amdgpu_buffer_rsrc_t es_rsrc = __builtin_amdgcn_make_buffer_rsrc(ebase, 0, 0x7fffffff, 0x00020000);
   const int dst32 = static_cast<int>(dst_b);  // within one segment's ES (< 2 GiB)
   const int grp = lane / 12, sub = lane - 12 * grp;  // groups 0..4; lanes 60..63 idle
@@ -419,17 +418,14 @@ __global__ __launch_bounds__(kTsThreads) void ts_gather_kernel(
       const int a = s + head + 4 * k0;
       const uint32_t sh = static_cast<uint32_t>(a & 3);
       const uint32_t* w = s_pk + (a >> 2);
-      const uint32_t x0 = w[0], x1 = w[1], x2 = w[2], x3 = w[3], x4 = w[4];
-      const uint32_t o0 = __builtin_amdgcn_alignbyte(x1, x0, sh), o1 = __builtin_amdgcn_alignbyte(x2, x1, sh),
-                     o2 = __builtin_amdgcn_alignbyte(x3, x2, sh), o3 = __builtin_amdgcn_alignbyte(x4, x3, sh);
+      const v4u q = funnel16(v4u{w[0], w[1], w[2], w[3]}, w[4], sh);
       uint32_t* dw = reinterpret_cast<uint32_t*>(d + head) + k0;
       if (k0 + 4 <= body) {
-        const v4u q = {o0, o1, o2, o3};
         __builtin_amdgcn_raw_buffer_store_b128(q, es_rsrc, jdst + head + 4 * k0, 0, 0);
       } else {
-        dw[0] = o0;
-        if (k0 + 1 < body) dw[1] = o1;
-        if (k0 + 2 < body) dw[2] = o2;
+        dw[0] = q.x;
+        if (k0 + 1 < body) dw[1] = q.y;
+        if (k0 + 2 < body) dw[2] = q.z;
       }
     }
     if (sub < tail) d[head + 4 * body + sub] = s_bytes[s + head + 4 * body + sub];
