@@ -27,7 +27,7 @@ import torch
 
 from ._native import device as _dev
 from ._native import runtime as _rt
-from .esindex import BatchPlan, EsIndex
+from .esindex import EsIndex, IndexedBatch
 from .tsdemux import DemuxResult
 
 CCINFO = {"status": 0, "n_sei": 1, "n_samples": 2, "n_triples": 3, "field1_pairs": 4, "field2_pairs": 5,
@@ -83,31 +83,23 @@ def caption_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], max_cc: in
     max_cc = int(max_cc)
     if not 1 <= max_cc <= MAX_CC_LIMIT:
         raise ValueError("caption_batch: max_cc must be 1 to 2048")
-    B, max_pes, dev, rt = len(res.es_offs), int(res.pes.shape[2]), res.es.device, _rt()
-    max_nal = int(ix.nal.shape[1])
+    B = len(res.es_offs)
     if enable is not None and len(enable) != B:
         raise ValueError("caption_batch: one enable flag per segment")
-    if ix.nal.device != dev:
-        raise ValueError("caption_batch: the batch and its index must be on one device")
-    if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
-            or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
-            or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
-        raise ValueError("caption_batch: the index does not belong to this batch")
+    batch = IndexedBatch("caption_batch", res, ix, caps)
+    dev = batch.dev
     en = np.ones(B, dtype=np.uint8) if enable is None else np.asarray([bool(e) for e in enable], dtype=np.uint8)
-    plan = BatchPlan("caption_batch", res, caps)
-    cc = Captions(plan.table(0, CCINFO_WORDS, torch.int64), plan.table(max_cc, CCROW_WORDS),
+    cc = Captions(batch.table(0, CCINFO_WORDS, torch.int64), batch.table(max_cc, CCROW_WORDS),
                   torch.empty((B, max_cc), dtype=torch.int64, device=dev),
                   torch.empty((B, max_cc, CC_SLOT_BYTES), dtype=torch.uint8, device=dev),
                   torch.empty((B, max_cc, 2, CC_FIELD_BYTES), dtype=torch.uint8, device=dev))
     if dev.type == "cpu":
-        rt.caption_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
-                         ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), en, max_cc,
-                         cc.ccsamples.numpy(), cc.ccpts.numpy(), cc.ccbytes.numpy(), cc.cc608.numpy(),
-                         cc.ccinfo.numpy())
+        _rt().caption_batch(*batch.host_args(), en, max_cc, cc.ccsamples.numpy(), cc.ccpts.numpy(), cc.ccbytes.numpy(),
+                            cc.cc608.numpy(), cc.ccinfo.numpy())
         return cc
-    d, _ = plan.on_device(plan.cap, "ES", 0, en=("enable", en, 1))  # one packed copy with the descriptors
+    d, _ = batch.on_device(batch.cap, "ES", 0, en=("enable", en, 1))  # one packed copy with the descriptors
     if B:
-        scratch = torch.empty(_dev().cc_scratch_words(B, max_nal), dtype=torch.int32, device=dev)
-        _dev().cc_extract(res.es, d["eo"], d["cap"], res.info, res.pes, max_pes, max_nal, ix.nal, ix.au, ix.aframes,
-                          ix.sinfo, d["en"], max_cc, scratch, cc.ccsamples, cc.ccpts, cc.ccbytes, cc.cc608, cc.ccinfo)
+        scratch = torch.empty(_dev().cc_scratch_words(B, batch.max_nal), dtype=torch.int32, device=dev)
+        _dev().cc_extract(*batch.device_args(d), d["en"], max_cc, scratch, cc.ccsamples, cc.ccpts, cc.ccbytes, cc.cc608,
+                          cc.ccinfo)
     return cc

@@ -24,7 +24,7 @@ import torch
 
 from ._native import device as _dev
 from ._native import runtime as _rt
-from .esindex import BatchPlan, EsIndex
+from .esindex import EsIndex, IndexedBatch
 from .tsdemux import DemuxResult
 
 CINFO = {"status": 0, "sps_nal": 1, "sps_bytes": 2, "sps_rbsp_bytes": 3, "pps_nal": 4, "pps_bytes": 5,
@@ -64,23 +64,12 @@ def config_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], max_ps: int
     max_ps = int(max_ps)
     if max_ps <= 0 or max_ps % 16 or max_ps > MAX_PS_LIMIT:
         raise ValueError("config_batch: max_ps must be a positive multiple of 16 up to 1024")
-    B, max_pes, dev, rt = len(res.es_offs), int(res.pes.shape[2]), res.es.device, _rt()
-    max_nal = int(ix.nal.shape[1])
-    if ix.nal.device != dev:
-        raise ValueError("config_batch: the batch and its index must be on one device")
-    if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
-            or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
-            or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
-        raise ValueError("config_batch: the index does not belong to this batch")
-    plan = BatchPlan("config_batch", res, caps)
-    cfg = CodecConfig(plan.table(0, CINFO_WORDS), torch.empty((B, 2, max_ps), dtype=torch.uint8, device=dev))
-    if dev.type == "cpu":
-        rt.config_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
-                        ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), max_ps,
-                        cfg.cinfo.numpy(), cfg.ps.numpy())
+    batch = IndexedBatch("config_batch", res, ix, caps)
+    cfg = CodecConfig(batch.table(0, CINFO_WORDS), batch.table(2, max_ps, torch.uint8))
+    if batch.dev.type == "cpu":
+        _rt().config_batch(*batch.host_args(), max_ps, cfg.cinfo.numpy(), cfg.ps.numpy())
         return cfg
-    d, _ = plan.on_device(plan.cap, "ES", 0)
-    if B:
-        _dev().codec_config(res.es, d["eo"], d["cap"], res.info, res.pes, max_pes, max_nal, ix.nal, ix.au,
-                            ix.aframes, ix.sinfo, max_ps, cfg.cinfo, cfg.ps)
+    d, _ = batch.on_device(batch.cap, "ES", 0)
+    if batch.B:
+        _dev().codec_config(*batch.device_args(d), max_ps, cfg.cinfo, cfg.ps)
     return cfg

@@ -31,7 +31,7 @@ T* check(const Tensor& t, const char* name, int64_t min_numel = 0) {
 
 hipStream_t stream() { return c10::hip::getCurrentHIPStream().stream(); }
 
-// The checks every op on a demuxed batch (es_batch below) makes of the tensors it names.
+// Device and alignment checks: es_batch below makes them of the batch's tensors, each op of its own.
 void same_device(const Tensor& first, std::initializer_list<std::reference_wrapper<const Tensor>> rest) {
   for (const Tensor& t : rest) TORCH_CHECK(first.device() == t.device(), "tensors on different devices");
 }
@@ -124,43 +124,48 @@ void ts_demux(Tensor buf, Tensor seg_off, Tensor seg_len, Tensor blk_prefix, int
   hip_ok(D::launch_ts_demux(a), "ts_demux launch");
 }
 
-// The demuxed batch es_index and remux share (launch.h EsBatch): es / info / pes are ts_demux's
-// outputs, cap the host upper bound of each segment's ES bytes (the Python wrapper has checked
-// es_off + cap against es), tile_prefix the exclusive prefix of the op's tiles per segment.
-// `before_tables` runs between the checks of pes and nal, where es_index checks its scratch.
-// An op without a tile space (codec_config) passes no tile_prefix and 0 tiles.
-template <typename F>
-D::EsBatch es_batch(const Tensor& es, const Tensor& es_off, const Tensor& cap, const c10::optional<Tensor>& tile_prefix,
-                    int64_t total_tiles, const Tensor& info, const Tensor& pes, int64_t max_pes, int64_t max_nal,
-                    const Tensor& nal, const Tensor& au, const Tensor& aframes, const Tensor& sinfo,
-                    F&& before_tables) {
+// The demuxed (and, behind es_index, indexed) batch every op below takes (launch.h EsBatch), checked
+// here for all of them: max_pes / max_nal / total_tiles in range (`op` names the caller), every
+// tensor a contiguous GPU tensor of its dtype and size, all of them on one device, es and nal
+// 16-byte aligned.  es / info / pes are ts_demux's outputs, cap the host upper bound of each
+// segment's ES bytes (the Python wrapper has checked es_off + cap against es), tile_prefix the
+// exclusive prefix of the op's tiles per segment.  An op without a tile space (codec_config)
+// passes no tile_prefix and 0 tiles.  What is left to an op: its own tensors and sizes.
+D::EsBatch es_batch(const char* op, const Tensor& es, const Tensor& es_off, const Tensor& cap,
+                    const c10::optional<Tensor>& tile_prefix, int64_t total_tiles, const Tensor& info, const Tensor& pes,
+                    int64_t max_pes, int64_t max_nal, const Tensor& nal, const Tensor& au, const Tensor& aframes,
+                    const Tensor& sinfo) {
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0 && max_nal <= 0x7fffffff && total_tiles >= 0, op,
+              ": max_pes / max_nal / total_tiles out of range");
   const int64_t B = es_off.numel();
-  D::EsBatch b{.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
-               .es_off = check<int64_t>(es_off, "es_off"),
-               .cap = check<int64_t>(cap, "cap", B),
-               .tile_prefix = tile_prefix.has_value() ? check<int64_t>(*tile_prefix, "tile_prefix", B + 1) : nullptr,
-               .nseg = static_cast<int>(B), .total_tiles = total_tiles,
-               .info = check<int64_t>(info, "info", B * ts::kInfoWords),
-               .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
-               .max_pes = max_pes, .max_nal = max_nal, .ix = {}, .stream = stream()};
-  before_tables();
-  b.ix = {check<int32_t>(nal, "nal", hlsp2p::table_words(B, max_nal, es_::kNalWords)),
-          check<int32_t>(au, "au", hlsp2p::table_words(B, max_pes, es_::kAuWords)),
-          check<int32_t>(aframes, "aframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
-          check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords)};
+  const D::EsBatch b{
+      .es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
+      .es_off = check<int64_t>(es_off, "es_off"),
+      .cap = check<int64_t>(cap, "cap", B),
+      .tile_prefix = tile_prefix.has_value() ? check<int64_t>(*tile_prefix, "tile_prefix", B + 1) : nullptr,
+      .nseg = static_cast<int>(B), .total_tiles = total_tiles,
+      .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+      .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+      .max_pes = max_pes, .max_nal = max_nal,
+      .ix = {check<int32_t>(nal, "nal", hlsp2p::table_words(B, max_nal, es_::kNalWords)),
+             check<int32_t>(au, "au", hlsp2p::table_words(B, max_pes, es_::kAuWords)),
+             check<int32_t>(aframes, "aframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+             check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords)},
+      .stream = stream()};
+  same_device(es, {es_off, cap, info, pes, nal, au, aframes, sinfo});
+  if (tile_prefix.has_value()) same_device(es, {*tile_prefix});
+  aligned16({{es, "es"}, {nal, "nal"}});
   return b;
 }
 
 // Sample index of a demuxed batch (es_index.hip): tile_prefix counts ceil(cap / es_index_tile_bytes()).
 void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
               int64_t max_pes, int64_t max_nal, Tensor scratch, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo) {
-  TORCH_CHECK(max_pes > 0 && max_nal > 0 && total_tiles >= 0, "es_index: max_pes / max_nal / total_tiles out of range");
-  D::EsIndexArgs a{};
-  a.b = es_batch(es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [&] {
-    a.scratch = check<int32_t>(scratch, "scratch", es_::index_scratch(total_tiles, es_off.numel(), max_nal).end);
-  });
-  same_device(es, {sinfo});
-  aligned16({{es, "es"}});
+  const D::EsIndexArgs a{
+      .b = es_batch("es_index", es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes,
+                    sinfo),
+      .scratch = check<int32_t>(scratch, "scratch", es_::index_scratch(total_tiles, es_off.numel(), max_nal).end)};
+  same_device(es, {scratch});
   hip_ok(D::launch_es_index(a), "es_index launch");
 }
 
@@ -171,10 +176,10 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
            int64_t max_pes, int64_t max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_aframes,
            Tensor scratch, Tensor vsamples, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off) {
   const int64_t B = es_off.numel();
-  TORCH_CHECK(max_pes > 0 && max_nal > 0 && max_aframes > 0 && total_tiles >= 0,
-              "remux: max_pes / max_nal / max_aframes / total_tiles out of range");
+  TORCH_CHECK(max_aframes > 0, "remux: max_aframes out of range");
   const D::RemuxArgs a{
-      .b = es_batch(es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .b = es_batch("remux", es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes,
+                    sinfo),
       .max_aframes = max_aframes,
       .scratch = check<int32_t>(scratch, "scratch", es_::remux_scratch(B, max_nal, max_aframes).end),
       .t = {check<int32_t>(vsamples, "vsamples", hlsp2p::table_words(B, max_pes, es_::kVsampleWords)),
@@ -182,8 +187,8 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
             check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
       .out = check<uint8_t>(out, "out"),
       .out_off = check<int64_t>(out_off, "out_off", B)};
-  same_device(es, {out, rinfo});
-  aligned16({{es, "es"}, {out, "out"}});
+  same_device(es, {scratch, vsamples, asamples, rinfo, out, out_off});
+  aligned16({{out, "out"}});
   TORCH_CHECK(es.data_ptr() != out.data_ptr(), "remux cannot run in place");
   hip_ok(D::launch_remux(a), "remux launch");
 }
@@ -193,15 +198,15 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
 void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
                   Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_ps, Tensor cinfo, Tensor ps) {
   const int64_t B = es_off.numel();
-  TORCH_CHECK(max_pes > 0 && max_nal > 0, "codec_config: max_pes / max_nal out of range");
   TORCH_CHECK(es_::max_ps_ok(max_ps), "codec_config: max_ps must be a positive multiple of 16 up to 1024");
   const D::CodecConfigArgs a{
-      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .b = es_batch("codec_config", es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes,
+                    sinfo),
       .max_ps = max_ps,
       .ps = check<uint8_t>(ps, "ps", es_::ps_bytes(B, max_ps)),
       .cinfo = check<int32_t>(cinfo, "cinfo", B * es_::kCinfoWords)};
-  same_device(es, {ps, cinfo, nal});
-  aligned16({{es, "es"}, {ps, "ps"}, {nal, "nal"}});
+  same_device(es, {ps, cinfo});
+  aligned16({{ps, "ps"}});
   hip_ok(D::launch_codec_config(a), "codec_config launch");
 }
 
@@ -210,15 +215,15 @@ void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes,
 void hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
                  Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_ps, Tensor hinfo, Tensor hps) {
   const int64_t B = es_off.numel();
-  TORCH_CHECK(max_pes > 0 && max_nal > 0, "hevc_config: max_pes / max_nal out of range");
   TORCH_CHECK(es_::max_ps_ok(max_ps), "hevc_config: max_ps must be a positive multiple of 16 up to 1024");
   const D::HevcConfigArgs a{
-      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .b = es_batch("hevc_config", es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes,
+                    sinfo),
       .max_ps = max_ps,
       .hps = check<uint8_t>(hps, "hps", es_::hps_bytes(B, max_ps)),
       .hinfo = check<int32_t>(hinfo, "hinfo", B * es_::kHinfoWords)};
-  same_device(es, {hps, hinfo, nal, es_off, cap, info, pes, sinfo});
-  aligned16({{es, "es"}, {hps, "hps"}, {nal, "nal"}});
+  same_device(es, {hps, hinfo});
+  aligned16({{hps, "hps"}});
   hip_ok(D::launch_hevc_config(a), "hevc_config launch");
 }
 
@@ -229,10 +234,10 @@ void sample_aes_decrypt(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tenso
                         Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor round_keys, Tensor iv, Tensor enable,
                         Tensor td, Tensor isb, Tensor sainfo) {
   const int64_t B = es_off.numel();
-  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0, "sample_aes_decrypt: max_pes / max_nal out of range");
   TORCH_CHECK(B <= 65535, "sample_aes_decrypt: at most 65535 segments per call");
   const D::SampleAesArgs a{
-      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .b = es_batch("sample_aes_decrypt", es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au,
+                    aframes, sinfo),
       .es = check<uint8_t>(es, "es"),
       .round_keys = check<uint32_t>(round_keys, "round_keys", B * es_::kAesRoundKeyWords),
       .iv = check<uint8_t>(iv, "iv", B * es_::kAesBlock),
@@ -240,8 +245,8 @@ void sample_aes_decrypt(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tenso
       .td = check<uint32_t>(td, "td", 256),
       .isb = check<uint8_t>(isb, "isb", 256),
       .sainfo = check<int64_t>(sainfo, "sainfo", B * es_::kSaWords)};
-  same_device(es, {nal, sainfo, es_off, cap, info, pes, sinfo, au, aframes, round_keys, iv, enable, td, isb});
-  aligned16({{es, "es"}, {iv, "iv"}});
+  same_device(es, {round_keys, iv, enable, td, isb, sainfo});
+  aligned16({{iv, "iv"}});
   hip_ok(D::launch_sample_aes(a), "sample_aes_decrypt launch");
 }
 
@@ -252,12 +257,10 @@ void cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, i
                 Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor enable, int64_t max_cc, Tensor scratch,
                 Tensor ccsamples, Tensor ccpts, Tensor ccbytes, Tensor cc608, Tensor ccinfo) {
   const int64_t B = es_off.numel();
-  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0 && max_nal <= 0x7fffffff,
-              "cc_extract: max_pes / max_nal out of range");
   TORCH_CHECK(es_::max_cc_ok(max_cc), "cc_extract: max_cc must be 1 to 2048");
   TORCH_CHECK(B <= 65535, "cc_extract: at most 65535 segments per call");
   const D::CcExtractArgs a{
-      .b = es_batch(es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo, [] {}),
+      .b = es_batch("cc_extract", es, es_off, cap, c10::nullopt, 0, info, pes, max_pes, max_nal, nal, au, aframes, sinfo),
       .enable = check<uint8_t>(enable, "enable", B),
       .max_cc = max_cc,
       .scratch = check<int32_t>(scratch, "scratch", es_::cc_scratch(B, max_nal).end),
@@ -266,10 +269,8 @@ void cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, i
             check<uint8_t>(ccbytes, "ccbytes", B * max_cc * es_::kCcSlotBytes),
             check<uint8_t>(cc608, "cc608", B * max_cc * 2 * es_::kCcFieldBytes),
             check<int64_t>(ccinfo, "ccinfo", B * es_::kCcInfoWords)}};
-  same_device(es, {es_off, cap, info, pes, nal, au, aframes, sinfo, enable, scratch, ccsamples, ccpts, ccbytes, cc608,
-                   ccinfo});
-  aligned16({{es, "es"}, {nal, "nal"}, {scratch, "scratch"}, {ccsamples, "ccsamples"}, {ccbytes, "ccbytes"},
-             {cc608, "cc608"}});
+  same_device(es, {enable, scratch, ccsamples, ccpts, ccbytes, cc608, ccinfo});
+  aligned16({{scratch, "scratch"}, {ccsamples, "ccsamples"}, {ccbytes, "ccbytes"}, {cc608, "cc608"}});
   hip_ok(D::launch_cc_extract(a), "cc_extract launch");
 }
 

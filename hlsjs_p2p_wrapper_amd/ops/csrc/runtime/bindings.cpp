@@ -10,11 +10,13 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <sstream>
 #include <stdexcept>
 #include <thread>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "aes_host.hpp"
@@ -66,9 +68,9 @@ void parallel_for(int64_t n, F&& f, int64_t work_bytes = -1) {
   for (auto& x : th) x.join();
 }
 
-// The demuxed and indexed batch index_batch, remux_batch, config_batch and hevc_config_batch take: its sizes are checked here, once
-// (`more_ok`: the caller's own sizes, part of the same check), then each segment's ES range and,
-// right behind it, whatever `also(b)` checks of segment b.
+// The demuxed and indexed batch every op from index_batch to caption_batch takes: its sizes are
+// checked here, once (`more_ok`: the caller's own sizes, part of the same check), then each
+// segment's ES range and, right behind it, whatever `also(b)` checks of segment b.
 struct EsBatch {
   const uint8_t* es;
   const int64_t *es_off, *cap, *info, *pes;
@@ -93,6 +95,47 @@ EsBatch es_batch(const std::string& op, const Arr<uint8_t>& es, const Arr<int64_
     r.total += r.cap[b];
   }
   return r;
+}
+
+// A table's pointer as the op's es::IndexTables asks for it.  A table the op writes comes as a
+// py::array and has to be writeable as it is; one it only reads comes as an Arr.  IndexTables has
+// one I32 for nal, au and aframes, so sample_decrypt_batch, which rewrites nal alone, gets the two
+// it only reads through `int32_t*` as well.
+template <typename T>
+T* table_ptr(py::array& a, const char* name) { return mut_ptr<T>(a, name); }
+template <typename T>
+T* table_ptr(const Arr<std::remove_const_t<T>>& a, const char*) { return const_cast<T*>(a.data()); }
+
+// One op on a demuxed and indexed batch, whole: es_batch's checks (`sized`, `also` as there), then
+// `body(segment b, its index tables, b)` for every segment, on threads and without the GIL.
+// I32 / I64 as in es::IndexTables: const where the op only reads the table.
+template <typename I32, typename I64, typename Nal, typename Rows, typename Sinfo, typename Also, typename Body>
+void each_segment(const std::string& op, const Arr<uint8_t>& es, const Arr<int64_t>& es_off, const Arr<int64_t>& cap,
+                  const Arr<int64_t>& info, const Arr<int64_t>& pes, int64_t max_pes, int64_t max_nal, Nal& nal,
+                  Rows& au, Rows& aframes, Sinfo& sinfo, bool sized, Also&& also, Body&& body) {
+  if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument(op + ": max_pes and max_nal must be positive");
+  const es::IndexTables<I32, I64> ix{table_ptr<I32>(nal, "nal"), table_ptr<I32>(au, "au"),
+                                     table_ptr<I32>(aframes, "aframes"), table_ptr<I64>(sinfo, "sinfo")};
+  const EsBatch batch =
+      es_batch(op, es, es_off, cap, info, pes, max_pes, max_nal, {&nal, &au, &aframes, &sinfo}, sized, also);
+  py::gil_scoped_release nogil;
+  parallel_for(es_off.size(), [&](int64_t b) {
+    const es::Segment s = batch.at(b);
+    body(s, es::index_tables_at(ix, s, b), b);
+  }, batch.total);
+}
+const auto no_check = [](int64_t) {};
+
+// One name dictionary of the module: slots or bits of a shared/layout.hpp enum by name, as Python ints.
+struct Named {
+  const char* name;
+  int64_t value;
+};
+py::dict name_dict(py::module_& m, const char* attr, std::initializer_list<Named> items) {
+  py::dict d;
+  for (const Named& n : items) d[n.name] = n.value;
+  m.attr(attr) = d;
+  return d;
 }
 
 SegKey key_from(const int64_t* p) {
@@ -339,10 +382,11 @@ PYBIND11_MODULE(_runtime, m) {
   m.attr("TS_PACKET") = ts::kPacket;
   m.attr("TS_PES_WORDS") = ts::kPesWords;
   {  // the info row and status bits by name (shared/layout.hpp)
-    py::dict d, st;
-    d["status"] = int(ts::kStatus);
-    d["pmt_pid"] = int(ts::kPmtPid);
-    d["n_packets"] = int(ts::kNumPackets);
+    py::dict d = name_dict(m, "TS_INFO", {{"status", ts::kStatus}, {"pmt_pid", ts::kPmtPid},
+                                          {"n_packets", ts::kNumPackets}, {"video_type", ts::kVideoType},
+                                          {"audio_type", ts::kAudioType}, {"payload_bytes", ts::kPayloadBytes},
+                                          {"audio_es_offset", ts::kAudioEsOffset},
+                                          {"id3_es_offset", ts::kId3EsOffset}});
     const char* cls[ts::kClasses] = {"video", "audio", "id3"};
     for (int c = 0; c < ts::kClasses; ++c) {  // the per-class families: base slot + class
       const std::string n = cls[c];
@@ -352,19 +396,9 @@ PYBIND11_MODULE(_runtime, m) {
       d[py::str(n + "_first_pts")] = ts::kFirstPts + c;
       d[py::str(n + "_last_pts")] = ts::kLastPts + c;
     }
-    d["video_type"] = int(ts::kVideoType);
-    d["audio_type"] = int(ts::kAudioType);
-    d["payload_bytes"] = int(ts::kPayloadBytes);
-    d["audio_es_offset"] = int(ts::kAudioEsOffset);
-    d["id3_es_offset"] = int(ts::kId3EsOffset);
-    m.attr("TS_INFO") = d;
-    st["bad_sync"] = int64_t(ts::kBadSync);
-    st["no_pat"] = int64_t(ts::kNoPat);
-    st["no_pmt"] = int64_t(ts::kNoPmt);
-    st["pes_overflow"] = int64_t(ts::kPesOverflow);
-    st["pes_header_error"] = int64_t(ts::kPesHeaderError);
-    st["bad_length"] = int64_t(ts::kBadLength);
-    m.attr("TS_STATUS") = st;
+    name_dict(m, "TS_STATUS", {{"bad_sync", ts::kBadSync}, {"no_pat", ts::kNoPat}, {"no_pmt", ts::kNoPmt},
+                               {"pes_overflow", ts::kPesOverflow}, {"pes_header_error", ts::kPesHeaderError},
+                               {"bad_length", ts::kBadLength}});
   }
   // Batched CPU sample index with the device kernels' layout (docs/ESINDEX.md).
   //   es: flat uint8 (segment b's ES at es_off[b], cap[b] bytes readable); info / pes: demux_batch's
@@ -373,43 +407,24 @@ PYBIND11_MODULE(_runtime, m) {
   m.def("index_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
                           int64_t max_pes, int64_t max_nal, py::array nal, py::array au, py::array aframes,
                           py::array sinfo) {
-    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("index_batch: max_pes and max_nal must be positive");
-    const es::IndexTables<int32_t, int64_t> out{mut_ptr<int32_t>(nal, "nal"), mut_ptr<int32_t>(au, "au"),
-                                                mut_ptr<int32_t>(aframes, "aframes"), mut_ptr<int64_t>(sinfo, "sinfo")};
-    const EsBatch batch = es_batch("index_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal, &au, &aframes, &sinfo}, true, [](int64_t) {});
-    py::gil_scoped_release nogil;
-    parallel_for(es_off.size(), [&](int64_t b) {
-      const es::Segment s = batch.at(b);
-      es::index_segment(s, es::index_tables_at(out, s, b));
-    }, batch.total);
+    each_segment<int32_t, int64_t>("index_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal, au, aframes, sinfo,
+                                   true, no_check, [](const es::Segment& s, const auto& out, int64_t) {
+      es::index_segment(s, out);
+    });
   });
   m.attr("ES_SINFO_WORDS") = es::kSinfoWords;
   m.attr("ES_NAL_WORDS") = es::kNalWords;
   m.attr("ES_AU_WORDS") = es::kAuWords;
   m.attr("ES_APES_WORDS") = es::kApesWords;
   m.attr("ES_DEFAULT_MAX_NAL") = es::kDefaultMaxNal;
-  {
-    py::dict d, st, fl;
-    d["status"] = int(es::kStatus);
-    d["n_nal"] = int(es::kNumNal);
-    d["n_au"] = int(es::kNumAu);
-    d["n_keyframe_aus"] = int(es::kNumKeyframeAus);
-    d["first_keyframe_au"] = int(es::kFirstKeyframeAu);
-    d["n_adts_frames"] = int(es::kNumAdtsFrames);
-    d["audio_sample_rate"] = int(es::kAudioSampleRate);
-    d["audio_channels"] = int(es::kAudioChannels);
-    m.attr("ES_SINFO") = d;
-    st["nal_overflow"] = int64_t(es::kNalOverflow);
-    st["adts_error"] = int64_t(es::kAdtsError);
-    st["unsupported_video"] = int64_t(es::kUnsupportedVideo);
-    m.attr("ES_STATUS") = st;
-    fl["keyframe"] = int(es::kAuKeyframe);
-    fl["sps"] = int(es::kAuSps);
-    fl["pps"] = int(es::kAuPps);
-    fl["aud"] = int(es::kAuAud);
-    m.attr("ES_AU_FLAGS") = fl;
-  }
+  name_dict(m, "ES_SINFO", {{"status", es::kStatus}, {"n_nal", es::kNumNal}, {"n_au", es::kNumAu},
+                            {"n_keyframe_aus", es::kNumKeyframeAus}, {"first_keyframe_au", es::kFirstKeyframeAu},
+                            {"n_adts_frames", es::kNumAdtsFrames}, {"audio_sample_rate", es::kAudioSampleRate},
+                            {"audio_channels", es::kAudioChannels}});
+  name_dict(m, "ES_STATUS", {{"nal_overflow", es::kNalOverflow}, {"adts_error", es::kAdtsError},
+                             {"unsupported_video", es::kUnsupportedVideo}});
+  name_dict(m, "ES_AU_FLAGS", {{"keyframe", es::kAuKeyframe}, {"sps", es::kAuSps}, {"pps", es::kAuPps},
+                               {"aud", es::kAuAud}});
   // Batched CPU remux with the device kernels' layout (docs/REMUX.md): the inputs of index_batch, its
   // four outputs, and per segment a region of remux_out_bytes(cap, max_nal) bytes of `out` at out_off.
   //   vsamples: int32[B, max_pes, ES_VSAMPLE_WORDS]; asamples: int32[B, max_aframes, ES_ASAMPLE_WORDS];
@@ -419,8 +434,7 @@ PYBIND11_MODULE(_runtime, m) {
                           Arr<int64_t> sinfo, int64_t max_aframes, py::array vsamples, py::array asamples,
                           py::array rinfo, py::array out, Arr<int64_t> out_off) {
     const int64_t B = es_off.size();
-    if (max_pes <= 0 || max_nal <= 0 || max_aframes <= 0)
-      throw std::invalid_argument("remux_batch: max_pes, max_nal and max_aframes must be positive");
+    if (max_aframes <= 0) throw std::invalid_argument("remux_batch: max_aframes must be positive");
     const es::RemuxTables tables{mut_ptr<int32_t>(vsamples, "vsamples"), mut_ptr<int32_t>(asamples, "asamples"),
                                  mut_ptr<int64_t>(rinfo, "rinfo")};
     uint8_t* op = mut_ptr<uint8_t>(out, "out");
@@ -428,18 +442,15 @@ PYBIND11_MODULE(_runtime, m) {
     const bool sized = out_off.size() == B && vsamples.size() >= table_words(B, max_pes, es::kVsampleWords) &&
                        asamples.size() >= table_words(B, max_aframes, es::kAsampleWords) &&
                        rinfo.size() >= B * es::kRinfoWords;
-    const EsBatch batch = es_batch("remux_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal, &au, &aframes, &sinfo}, sized, [&](int64_t b) {
+    const auto region_ok = [&](int64_t b) {
       if (oo[b] < 0 || oo[b] + es::remux_out_bytes(cap.data()[b], max_nal) > out.size())
         throw std::invalid_argument("remux_batch: output region out of bounds");
+    };
+    each_segment<const int32_t, const int64_t>("remux_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal, au,
+                                               aframes, sinfo, sized, region_ok,
+                                               [&](const es::Segment& s, const auto& ix, int64_t b) {
+      es::remux_segment(s, ix, max_aframes, es::remux_tables_at(tables, s, max_aframes, b), op + oo[b]);
     });
-    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
-    py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
-      const es::Segment s = batch.at(b);
-      es::remux_segment(s, es::index_tables_at(ix, s, b), max_aframes, es::remux_tables_at(tables, s, max_aframes, b),
-                        op + oo[b]);
-    }, batch.total);
   });
   m.def("remux_out_bytes", py::vectorize(&es::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
@@ -451,26 +462,14 @@ PYBIND11_MODULE(_runtime, m) {
   m.attr("ES_DEFAULT_MAX_AFRAMES") = es::kDefaultMaxAframes;
   m.attr("ES_REMUX_TILE") = es::kRemuxTile;
   m.attr("ES_OUT_ALIGN") = es::kOutAlign;
-  {
-    py::dict d, st, fl;
-    d["status"] = int(es::kRStatus);
-    d["video_payload_bytes"] = int(es::kVideoPayloadBytes);
-    d["n_vsamples"] = int(es::kNumVsamples);
-    d["audio_box_offset"] = int(es::kAudioBoxOffset);
-    d["audio_payload_bytes"] = int(es::kAudioPayloadBytes);
-    d["n_aframes"] = int(es::kNumAframes);
-    d["video_base_dts"] = int(es::kVideoBaseDts);
-    d["audio_base_pts"] = int(es::kAudioBasePts);
-    m.attr("ES_RINFO") = d;
-    st["truncated"] = int64_t(es::kTruncated);
-    st["aframe_overflow"] = int64_t(es::kAframeOverflow);
-    st["bad_timestamps"] = int64_t(es::kBadTimestamps);
-    st["unsupported_video"] = int64_t(es::kRemuxUnsupportedVideo);
-    m.attr("ES_RSTATUS") = st;
-    fl["sync"] = int64_t(es::kSampleSync);
-    fl["non_sync"] = int64_t(es::kSampleNonSync);
-    m.attr("ES_SAMPLE_FLAGS") = fl;
-  }
+  name_dict(m, "ES_RINFO", {{"status", es::kRStatus}, {"video_payload_bytes", es::kVideoPayloadBytes},
+                            {"n_vsamples", es::kNumVsamples}, {"audio_box_offset", es::kAudioBoxOffset},
+                            {"audio_payload_bytes", es::kAudioPayloadBytes}, {"n_aframes", es::kNumAframes},
+                            {"video_base_dts", es::kVideoBaseDts}, {"audio_base_pts", es::kAudioBasePts}});
+  name_dict(m, "ES_RSTATUS", {{"truncated", es::kTruncated}, {"aframe_overflow", es::kAframeOverflow},
+                              {"bad_timestamps", es::kBadTimestamps},
+                              {"unsupported_video", es::kRemuxUnsupportedVideo}});
+  name_dict(m, "ES_SAMPLE_FLAGS", {{"sync", es::kSampleSync}, {"non_sync", es::kSampleNonSync}});
 
   // Batched CPU codec configuration with the device kernel's layout (docs/INITSEGMENT.md): the inputs of
   // index_batch and its four outputs.
@@ -479,54 +478,31 @@ PYBIND11_MODULE(_runtime, m) {
                            int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au, Arr<int32_t> aframes,
                            Arr<int64_t> sinfo, int64_t max_ps, py::array cinfo, py::array ps) {
     const int64_t B = es_off.size();
-    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("config_batch: max_pes and max_nal must be positive");
     if (!es::max_ps_ok(max_ps))
       throw std::invalid_argument("config_batch: max_ps must be a positive multiple of 16 up to 1024");
     int32_t* ci = mut_ptr<int32_t>(cinfo, "cinfo");
     uint8_t* pp = mut_ptr<uint8_t>(ps, "ps");
     const bool sized = cinfo.size() >= B * es::kCinfoWords && ps.size() >= es::ps_bytes(B, max_ps);
-    const EsBatch batch = es_batch("config_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
-    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
-    py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
-      const es::Segment s = batch.at(b);
-      es::config_segment(s, es::index_tables_at(ix, s, b), max_ps, pp + es::ps_bytes(b, max_ps),
-                         ci + b * es::kCinfoWords);
-    }, batch.total);
+    each_segment<const int32_t, const int64_t>("config_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal, au,
+                                               aframes, sinfo, sized, no_check,
+                                               [&](const es::Segment& s, const auto& ix, int64_t b) {
+      es::config_segment(s, ix, max_ps, pp + es::ps_bytes(b, max_ps), ci + b * es::kCinfoWords);
+    });
   });
   m.attr("ES_CINFO_WORDS") = es::kCinfoWords;
   m.attr("ES_DEFAULT_MAX_PS") = es::kDefaultMaxPs;
-  {
-    py::dict d, st;
-    d["status"] = int(es::kCStatus);
-    d["sps_nal"] = int(es::kCSpsNal);
-    d["sps_bytes"] = int(es::kCSpsBytes);
-    d["sps_rbsp_bytes"] = int(es::kCSpsRbspBytes);
-    d["pps_nal"] = int(es::kCPpsNal);
-    d["pps_bytes"] = int(es::kCPpsBytes);
-    d["profile_idc"] = int(es::kCProfileIdc);
-    d["profile_compat"] = int(es::kCProfileCompat);
-    d["level_idc"] = int(es::kCLevelIdc);
-    d["chroma_format_idc"] = int(es::kCChromaFormatIdc);
-    d["bit_depth_luma"] = int(es::kCBitDepthLuma);
-    d["bit_depth_chroma"] = int(es::kCBitDepthChroma);
-    d["width"] = int(es::kCWidth);
-    d["height"] = int(es::kCHeight);
-    d["sar_width"] = int(es::kCSarWidth);
-    d["sar_height"] = int(es::kCSarHeight);
-    d["aac_object_type"] = int(es::kCAacObjectType);
-    d["aac_rate_index"] = int(es::kCAacRateIndex);
-    d["aac_channel_config"] = int(es::kCAacChannelConfig);
-    m.attr("ES_CINFO") = d;
-    st["no_sps"] = int(es::kNoSps);
-    st["no_pps"] = int(es::kNoPps);
-    st["ps_overflow"] = int(es::kPsOverflow);
-    st["bad_sps"] = int(es::kBadSps);
-    st["unsupported_video"] = int(es::kConfigUnsupportedVideo);
-    st["no_audio_config"] = int(es::kNoAudioConfig);
-    m.attr("ES_CSTATUS") = st;
-  }
+  name_dict(m, "ES_CINFO", {{"status", es::kCStatus}, {"sps_nal", es::kCSpsNal}, {"sps_bytes", es::kCSpsBytes},
+                            {"sps_rbsp_bytes", es::kCSpsRbspBytes}, {"pps_nal", es::kCPpsNal},
+                            {"pps_bytes", es::kCPpsBytes}, {"profile_idc", es::kCProfileIdc},
+                            {"profile_compat", es::kCProfileCompat}, {"level_idc", es::kCLevelIdc},
+                            {"chroma_format_idc", es::kCChromaFormatIdc}, {"bit_depth_luma", es::kCBitDepthLuma},
+                            {"bit_depth_chroma", es::kCBitDepthChroma}, {"width", es::kCWidth},
+                            {"height", es::kCHeight}, {"sar_width", es::kCSarWidth}, {"sar_height", es::kCSarHeight},
+                            {"aac_object_type", es::kCAacObjectType}, {"aac_rate_index", es::kCAacRateIndex},
+                            {"aac_channel_config", es::kCAacChannelConfig}});
+  name_dict(m, "ES_CSTATUS", {{"no_sps", es::kNoSps}, {"no_pps", es::kNoPps}, {"ps_overflow", es::kPsOverflow},
+                              {"bad_sps", es::kBadSps}, {"unsupported_video", es::kConfigUnsupportedVideo},
+                              {"no_audio_config", es::kNoAudioConfig}});
 
   // Batched CPU HEVC configuration with the device kernel's layout (docs/INITSEGMENT.md): the inputs of
   // config_batch.
@@ -536,58 +512,34 @@ PYBIND11_MODULE(_runtime, m) {
                                 Arr<int32_t> aframes, Arr<int64_t> sinfo, int64_t max_ps, py::array hinfo,
                                 py::array hps) {
     const int64_t B = es_off.size();
-    if (max_pes <= 0 || max_nal <= 0)
-      throw std::invalid_argument("hevc_config_batch: max_pes and max_nal must be positive");
     if (!es::max_ps_ok(max_ps))
       throw std::invalid_argument("hevc_config_batch: max_ps must be a positive multiple of 16 up to 1024");
     int32_t* hi = mut_ptr<int32_t>(hinfo, "hinfo");
     uint8_t* hp = mut_ptr<uint8_t>(hps, "hps");
     const bool sized = hinfo.size() >= B * es::kHinfoWords && hps.size() >= es::hps_bytes(B, max_ps);
-    const EsBatch batch = es_batch("hevc_config_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
-    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
-    py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
-      const es::Segment s = batch.at(b);
-      es::hevc_config_segment(s, es::index_tables_at(ix, s, b), max_ps, hp + es::hps_bytes(b, max_ps),
-                              hi + b * es::kHinfoWords);
-    }, batch.total);
+    each_segment<const int32_t, const int64_t>("hevc_config_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal,
+                                               au, aframes, sinfo, sized, no_check,
+                                               [&](const es::Segment& s, const auto& ix, int64_t b) {
+      es::hevc_config_segment(s, ix, max_ps, hp + es::hps_bytes(b, max_ps), hi + b * es::kHinfoWords);
+    });
   });
   m.attr("ES_HINFO_WORDS") = es::kHinfoWords;
   m.attr("ES_HPS_ROWS") = es::kHpsRows;
-  {
-    py::dict d, st;
-    d["status"] = int(es::kHStatus);
-    d["vps_nal"] = int(es::kHVpsNal);
-    d["vps_bytes"] = int(es::kHVpsBytes);
-    d["sps_nal"] = int(es::kHSpsNal);
-    d["sps_bytes"] = int(es::kHSpsBytes);
-    d["sps_rbsp_bytes"] = int(es::kHSpsRbspBytes);
-    d["pps_nal"] = int(es::kHPpsNal);
-    d["pps_bytes"] = int(es::kHPpsBytes);
-    d["profile_space"] = int(es::kHProfileSpace);
-    d["tier_flag"] = int(es::kHTierFlag);
-    d["profile_idc"] = int(es::kHProfileIdc);
-    d["profile_compat"] = int(es::kHProfileCompat);
-    d["constraint_hi"] = int(es::kHConstraintHi);
-    d["constraint_lo"] = int(es::kHConstraintLo);
-    d["level_idc"] = int(es::kHLevelIdc);
-    d["num_temporal_layers"] = int(es::kHNumTemporalLayers);
-    d["temporal_id_nested"] = int(es::kHTemporalIdNested);
-    d["chroma_format_idc"] = int(es::kHChromaFormatIdc);
-    d["bit_depth_luma"] = int(es::kHBitDepthLuma);
-    d["bit_depth_chroma"] = int(es::kHBitDepthChroma);
-    d["width"] = int(es::kHWidth);
-    d["height"] = int(es::kHHeight);
-    m.attr("ES_HINFO") = d;
-    st["no_vps"] = int(es::kHNoVps);
-    st["no_sps"] = int(es::kHNoSps);
-    st["no_pps"] = int(es::kHNoPps);
-    st["ps_overflow"] = int(es::kHPsOverflow);
-    st["bad_sps"] = int(es::kHBadSps);
-    st["not_hevc"] = int(es::kHNotHevc);
-    m.attr("ES_HSTATUS") = st;
-  }
+  name_dict(m, "ES_HINFO", {{"status", es::kHStatus}, {"vps_nal", es::kHVpsNal}, {"vps_bytes", es::kHVpsBytes},
+                            {"sps_nal", es::kHSpsNal}, {"sps_bytes", es::kHSpsBytes},
+                            {"sps_rbsp_bytes", es::kHSpsRbspBytes}, {"pps_nal", es::kHPpsNal},
+                            {"pps_bytes", es::kHPpsBytes}, {"profile_space", es::kHProfileSpace},
+                            {"tier_flag", es::kHTierFlag}, {"profile_idc", es::kHProfileIdc},
+                            {"profile_compat", es::kHProfileCompat}, {"constraint_hi", es::kHConstraintHi},
+                            {"constraint_lo", es::kHConstraintLo}, {"level_idc", es::kHLevelIdc},
+                            {"num_temporal_layers", es::kHNumTemporalLayers},
+                            {"temporal_id_nested", es::kHTemporalIdNested},
+                            {"chroma_format_idc", es::kHChromaFormatIdc}, {"bit_depth_luma", es::kHBitDepthLuma},
+                            {"bit_depth_chroma", es::kHBitDepthChroma}, {"width", es::kHWidth},
+                            {"height", es::kHHeight}});
+  name_dict(m, "ES_HSTATUS", {{"no_vps", es::kHNoVps}, {"no_sps", es::kHNoSps}, {"no_pps", es::kHNoPps},
+                              {"ps_overflow", es::kHPsOverflow}, {"bad_sps", es::kHBadSps},
+                              {"not_hevc", es::kHNotHevc}});
 
   // Batched CPU SAMPLE-AES decryption in place with the device kernel's result (docs/SAMPLEAES.md): the
   // inputs of remux_batch, of which es and the length column of nal are rewritten.
@@ -598,50 +550,34 @@ PYBIND11_MODULE(_runtime, m) {
                                    Arr<int32_t> au, Arr<int32_t> aframes, Arr<int64_t> sinfo, Arr<uint32_t> drk,
                                    Arr<uint8_t> iv, Arr<uint8_t> enable, py::array sainfo) {
     const int64_t B = es_off.size();
-    if (max_pes <= 0 || max_nal <= 0)
-      throw std::invalid_argument("sample_decrypt_batch: max_pes and max_nal must be positive");
     uint8_t* ep = mut_ptr<uint8_t>(es_rw, "es");
-    int32_t* np = mut_ptr<int32_t>(nal_rw, "nal");
     int64_t* sa = mut_ptr<int64_t>(sainfo, "sainfo");
     const Arr<uint8_t> es(es_rw);  // the same bytes: es_rw is contiguous uint8
     if (es.data() != ep) throw std::invalid_argument("sample_decrypt_batch: es must be a contiguous uint8 array");
     const bool sized = drk.size() >= B * es::kAesRoundKeyWords && iv.size() >= B * es::kAesBlock &&
                        enable.size() >= B && sainfo.size() >= B * es::kSaWords;
-    const EsBatch batch = es_batch("sample_decrypt_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal_rw, &au, &aframes, &sinfo}, sized, [](int64_t) {});
-    const es::IndexTables<int32_t, const int64_t> ix{np, const_cast<int32_t*>(au.data()),
-                                                     const_cast<int32_t*>(aframes.data()), sinfo.data()};
+    const int64_t* eo = es_off.data();
     const uint32_t* rk = drk.data();
     const uint8_t *ivp = iv.data(), *en = enable.data();
-    py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
+    each_segment<int32_t, const int64_t>("sample_decrypt_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal_rw,
+                                         au, aframes, sinfo, sized, no_check,
+                                         [&](const es::Segment& s, const auto& ix, int64_t b) {
       int64_t* row = sa + b * es::kSaWords;
       if (!en[b]) {
         std::fill(row, row + es::kSaWords, 0);
         return;
       }
-      const es::Segment s = batch.at(b);
-      es::sample_decrypt_segment(s, ep + batch.es_off[b], es::index_tables_at(ix, s, b), rk + b * es::kAesRoundKeyWords,
-                                 ivp + b * es::kAesBlock, row);
-    }, batch.total);
+      es::sample_decrypt_segment(s, ep + eo[b], ix, rk + b * es::kAesRoundKeyWords, ivp + b * es::kAesBlock, row);
+    });
   });
   m.attr("ES_SAINFO_WORDS") = es::kSaWords;
   m.attr("ES_SA_ROUND") = es::kSaRound;
-  {
-    py::dict d, st;
-    d["status"] = int(es::kSaStatus);
-    d["protected_nals"] = int(es::kSaProtectedNals);
-    d["removed_bytes"] = int(es::kSaRemovedBytes);
-    d["video_blocks"] = int(es::kSaVideoBlocks);
-    d["audio_frames"] = int(es::kSaAudioFrames);
-    d["audio_blocks"] = int(es::kSaAudioBlocks);
-    m.attr("ES_SAINFO") = d;
-    st["truncated"] = int64_t(es::kSaTruncated);
-    st["unsupported_video"] = int64_t(es::kSaUnsupportedVideo);
-    st["unsupported_audio"] = int64_t(es::kSaUnsupportedAudio);
-    st["partial_audio"] = int64_t(es::kSaPartialAudio);
-    m.attr("ES_SASTATUS") = st;
-  }
+  name_dict(m, "ES_SAINFO", {{"status", es::kSaStatus}, {"protected_nals", es::kSaProtectedNals},
+                             {"removed_bytes", es::kSaRemovedBytes}, {"video_blocks", es::kSaVideoBlocks},
+                             {"audio_frames", es::kSaAudioFrames}, {"audio_blocks", es::kSaAudioBlocks}});
+  name_dict(m, "ES_SASTATUS", {{"truncated", es::kSaTruncated}, {"unsupported_video", es::kSaUnsupportedVideo},
+                               {"unsupported_audio", es::kSaUnsupportedAudio},
+                               {"partial_audio", es::kSaPartialAudio}});
 
   // Batched CPU caption extraction with the device kernels' layout (docs/CAPTIONS.md): the inputs of
   // config_batch and an enable byte per segment (0: fill values and an all-zero ccinfo row).
@@ -653,7 +589,6 @@ PYBIND11_MODULE(_runtime, m) {
                             py::array ccsamples, py::array ccpts, py::array ccbytes, py::array cc608,
                             py::array ccinfo) {
     const int64_t B = es_off.size();
-    if (max_pes <= 0 || max_nal <= 0) throw std::invalid_argument("caption_batch: max_pes and max_nal must be positive");
     if (!es::max_cc_ok(max_cc)) throw std::invalid_argument("caption_batch: max_cc must be 1 to 2048");
     const es::CcTables t{mut_ptr<int32_t>(ccsamples, "ccsamples"), mut_ptr<int64_t>(ccpts, "ccpts"),
                          mut_ptr<uint8_t>(ccbytes, "ccbytes"), mut_ptr<uint8_t>(cc608, "cc608"),
@@ -661,15 +596,12 @@ PYBIND11_MODULE(_runtime, m) {
     const bool sized = enable.size() >= B && ccsamples.size() >= table_words(B, max_cc, es::kCcRowWords) &&
                        ccpts.size() >= B * max_cc && ccbytes.size() >= B * max_cc * es::kCcSlotBytes &&
                        cc608.size() >= B * max_cc * 2 * es::kCcFieldBytes && ccinfo.size() >= B * es::kCcInfoWords;
-    const EsBatch batch = es_batch("caption_batch", es, es_off, cap, info, pes, max_pes, max_nal,
-                                   {&nal, &au, &aframes, &sinfo}, sized, [](int64_t) {});
-    const es::IndexTables<const int32_t, const int64_t> ix{nal.data(), au.data(), aframes.data(), sinfo.data()};
     const uint8_t* en = enable.data();
-    py::gil_scoped_release nogil;
-    parallel_for(B, [&](int64_t b) {
-      const es::Segment s = batch.at(b);
-      es::caption_segment(s, es::index_tables_at(ix, s, b), en[b] != 0, max_cc, es::cc_tables_at(t, max_cc, b));
-    }, batch.total);
+    each_segment<const int32_t, const int64_t>("caption_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal, au,
+                                               aframes, sinfo, sized, no_check,
+                                               [&](const es::Segment& s, const auto& ix, int64_t b) {
+      es::caption_segment(s, ix, en[b] != 0, max_cc, es::cc_tables_at(t, max_cc, b));
+    });
   });
   m.attr("ES_CCINFO_WORDS") = es::kCcInfoWords;
   m.attr("ES_CCROW_WORDS") = es::kCcRowWords;
@@ -678,32 +610,15 @@ PYBIND11_MODULE(_runtime, m) {
   m.attr("ES_CC_FIELD_BYTES") = es::kCcFieldBytes;
   m.attr("ES_CC_DEFAULT_MAX") = es::kDefaultMaxCc;
   m.attr("ES_CC_MAX_LIMIT") = es::kMaxCcLimit;
-  {
-    py::dict d, row, st;
-    d["status"] = int(es::kCiStatus);
-    d["n_sei"] = int(es::kCiNumSei);
-    d["n_samples"] = int(es::kCiNumSamples);
-    d["n_triples"] = int(es::kCiNumTriples);
-    d["field1_pairs"] = int(es::kCiField1Pairs);
-    d["field2_pairs"] = int(es::kCiField2Pairs);
-    d["first_pts"] = int(es::kCiFirstPts);
-    d["last_pts"] = int(es::kCiLastPts);
-    m.attr("ES_CCINFO") = d;
-    row["nal"] = int(es::kCrNal);
-    row["au"] = int(es::kCrAu);
-    row["size"] = int(es::kCrSize);
-    row["cc_count"] = int(es::kCrCount);
-    row["order"] = int(es::kCrOrder);
-    row["field1_pairs"] = int(es::kCrField1Pairs);
-    row["field2_pairs"] = int(es::kCrField2Pairs);
-    row["flags"] = int(es::kCrFlags);
-    m.attr("ES_CCROW") = row;
-    st["truncated"] = int64_t(es::kCcTruncated);
-    st["unsupported_video"] = int64_t(es::kCcUnsupportedVideo);
-    st["cc_overflow"] = int64_t(es::kCcOverflow);
-    st["sei_clipped"] = int64_t(es::kCcSeiClipped);
-    m.attr("ES_CCSTATUS") = st;
-  }
+  name_dict(m, "ES_CCINFO", {{"status", es::kCiStatus}, {"n_sei", es::kCiNumSei}, {"n_samples", es::kCiNumSamples},
+                             {"n_triples", es::kCiNumTriples}, {"field1_pairs", es::kCiField1Pairs},
+                             {"field2_pairs", es::kCiField2Pairs}, {"first_pts", es::kCiFirstPts},
+                             {"last_pts", es::kCiLastPts}});
+  name_dict(m, "ES_CCROW", {{"nal", es::kCrNal}, {"au", es::kCrAu}, {"size", es::kCrSize}, {"cc_count", es::kCrCount},
+                            {"order", es::kCrOrder}, {"field1_pairs", es::kCrField1Pairs},
+                            {"field2_pairs", es::kCrField2Pairs}, {"flags", es::kCrFlags}});
+  name_dict(m, "ES_CCSTATUS", {{"truncated", es::kCcTruncated}, {"unsupported_video", es::kCcUnsupportedVideo},
+                               {"cc_overflow", es::kCcOverflow}, {"sei_clipped", es::kCcSeiClipped}});
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

@@ -56,10 +56,11 @@ class EsIndex:
 
 
 class BatchPlan:
-    """What :func:`index_batch`, ``remux_batch`` and ``config_batch`` settle before their launch, once: the batch's
-    arrays with the ES ranges checked (``op`` names the caller in every message), one allocation
-    per result table on the batch's device, and for the device path the launch rules, the tile
-    space and the packed descriptors."""
+    """What every op on a demuxed batch settles before its launch, once: the batch's arrays with
+    the ES ranges checked (``op`` names the caller in every message), one allocation per result
+    table on the batch's device, and for the device path the launch rules, the tile space and the
+    packed descriptors.  :func:`index_batch` takes it as it is; the ops behind it take an
+    :class:`IndexedBatch`."""
 
     __slots__ = ("op", "es", "eo", "cap", "B", "max_pes", "dev")
 
@@ -99,6 +100,41 @@ class BatchPlan:
         np.cumsum((sized + tile - 1) // tile, out=tile_prefix[1:])
         arrays["tp"] = tile_prefix
         return pack_to_device(arrays, self.dev), int(tile_prefix[-1])
+
+
+class IndexedBatch(BatchPlan):
+    """A :class:`BatchPlan` that also holds the batch's index: what ``remux_batch``,
+    ``config_batch``, ``hevc_config_batch``, ``sample_decrypt_batch`` and ``caption_batch`` check
+    and hand to their native call.  The batch and its index are on one device, the four index
+    tables have the shapes of this batch, ``es`` is a contiguous one-dimensional uint8 tensor and
+    ``nal`` contiguous, and the ES ranges lie inside ``es``."""
+
+    __slots__ = ("res", "ix", "max_nal")
+
+    def __init__(self, op: str, res: DemuxResult, ix: EsIndex, caps: Sequence[int]):
+        B, max_pes, max_nal, rt = len(res.es_offs), int(res.pes.shape[2]), int(ix.nal.shape[1]), _rt()
+        if ix.nal.device != res.es.device:
+            raise ValueError(f"{op}: the batch and its index must be on one device")
+        if res.es.dtype != torch.uint8 or res.es.dim() != 1 or not res.es.is_contiguous() or not ix.nal.is_contiguous():
+            raise ValueError(f"{op}: es must be a contiguous one-dimensional uint8 tensor, nal contiguous")
+        if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
+                or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
+                or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
+            raise ValueError(f"{op}: the index does not belong to this batch")
+        super().__init__(op, res, caps)
+        self.res, self.ix, self.max_nal = res, ix, max_nal
+
+    def host_args(self) -> tuple:
+        """The eleven arguments every runtime entry point on an indexed batch starts with, as numpy views."""
+        res, ix = self.res, self.ix
+        return (res.es.numpy(), self.eo, self.cap, res.info.numpy(), res.pes.numpy(), self.max_pes, self.max_nal,
+                ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy())
+
+    def device_args(self, d: Dict[str, torch.Tensor]) -> tuple:
+        """The same eleven as tensors for ``_C``; ``d`` holds :meth:`on_device`'s ``eo`` and ``cap``."""
+        res, ix = self.res, self.ix
+        return (res.es, d["eo"], d["cap"], res.info, res.pes, self.max_pes, self.max_nal, ix.nal, ix.au, ix.aframes,
+                ix.sinfo)
 
 
 def index_batch(res: DemuxResult, caps: Sequence[int], max_nal: int = DEFAULT_MAX_NAL) -> EsIndex:

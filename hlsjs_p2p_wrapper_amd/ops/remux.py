@@ -27,7 +27,7 @@ import torch
 from ._native import device as _dev
 from ._native import runtime as _rt
 from .desc import check_ranges
-from .esindex import BatchPlan, EsIndex
+from .esindex import EsIndex, IndexedBatch
 from .tsdemux import DemuxResult
 
 RINFO = {"status": 0, "video_payload_bytes": 1, "n_vsamples": 2, "audio_box_offset": 3, "audio_payload_bytes": 4,
@@ -90,37 +90,30 @@ def remux_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], out: torch.T
     of :func:`remux_out_bytes` bytes (:func:`layout_out` lays them out) of which only the box
     headers and payloads are written."""
     oo = np.asarray(out_offs, dtype=np.int64)
-    B, max_pes, dev, rt = len(res.es_offs), int(res.pes.shape[2]), res.es.device, _rt()
-    max_nal = int(ix.nal.shape[1])
     max_aframes = int(max_aframes)
     if max_aframes <= 0:
         raise ValueError("remux_batch: max_aframes must be positive")
     if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous():
         raise ValueError("remux_batch: out must be a contiguous one-dimensional uint8 tensor")
-    if out.device != dev or ix.nal.device != dev:
+    if out.device != res.es.device:
         raise ValueError("remux_batch: the batch, its index and out must be on one device")
-    if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
-            or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
-            or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
-        raise ValueError("remux_batch: the index does not belong to this batch")
-    plan = BatchPlan("remux_batch", res, caps)
-    region = remux_out_bytes(plan.cap, max_nal)
+    batch = IndexedBatch("remux_batch", res, ix, caps)
+    B, max_pes, max_nal, rt = batch.B, batch.max_pes, batch.max_nal, _rt()
+    region = remux_out_bytes(batch.cap, max_nal)
     check_ranges("remux_batch", "output", oo, region, out.numel())
     order = np.argsort(oo, kind="stable")
     if np.any(oo[order][1:] < (oo + region)[order][:-1]):
         raise ValueError("remux_batch: output regions overlap")
-    rx = Remuxed(plan.table(0, RINFO_WORDS, torch.int64), plan.table(max_pes, rt.ES_VSAMPLE_WORDS),
-                 plan.table(max_aframes, rt.ES_ASAMPLE_WORDS), out, oo)
-    if dev.type == "cpu":
-        rt.remux_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
-                       ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), max_aframes,
-                       rx.vsamples.numpy(), rx.asamples.numpy(), rx.rinfo.numpy(), out.numpy(), oo)
+    rx = Remuxed(batch.table(0, RINFO_WORDS, torch.int64), batch.table(max_pes, rt.ES_VSAMPLE_WORDS),
+                 batch.table(max_aframes, rt.ES_ASAMPLE_WORDS), out, oo)
+    if batch.dev.type == "cpu":
+        rt.remux_batch(*batch.host_args(), max_aframes, rx.vsamples.numpy(), rx.asamples.numpy(), rx.rinfo.numpy(),
+                       out.numpy(), oo)
         return rx
-    tile = _dev().remux_tile_bytes()
-    d, total_tiles = plan.on_device(region, "output region", tile, oo=("output", oo, OUT_ALIGN))
-    scratch = torch.empty(_dev().remux_scratch_words(B, max_nal, max_aframes), dtype=torch.int32, device=dev)
+    d, total_tiles = batch.on_device(region, "output region", _dev().remux_tile_bytes(), oo=("output", oo, OUT_ALIGN))
+    scratch = torch.empty(_dev().remux_scratch_words(B, max_nal, max_aframes), dtype=torch.int32, device=batch.dev)
     if B:
-        _dev().remux(res.es, d["eo"], d["cap"], d["tp"], total_tiles, res.info, res.pes, max_pes, max_nal, ix.nal,
-                     ix.au, ix.aframes, ix.sinfo, max_aframes, scratch, rx.vsamples, rx.asamples, rx.rinfo, out,
-                     d["oo"])
+        a = batch.device_args(d)  # the tile space goes behind es, eo and cap
+        _dev().remux(*a[:3], d["tp"], total_tiles, *a[3:], max_aframes, scratch, rx.vsamples, rx.asamples, rx.rinfo,
+                     out, d["oo"])
     return rx

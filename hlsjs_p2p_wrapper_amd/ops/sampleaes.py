@@ -28,7 +28,7 @@ from . import aes
 from ._native import device as _dev
 from ._native import runtime as _rt
 from .desc import pack_to_device
-from .esindex import BatchPlan, EsIndex
+from .esindex import EsIndex, IndexedBatch
 from .tsdemux import DemuxResult
 
 SAINFO = {"status": 0, "protected_nals": 1, "removed_bytes": 2, "video_blocks": 3, "audio_frames": 4,
@@ -63,24 +63,16 @@ def sample_decrypt_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], key
     ``keys[i]`` / ``ivs[i]`` are 16 bytes each; ``enable[i]`` false leaves segment i alone with an
     all-zero ``sainfo`` row (its key and IV may be ``None``).  Writes ``res.es`` and the length
     column of ``ix.nal``."""
-    B, max_pes, dev, rt = len(res.es_offs), int(res.pes.shape[2]), res.es.device, _rt()
-    max_nal = int(ix.nal.shape[1])
+    B = len(res.es_offs)
     if len(keys) != B or len(ivs) != B or (enable is not None and len(enable) != B):
         raise ValueError("sample_decrypt_batch: one key, one IV and one enable flag per segment")
-    if ix.nal.device != dev:
-        raise ValueError("sample_decrypt_batch: the batch and its index must be on one device")
-    if res.es.dtype != torch.uint8 or res.es.dim() != 1 or not res.es.is_contiguous() or not ix.nal.is_contiguous():
-        raise ValueError("sample_decrypt_batch: es must be a contiguous one-dimensional uint8 tensor, nal contiguous")
-    if tuple(ix.nal.shape) != (B, max_nal, rt.ES_NAL_WORDS) or tuple(ix.au.shape) != (B, max_pes, rt.ES_AU_WORDS) \
-            or tuple(ix.aframes.shape) != (B, max_pes, rt.ES_APES_WORDS) \
-            or tuple(ix.sinfo.shape) != (B, rt.ES_SINFO_WORDS):
-        raise ValueError("sample_decrypt_batch: the index does not belong to this batch")
-    if np.any(np.asarray(caps, dtype=np.int64) >= 2 ** 31):  # NAL rows hold int32 offsets on either device
+    batch = IndexedBatch("sample_decrypt_batch", res, ix, caps)
+    if np.any(batch.cap >= 2 ** 31):  # NAL rows hold int32 offsets on either device
         raise ValueError("sample_decrypt_batch: a segment's ES must be below 2 GiB")
     en = np.ones(B, dtype=np.uint8) if enable is None else np.asarray([bool(e) for e in enable], dtype=np.uint8)
     drk = np.zeros((B, 44), dtype=np.uint32)
     iv = np.zeros((B, 16), dtype=np.uint8)
-    on_gpu = dev.type != "cpu"
+    on_gpu = batch.dev.type != "cpu"
     for i in range(B):
         if not en[i]:
             continue
@@ -89,17 +81,13 @@ def sample_decrypt_batch(res: DemuxResult, ix: EsIndex, caps: Sequence[int], key
         # the kernel takes little-endian column words, the host big-endian ones
         drk[i] = aes.round_keys_le(bytes(keys[i])) if on_gpu else aes.round_keys(bytes(keys[i]))
         iv[i] = np.frombuffer(bytes(ivs[i]), dtype=np.uint8)
-    plan = BatchPlan("sample_decrypt_batch", res, caps)
-    sa = SampleAes(plan.table(0, SAINFO_WORDS, torch.int64))
+    sa = SampleAes(batch.table(0, SAINFO_WORDS, torch.int64))
     if not on_gpu:
-        rt.sample_decrypt_batch(res.es.numpy(), plan.eo, plan.cap, res.info.numpy(), res.pes.numpy(), max_pes, max_nal,
-                                ix.nal.numpy(), ix.au.numpy(), ix.aframes.numpy(), ix.sinfo.numpy(), drk, iv, en,
-                                sa.sainfo.numpy())
+        _rt().sample_decrypt_batch(*batch.host_args(), drk, iv, en, sa.sainfo.numpy())
         return sa
-    d, _ = plan.on_device(plan.cap, "ES", 0)
+    d, _ = batch.on_device(batch.cap, "ES", 0)
     if B:
-        k = pack_to_device({"drk": drk, "iv": iv, "en": en}, dev)
-        tdl, isb = aes.device_tables(dev)
-        _dev().sample_aes_decrypt(res.es, d["eo"], d["cap"], res.info, res.pes, max_pes, max_nal, ix.nal, ix.au,
-                                  ix.aframes, ix.sinfo, k["drk"], k["iv"], k["en"], tdl, isb, sa.sainfo)
+        k = pack_to_device({"drk": drk, "iv": iv, "en": en}, batch.dev)
+        tdl, isb = aes.device_tables(batch.dev)
+        _dev().sample_aes_decrypt(*batch.device_args(d), k["drk"], k["iv"], k["en"], tdl, isb, sa.sainfo)
     return sa
