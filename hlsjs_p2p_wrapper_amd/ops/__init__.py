@@ -1,11 +1,12 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
-``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``): import the submodule you need.  The
+``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``): import the submodule you need.  The
 entry points of the sample index, of the remux, of the two codec configurations, of the SAMPLE-AES
-decrypt and of the caption extraction are also reachable from the package (``ops.index_batch``,
+decrypt, of the caption extraction and of the fragmented-MP4 demux are also reachable from the package
+(``ops.index_batch``,
 ``ops.EsIndex``, ``ops.remux_batch``,
 ``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
 ``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``, ``ops.caption_batch``,
-``ops.Captions``), resolved on first use."""
+``ops.Captions``, ``ops.mp4_demux_batch``, ``ops.Mp4Demux``, ``ops.Mp4Track``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
@@ -13,7 +14,8 @@ _CODECCONFIG = ("config_batch", "CodecConfig")
 _HEVCCONFIG = ("hevc_config_batch", "HevcConfig")
 _SAMPLEAES = ("sample_decrypt_batch", "SampleAes")
 _CAPTIONS = ("caption_batch", "Captions")
-__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS)
+_MP4DEMUX = ("mp4_demux_batch", "Mp4Demux", "Mp4Track")
+__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX)
 
 
 def __getattr__(name):
@@ -41,4 +43,8 @@ def __getattr__(name):
         from . import captions
 
         return getattr(captions, name)
+    if name in _MP4DEMUX:
+        from . import mp4demux
+
+        return getattr(mp4demux, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

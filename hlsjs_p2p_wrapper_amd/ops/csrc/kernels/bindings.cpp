@@ -274,6 +274,43 @@ void cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, i
   hip_ok(D::launch_cc_extract(a), "cc_extract launch");
 }
 
+// Demux of fragmented-MP4 segments (mp4_demux.hip): segment i is buf[off[i], off[i] + clamp(len[i], 0,
+// cap[i])) (the Python wrapper has checked off + cap against buf), tracks int64[B, 2, 8]; ten output
+// tables, info / pes in ts_demux's layout and nal / au / aframes / sinfo in es_index's.
+void mp4_demux(Tensor buf, Tensor off, Tensor len, Tensor cap, Tensor tracks, int64_t max_pes, int64_t max_nal,
+               int64_t max_moof, int64_t max_run, int64_t max_emsg, Tensor minfo, Tensor msamples, Tensor runs,
+               Tensor emsg, Tensor info, Tensor pes, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo) {
+  namespace mp4 = hlsp2p::mp4;
+  const int64_t B = off.numel();
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff && max_nal > 0 && max_nal <= 0x7fffffff,
+              "mp4_demux: max_pes / max_nal out of range");
+  TORCH_CHECK(mp4::max_rows_ok(max_moof) && mp4::max_rows_ok(max_run) && mp4::max_rows_ok(max_emsg),
+              "mp4_demux: max_moof / max_run / max_emsg must be 1 to 256");
+  const D::Mp4DemuxArgs a{
+      .buf = check<uint8_t>(buf, "buf"), .buf_numel = buf.numel(),
+      .off = check<int64_t>(off, "off"),
+      .len = check<int64_t>(len, "len", B),
+      .cap = check<int64_t>(cap, "cap", B),
+      .tracks = check<int64_t>(tracks, "tracks", B * mp4::kTracks * mp4::kTrackWords),
+      .nseg = static_cast<int>(B),
+      .lim = {max_pes, max_nal, max_moof, max_run, max_emsg},
+      .t = {check<int64_t>(minfo, "minfo", B * mp4::kMinfoWords),
+            check<int32_t>(msamples, "msamples", hlsp2p::table_words(B, mp4::kTracks * max_pes, mp4::kMsampleWords)),
+            check<int64_t>(runs, "runs", hlsp2p::table_words(B, max_run, mp4::kRunWords)),
+            check<int64_t>(emsg, "emsg", hlsp2p::table_words(B, max_emsg, mp4::kEmsgWords)),
+            check<int64_t>(info, "info", B * ts::kInfoWords),
+            check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+            {check<int32_t>(nal, "nal", hlsp2p::table_words(B, max_nal, es_::kNalWords)),
+             check<int32_t>(au, "au", hlsp2p::table_words(B, max_pes, es_::kAuWords)),
+             check<int32_t>(aframes, "aframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+             check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords)}},
+      .stream = stream()};
+  same_device(buf, {off, len, cap, tracks, minfo, msamples, runs, emsg, info, pes, nal, au, aframes, sinfo});
+  aligned16({{buf, "buf"}, {msamples, "msamples"}, {runs, "runs"}, {emsg, "emsg"}, {nal, "nal"}, {au, "au"},
+             {aframes, "aframes"}});
+  hip_ok(D::launch_mp4_demux(a), "mp4_demux launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -413,6 +450,10 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("cc_extract(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, Tensor enable, int max_cc, Tensor(a!) scratch, "
         "Tensor(b!) ccsamples, Tensor(c!) ccpts, Tensor(d!) ccbytes, Tensor(e!) cc608, Tensor(f!) ccinfo) -> ()");
+  m.def("mp4_demux(Tensor buf, Tensor off, Tensor len, Tensor cap, Tensor tracks, int max_pes, int max_nal, "
+        "int max_moof, int max_run, int max_emsg, Tensor(a!) minfo, Tensor(b!) msamples, Tensor(c!) runs, "
+        "Tensor(d!) emsg, Tensor(e!) info, Tensor(f!) pes, Tensor(g!) nal, Tensor(h!) au, Tensor(i!) aframes, "
+        "Tensor(j!) sinfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -427,6 +468,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("hevc_config", &hevc_config);
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
   m.impl("cc_extract", &cc_extract);
+  m.impl("mp4_demux", &mp4_demux);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -467,6 +509,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cc_extract", &cc_extract);
   m.def("cc_scratch_words", [](int64_t nseg, int64_t max_nal) { return es_::cc_scratch(nseg, max_nal).end; },
         py::arg("nseg"), py::arg("max_nal"));
+  m.def("mp4_demux", &mp4_demux);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("segment_copy", &segment_copy);

@@ -164,6 +164,18 @@ struct CcExtractArgs {
 };
 hipError_t launch_cc_extract(const CcExtractArgs& a);
 
+struct Mp4DemuxArgs {
+  const uint8_t* buf;  // segment i is buf[off[i], off[i] + clamp(len[i], 0, cap[i])), only read; off 16-byte aligned
+  int64_t buf_numel;
+  const int64_t *off, *len, *cap;
+  const int64_t* tracks;  // nseg x mp4::kTracks x mp4::kTrackWords
+  int nseg;
+  mp4::Limits lim;  // max_pes, max_nal positive; max_moof, max_run, max_emsg mp4::max_rows_ok
+  mp4::Tables t;    // every table 16-byte aligned; runs is also the scratch between the first two kernels
+  hipStream_t stream;
+};
+hipError_t launch_mp4_demux(const Mp4DemuxArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

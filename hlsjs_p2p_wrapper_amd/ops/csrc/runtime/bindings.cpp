@@ -26,6 +26,7 @@
 #include "es.hpp"
 #include "hevc.hpp"
 #include "locator.hpp"
+#include "mp4.hpp"
 #include "planner.hpp"
 #include "remux.hpp"
 #include "sampleaes.hpp"
@@ -619,6 +620,89 @@ PYBIND11_MODULE(_runtime, m) {
                             {"field2_pairs", es::kCrField2Pairs}, {"flags", es::kCrFlags}});
   name_dict(m, "ES_CCSTATUS", {{"truncated", es::kCcTruncated}, {"unsupported_video", es::kCcUnsupportedVideo},
                                {"cc_overflow", es::kCcOverflow}, {"sei_clipped", es::kCcSeiClipped}});
+
+  // Batched CPU fragmented-MP4 demux with the device kernels' layout (docs/FMP4DEMUX.md): segment b
+  // is buf[off[b], off[b] + len[b]), tracks int64[B, MP4_TRACKS, MP4_TRACK_WORDS].
+  //   minfo: int64[B, MP4_MINFO_WORDS]; msamples: int32[B, MP4_TRACKS, max_pes, MP4_MSAMPLE_WORDS]
+  //   runs: int64[B, max_run, MP4_RUN_WORDS]; emsg: int64[B, max_emsg, MP4_EMSG_WORDS]
+  //   info / pes as demux_batch writes them, nal / au / aframes / sinfo as index_batch does
+  m.def("mp4_demux_batch", [](Arr<uint8_t> buf, Arr<int64_t> off, Arr<int64_t> len, Arr<int64_t> tracks,
+                              int64_t max_pes, int64_t max_nal, int64_t max_moof, int64_t max_run, int64_t max_emsg,
+                              py::array minfo, py::array msamples, py::array runs, py::array emsg, py::array info,
+                              py::array pes, py::array nal, py::array au, py::array aframes, py::array sinfo) {
+    const int64_t B = off.size();
+    if (max_pes <= 0 || max_nal <= 0 || !mp4::max_rows_ok(max_moof) || !mp4::max_rows_ok(max_run) ||
+        !mp4::max_rows_ok(max_emsg))
+      throw std::invalid_argument("mp4_demux_batch: max_pes and max_nal must be positive, max_moof / max_run / "
+                                  "max_emsg 1 to 256");
+    const mp4::Limits lim{max_pes, max_nal, max_moof, max_run, max_emsg};
+    const mp4::Tables t{mut_ptr<int64_t>(minfo, "minfo"), mut_ptr<int32_t>(msamples, "msamples"),
+                        mut_ptr<int64_t>(runs, "runs"), mut_ptr<int64_t>(emsg, "emsg"), mut_ptr<int64_t>(info, "info"),
+                        mut_ptr<int64_t>(pes, "pes"),
+                        {mut_ptr<int32_t>(nal, "nal"), mut_ptr<int32_t>(au, "au"), mut_ptr<int32_t>(aframes, "aframes"),
+                         mut_ptr<int64_t>(sinfo, "sinfo")}};
+    if (len.size() != B || tracks.size() < B * mp4::kTracks * mp4::kTrackWords || minfo.size() < B * mp4::kMinfoWords ||
+        msamples.size() < table_words(B, mp4::kTracks * max_pes, mp4::kMsampleWords) ||
+        runs.size() < table_words(B, max_run, mp4::kRunWords) || emsg.size() < table_words(B, max_emsg, mp4::kEmsgWords) ||
+        info.size() < B * ts::kInfoWords || pes.size() < ts::pes_words(B, max_pes) ||
+        nal.size() < table_words(B, max_nal, es::kNalWords) || au.size() < table_words(B, max_pes, es::kAuWords) ||
+        aframes.size() < table_words(B, max_pes, es::kApesWords) || sinfo.size() < B * es::kSinfoWords)
+      throw std::invalid_argument("mp4_demux_batch: an argument is too small");
+    const int64_t *o = off.data(), *l = len.data();
+    int64_t total = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (o[b] < 0 || l[b] < 0 || l[b] >= (int64_t(1) << 31) || o[b] + l[b] > buf.size())
+        throw std::invalid_argument("mp4_demux_batch: segment out of bounds");
+      total += l[b];
+    }
+    const uint8_t* base = buf.data();
+    const int64_t* tk = tracks.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      mp4::demux_segment(base + o[b], l[b], tk + b * mp4::kTracks * mp4::kTrackWords, lim, mp4::tables_at(t, lim, b));
+    }, total);
+  });
+  m.attr("MP4_TRACKS") = mp4::kTracks;
+  m.attr("MP4_TRACK_WORDS") = mp4::kTrackWords;
+  m.attr("MP4_MINFO_WORDS") = mp4::kMinfoWords;
+  m.attr("MP4_MINFO_TRACK0") = mp4::kMTrack0;
+  m.attr("MP4_MINFO_TRACK_WORDS") = mp4::kMTrackWords;
+  m.attr("MP4_MSAMPLE_WORDS") = mp4::kMsampleWords;
+  m.attr("MP4_RUN_WORDS") = mp4::kRunWords;
+  m.attr("MP4_EMSG_WORDS") = mp4::kEmsgWords;
+  m.attr("MP4_MAX_BOX_ROWS") = mp4::kMaxBoxRows;
+  m.attr("MP4_DEFAULT_MAX_MOOF") = mp4::kDefaultMaxMoof;
+  m.attr("MP4_DEFAULT_MAX_RUN") = mp4::kDefaultMaxRun;
+  m.attr("MP4_DEFAULT_MAX_EMSG") = mp4::kDefaultMaxEmsg;
+  name_dict(m, "MP4_TRACK", {{"id", mp4::kTkId}, {"kind", mp4::kTkKind}, {"codec_type", mp4::kTkCodecType},
+                             {"nal_length_size", mp4::kTkNalLengthSize}, {"default_duration", mp4::kTkDefDuration},
+                             {"default_size", mp4::kTkDefSize}, {"default_flags", mp4::kTkDefFlags}});
+  name_dict(m, "MP4_KIND", {{"none", mp4::kKindNone}, {"video", mp4::kKindVideo}, {"audio", mp4::kKindAudio}});
+  name_dict(m, "MP4_MINFO", {{"status", mp4::kMStatus}, {"n_moof", mp4::kMNumMoof},
+                             {"first_sequence", mp4::kMFirstSequence}, {"n_run", mp4::kMNumRun},
+                             {"n_other_traf", mp4::kMNumOtherTraf}, {"n_emsg", mp4::kMNumEmsg}});
+  name_dict(m, "MP4_MINFO_TRACK", {{"n_samples", mp4::kMtNumSamples}, {"base_time", mp4::kMtBaseTime},
+                                   {"duration", mp4::kMtDuration}, {"min_pts", mp4::kMtMinPts},
+                                   {"max_pts", mp4::kMtMaxPts}, {"first_sync", mp4::kMtFirstSync}});
+  name_dict(m, "MP4_STATUS", {{"bad_box", mp4::kBadBox}, {"moof_overflow", mp4::kMoofOverflow},
+                              {"emsg_overflow", mp4::kEmsgOverflow}, {"run_overflow", mp4::kRunOverflow},
+                              {"no_tfdt", mp4::kNoTfdt}, {"sample_out_of_range", mp4::kSampleOutOfRange},
+                              {"sample_overflow", mp4::kSampleOverflow}, {"nal_error", mp4::kNalError},
+                              {"bad_timestamps", mp4::kBadTimestamps}});
+  name_dict(m, "MP4_MSAMPLE", {{"size", mp4::kMsSize}, {"duration", mp4::kMsDuration}, {"cts", mp4::kMsCts},
+                               {"flags", mp4::kMsFlags}});
+  name_dict(m, "MP4_RUN", {{"track", mp4::kRnTrack}, {"moof", mp4::kRnMoof}, {"first", mp4::kRnFirst},
+                           {"count", mp4::kRnCount}, {"entries", mp4::kRnEntries}, {"flags", mp4::kRnFlags},
+                           {"traf_run", mp4::kRnTrafRun}, {"default_duration", mp4::kRnDefDuration},
+                           {"default_size", mp4::kRnDefSize}, {"default_flags", mp4::kRnDefFlags},
+                           {"first_flags", mp4::kRnFirstFlags}, {"start", mp4::kRnStart},
+                           {"start_sample", mp4::kRnStartSample}, {"time", mp4::kRnTime},
+                           {"time_sample", mp4::kRnTimeSample}});
+  name_dict(m, "MP4_EMSG", {{"offset", mp4::kEmOffset}, {"size", mp4::kEmSize}, {"version", mp4::kEmVersion},
+                            {"timescale", mp4::kEmTimescale}, {"time", mp4::kEmTime},
+                            {"time_is_delta", mp4::kEmTimeIsDelta}, {"duration", mp4::kEmDuration}, {"id", mp4::kEmId},
+                            {"data_offset", mp4::kEmDataOffset}, {"data_length", mp4::kEmDataLength},
+                            {"is_id3", mp4::kEmIsId3}});
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

@@ -651,4 +651,371 @@ HLSP2P_RULE int64_t cc_status(const Segment& s, const int64_t* sinfo) {
   return st;
 }
 }  // namespace es
+
+// ---------------------------------------------------------------- fragmented MP4 demux (docs/FMP4DEMUX.md)
+// A reader `rd` gives rd.u8(p), byte p of the segment, and rd.be32(p), and is asked only for bytes of [0, n).  Offsets are
+// int64 and wrap like two's complement where a file can make them overflow.
+namespace mp4 {
+constexpr uint32_t fourcc(char a, char b, char c, char d) {
+  return (uint32_t(uint8_t(a)) << 24) | (uint32_t(uint8_t(b)) << 16) | (uint32_t(uint8_t(c)) << 8) | uint32_t(uint8_t(d));
+}
+constexpr uint32_t kMoof = fourcc('m', 'o', 'o', 'f'), kEmsg = fourcc('e', 'm', 's', 'g'), kMfhd = fourcc('m', 'f', 'h', 'd'),
+                   kTraf = fourcc('t', 'r', 'a', 'f'), kTfhd = fourcc('t', 'f', 'h', 'd'), kTfdt = fourcc('t', 'f', 'd', 't'),
+                   kTrun = fourcc('t', 'r', 'u', 'n');
+HLSP2P_RULE int64_t wrap_add(int64_t a, int64_t b) {
+  return static_cast<int64_t>(static_cast<uint64_t>(a) + static_cast<uint64_t>(b));
+}
+HLSP2P_RULE int64_t wrap_sub(int64_t a, int64_t b) {
+  return static_cast<int64_t>(static_cast<uint64_t>(a) - static_cast<uint64_t>(b));
+}
+// big-endian fields: rd.be32(p) is the four bytes at p, for a reader that has a faster way than four u8
+template <class R>
+HLSP2P_RULE uint32_t be32_bytes(R& rd, int64_t p) {
+  return (uint32_t(rd.u8(p)) << 24) | (uint32_t(rd.u8(p + 1)) << 16) | (uint32_t(rd.u8(p + 2)) << 8) | uint32_t(rd.u8(p + 3));
+}
+template <class R>
+HLSP2P_RULE uint32_t be32(R& rd, int64_t p) { return rd.be32(p); }
+template <class R>
+HLSP2P_RULE uint64_t be64(R& rd, int64_t p) {
+  return (uint64_t(be32(rd, p)) << 32) | be32(rd, p + 4);
+}
+
+// The box header at p of [p, limit).  !ok: no box there (fewer than 8 bytes, a 64-bit size of 2^31
+// or more, a size below the header or beyond limit); type is set whenever 8 bytes were there.
+struct Box {
+  bool ok;
+  uint32_t type;
+  int64_t hdr, size;
+};
+template <class R>
+HLSP2P_RULE Box box_at(R& rd, int64_t p, int64_t limit) {
+  Box b = {false, 0, 8, 0};
+  if (limit - p < 8) return b;
+  const uint32_t size32 = be32(rd, p);
+  b.type = be32(rd, p + 4);
+  b.size = size32;
+  if (size32 == 1) {
+    if (limit - p < 16) return b;
+    const uint64_t large = be64(rd, p + 8);
+    if (large >= 0x80000000ull) return b;
+    b.hdr = 16;
+    b.size = static_cast<int64_t>(large);
+  } else if (size32 == 0) {
+    b.size = limit - p;
+  }
+  b.ok = b.size >= b.hdr && b.size <= limit - p;
+  return b;
+}
+
+// The top level of a segment of n bytes: on_moof(k, p, box) / on_emsg(k, p, box) for the k-th of
+// each, in order; every step consumes at least 8 bytes.
+struct TopOut { int64_t status, n_moof, n_emsg; };
+template <class R, class FM, class FE>
+HLSP2P_RULE TopOut top_walk(R& rd, int64_t n, FM&& on_moof, FE&& on_emsg) {
+  TopOut o = {0, 0, 0};
+  int64_t p = 0;
+  while (p < n) {
+    const Box b = box_at(rd, p, n);
+    if (!b.ok) {
+      o.status |= kBadBox;
+      break;
+    }
+    if (b.type == kMoof) on_moof(o.n_moof++, p, b);
+    else if (b.type == kEmsg) on_emsg(o.n_emsg++, p, b);
+    p += b.size;
+  }
+  return o;
+}
+
+// slot of track_ID id among a segment's kTracks configured tracks, -1: none
+HLSP2P_RULE int track_slot(const int64_t* tracks, int64_t id) {
+  for (int s = 0; s < kTracks; ++s)
+    if (tracks[s * kTrackWords + kTkId] > 0 && tracks[s * kTrackWords + kTkId] == id) return s;
+  return -1;
+}
+// the video track is indexed: a NAL-structured codec with a usable length size
+HLSP2P_RULE bool video_indexed(const int64_t* tracks) {
+  const int64_t L = tracks[kTkNalLengthSize];
+  return tracks[kTkId] > 0 && es::video_supported(tracks[kTkCodecType]) && (L == 1 || L == 2 || L == 4);
+}
+
+// One trun of a configured track as moof_walk hands it on.
+struct Run {
+  int track;
+  int64_t count, entries;  // whole entries that fit, and where the first one lies
+  uint32_t flags;          // tr_flags | version << 24
+  int64_t traf_run;        // 0: the first run of its traf
+  uint32_t def_duration, def_size, def_flags;
+  int64_t first_flags;  // -1: absent
+  bool has_start;       // data_offset present, or the first run of its traf
+  int64_t start;
+  bool has_tfdt;  // of its traf
+  int64_t tfdt;
+};
+struct MoofOut { int64_t status, seq, n_other, n_run; };
+HLSP2P_RULE int run_stride(uint32_t flags) { return 4 * __builtin_popcount((flags >> 8) & 0xf); }
+
+// The children of one traf, [p, tend) inside the moof at mp.
+template <class R, class F>
+HLSP2P_RULE void traf_walk(R& rd, int64_t mp, int64_t p, int64_t tend, const int64_t* tracks, int64_t n, MoofOut& o,
+                           F&& on_run) {
+  int slot = -2;  // -2: no usable tfhd so far, -1: a track that is not configured
+  bool seen_tfhd = false, seen_tfdt = false, seen_trun = false, has_tfdt = false;
+  int64_t tfdt = 0, base = mp, traf_run = 0;
+  uint32_t def_duration = 0, def_size = 0, def_flags = 0;
+  while (p < tend) {
+    const Box b = box_at(rd, p, tend);
+    if (!b.ok) {
+      o.status |= kBadBox;
+      break;
+    }
+    const int64_t body = p + b.hdr, bend = p + b.size, len = bend - body;
+    if (b.type == kTfhd && !seen_tfhd) {
+      seen_tfhd = true;
+      const uint32_t f = len >= 8 ? be32(rd, body) & 0xffffffu : 0;
+      const int64_t need = 8 + ((f & 1) ? 8 : 0) + ((f & 2) ? 4 : 0) + ((f & 8) ? 4 : 0) + ((f & 0x10) ? 4 : 0) +
+                           ((f & 0x20) ? 4 : 0);
+      if (len < need) {
+        o.status |= kBadBox;
+      } else {
+        slot = track_slot(tracks, be32(rd, body + 4));
+        int64_t q = body + 8;
+        if (f & 1) {
+          base = static_cast<int64_t>(be64(rd, q));
+          q += 8;
+        }
+        if (f & 2) q += 4;
+        if (slot >= 0) {
+          const int64_t* t = tracks + slot * kTrackWords;
+          def_duration = static_cast<uint32_t>(t[kTkDefDuration]);
+          def_size = static_cast<uint32_t>(t[kTkDefSize]);
+          def_flags = static_cast<uint32_t>(t[kTkDefFlags]);
+        }
+        if (f & 8) {
+          def_duration = be32(rd, q);
+          q += 4;
+        }
+        if (f & 0x10) {
+          def_size = be32(rd, q);
+          q += 4;
+        }
+        if (f & 0x20) def_flags = be32(rd, q);
+      }
+    } else if (b.type == kTfdt && !seen_tfdt && !seen_trun) {
+      seen_tfdt = true;
+      const int version = len >= 8 ? rd.u8(body) : 0;
+      if (len < (version == 0 ? 8 : 12)) {
+        o.status |= kBadBox;
+      } else {
+        tfdt = version == 0 ? static_cast<int64_t>(be32(rd, body + 4)) : static_cast<int64_t>(be64(rd, body + 4));
+        has_tfdt = true;
+      }
+    } else if (b.type == kTrun) {
+      seen_trun = true;
+      if (slot == -2) {
+        o.status |= kBadBox;
+      } else if (slot >= 0) {
+        const uint32_t vf = len >= 8 ? be32(rd, body) : 0;
+        const uint32_t f = vf & 0xffffffu;
+        if (len < 8 + ((f & 1) ? 4 : 0) + ((f & 4) ? 4 : 0)) {
+          o.status |= kBadBox;
+        } else {
+          const uint32_t sample_count = be32(rd, body + 4);
+          int64_t q = body + 8;
+          Run r = {slot, 0, 0, vf, traf_run, def_duration, def_size, def_flags, -1, traf_run == 0, base, has_tfdt, tfdt};
+          if (f & 1) {
+            r.has_start = true;
+            r.start = wrap_add(base, static_cast<int32_t>(be32(rd, q)));
+            q += 4;
+          }
+          if (f & 4) {
+            r.first_flags = be32(rd, q);
+            q += 4;
+          }
+          const int stride = run_stride(f);
+          const int64_t fit = stride ? (bend - q) / stride : n;
+          r.count = sample_count < fit ? sample_count : fit;
+          r.entries = q;
+          if (r.count < sample_count) o.status |= kBadBox;
+          on_run(o.n_run, r);
+          ++o.n_run;
+          ++traf_run;
+        }
+      }
+    }
+    p = bend;
+  }
+  if (slot == -2) o.status |= kBadBox;
+  else if (slot == -1) ++o.n_other;
+  else if (!has_tfdt) o.status |= kNoTfdt;
+}
+
+// The children of the moof box b at mp: on_run(j, run) for the j-th trun of a configured track.
+template <class R, class F>
+HLSP2P_RULE MoofOut moof_walk(R& rd, int64_t mp, const Box& b, const int64_t* tracks, int64_t n, F&& on_run) {
+  MoofOut o = {0, -1, 0, 0};
+  bool seen_mfhd = false;
+  const int64_t mend = mp + b.size;
+  int64_t p = mp + b.hdr;
+  while (p < mend) {
+    const Box c = box_at(rd, p, mend);
+    if (!c.ok) {
+      o.status |= kBadBox;
+      break;
+    }
+    const int64_t body = p + c.hdr, bend = p + c.size;
+    if (c.type == kMfhd && !seen_mfhd) {
+      seen_mfhd = true;
+      if (bend - body >= 8) o.seq = be32(rd, body + 4);
+      else o.status |= kBadBox;
+    } else if (c.type == kTraf) {
+      traf_walk(rd, mp, body, bend, tracks, n, o, on_run);
+    }
+    p = bend;
+  }
+  return o;
+}
+
+// Sample j of a run: each field from its entry, else the run's default.
+struct Sample {
+  uint32_t size, duration, flags;
+  int32_t cts;
+};
+template <class R>
+HLSP2P_RULE Sample sample_at(R& rd, int64_t entries, uint32_t flags, int64_t j, uint32_t def_duration, uint32_t def_size,
+                             uint32_t def_flags, int64_t first_flags) {
+  Sample s = {def_size, def_duration, def_flags, 0};
+  int64_t q = entries + j * run_stride(flags);
+  if (flags & 0x100) {
+    s.duration = be32(rd, q);
+    q += 4;
+  }
+  if (flags & 0x200) {
+    s.size = be32(rd, q);
+    q += 4;
+  }
+  if (flags & 0x400) {
+    s.flags = be32(rd, q);
+    q += 4;
+  }
+  if (flags & 0x800) s.cts = static_cast<int32_t>(be32(rd, q));  // signed in both versions
+  if (j == 0 && first_flags >= 0) s.flags = static_cast<uint32_t>(first_flags);
+  return s;
+}
+// [off, off + size) clamped to the segment's [0, n)
+struct Placed {
+  int64_t off, size;
+  bool clipped;
+};
+HLSP2P_RULE Placed place_sample(int64_t off, uint32_t size, int64_t n) {
+  const int64_t end = wrap_add(off, size);
+  const bool inside = off >= 0 && end >= off && end <= n;
+  const int64_t a = clamp(off, 0, n);
+  const int64_t e = end < off ? n : clamp(end, a, n);
+  return {a, e - a, !inside};
+}
+
+// One step of the length-prefixed walk at q of a sample that ends at `end`: 1: the NAL (s, len);
+// 0: no length field fits any more (clean iff q == end); 2: a length beyond the sample.
+template <class R>
+HLSP2P_RULE int nal_step(R& rd, int64_t q, int64_t end, int L, int64_t& s, int64_t& len) {
+  if (q + L > end) return 0;
+  uint32_t v = 0;
+  for (int i = 0; i < L; ++i) v = (v << 8) | uint32_t(rd.u8(q + i));
+  s = q + L;
+  if (v > end - s) return 2;
+  len = v;
+  return 1;
+}
+
+// 'https://aomedia.org/emsg/ID3', four characters per word
+constexpr int kId3SchemeChars = 28;
+HLSP2P_RULE uint32_t id3_scheme_word(int w) {
+  switch (w) {
+    case 0: return fourcc('h', 't', 't', 'p'); case 1: return fourcc('s', ':', '/', '/');
+    case 2: return fourcc('a', 'o', 'm', 'e'); case 3: return fourcc('d', 'i', 'a', '.');
+    case 4: return fourcc('o', 'r', 'g', '/'); case 5: return fourcc('e', 'm', 's', 'g');
+    case 6: return fourcc('/', 'I', 'D', '3'); default: return 0;
+  }
+}
+// The zero-terminated string at q of [.., bend): the position behind its terminator, -1 when it
+// does not end inside; id3: it is the ID3 scheme, terminator included.
+template <class R>
+HLSP2P_RULE int64_t emsg_string(R& rd, int64_t q, int64_t bend, bool& id3) {
+  bool match = true;
+  for (int i = 0; q < bend; ++q, ++i) {
+    const uint32_t c = rd.u8(q);
+    if (c == 0) {
+      id3 = match && i == kId3SchemeChars;
+      return q + 1;
+    }
+    match = match && i < kId3SchemeChars && c == ((id3_scheme_word(i >> 2) >> (24 - 8 * (i & 3))) & 0xff);
+    if (i >= kId3SchemeChars) i = kId3SchemeChars;  // stays behind the scheme, never overflows
+  }
+  return -1;
+}
+struct Emsg {
+  bool ok;
+  int64_t version, timescale, time, is_delta, duration, id, data_off, data_len, is_id3;
+};
+template <class R>
+HLSP2P_RULE Emsg emsg_parse(R& rd, int64_t p, const Box& b) {
+  Emsg e = {false, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int64_t body = p + b.hdr, bend = p + b.size;
+  if (bend - body < 4) return e;
+  e.version = rd.u8(body);
+  bool id3 = false, other = false;
+  int64_t q;
+  if (e.version == 0) {
+    q = emsg_string(rd, body + 4, bend, id3);
+    if (q >= 0) q = emsg_string(rd, q, bend, other);
+    if (q < 0 || bend - q < 16) return e;
+    e.timescale = be32(rd, q);
+    e.time = be32(rd, q + 4);
+    e.is_delta = 1;
+    e.duration = be32(rd, q + 8);
+    e.id = be32(rd, q + 12);
+    q += 16;
+  } else if (e.version == 1) {
+    if (bend - body < 24) return e;
+    e.timescale = be32(rd, body + 4);
+    e.time = static_cast<int64_t>(be64(rd, body + 8));
+    e.duration = be32(rd, body + 16);
+    e.id = be32(rd, body + 20);
+    q = emsg_string(rd, body + 24, bend, id3);
+    if (q >= 0) q = emsg_string(rd, q, bend, other);
+    if (q < 0) return e;
+  } else {
+    return e;
+  }
+  e.data_off = q;
+  e.data_len = bend - q;
+  e.is_id3 = id3 ? 1 : 0;
+  e.ok = true;
+  return e;
+}
+
+// What the sample pass settles of a run beyond the box walk: where its bytes and its clock start.
+// `run(k)` is recorded run k <= r as a Run.  The start comes from the nearest run of the same traf
+// that has one of its own (the first run of a traf always has); the time from the nearest first run
+// of a traf of the same track that has a tfdt, else 0 at the track's sample 0.
+template <class A>
+HLSP2P_RULE int64_t start_anchor(A&& run, int64_t r) {
+  while (!run(r).has_start) --r;
+  return r;
+}
+template <class A>
+HLSP2P_RULE int64_t time_anchor(A&& run, int64_t r) {
+  const int track = run(r).track;
+  for (; r >= 0; --r) {
+    const Run k = run(r);
+    if (k.track == track && k.traf_run == 0 && k.has_tfdt) return r;
+  }
+  return -1;
+}
+// A duration as msamples holds it: fits == false stores 0 and flags bad_timestamps
+HLSP2P_RULE es::Delta32 duration32(uint32_t d) {
+  return d <= 0x7fffffffu ? es::Delta32{static_cast<int32_t>(d), true} : es::Delta32{0, false};
+}
+}  // namespace mp4
 }  // namespace hlsp2p

@@ -263,6 +263,93 @@ constexpr CcScratch cc_scratch(int64_t nseg, int64_t max_nal) {
 }
 }  // namespace es
 
+// ---------------------------------------------------------------- fragmented MP4 demux (docs/FMP4DEMUX.md)
+namespace mp4 {
+constexpr int kTracks = 2;  // slot 0 the video track, slot 1 the audio track
+constexpr int64_t kDefaultMaxMoof = 64, kDefaultMaxRun = 128, kDefaultMaxEmsg = 16;
+constexpr int64_t kMaxBoxRows = 256;  // max_moof, max_run, max_emsg: 1 .. this (a lane per row in one workgroup)
+constexpr bool max_rows_ok(int64_t v) { return v >= 1 && v <= kMaxBoxRows; }
+
+// tracks[] row (int64) [segment][kTracks]: what the init segment says about a track
+constexpr int kTrackWords = 8;
+enum TrackRow : int {
+  kTkId = 0,             // track_ID, <= 0: the slot is empty
+  kTkKind = 1,           // TrackKind
+  kTkCodecType = 2,      // slot 0: 0x1B / 0x24 / 0 (no NAL index); slot 1: 0x0F for mp4a, else 0
+  kTkNalLengthSize = 3,  // 1, 2 or 4 where kTkCodecType is a video type
+  kTkDefDuration = 4, kTkDefSize = 5, kTkDefFlags = 6,  // the trex defaults
+  kTkSpare = 7,
+};
+enum TrackKind : int { kKindNone = 0, kKindVideo = 1, kKindAudio = 2 };
+
+// minfo[] row (int64); the per-track family is kMTrack0 + kMTrackWords * slot + MinfoTrack
+constexpr int kMTrack0 = 6, kMTrackWords = 6;
+constexpr int kMinfoWords = kMTrack0 + kTracks * kMTrackWords;
+enum Minfo : int {
+  kMStatus = 0,
+  kMNumMoof = 1,       // true total
+  kMFirstSequence = 2, // mfhd sequence_number of the first moof, -1: none
+  kMNumRun = 3,        // true total of the configured tracks' trun boxes
+  kMNumOtherTraf = 4,
+  kMNumEmsg = 5,       // true total
+};
+enum MinfoTrack : int {
+  kMtNumSamples = 0,  // true total
+  kMtBaseTime = 1,    // decode time of the track's first sample-bearing traf, -1: none
+  kMtDuration = 2,    // over all samples
+  kMtMinPts = 3, kMtMaxPts = 4,  // over the recorded samples, -1 without one
+  kMtFirstSync = 5,   // among the recorded samples, -1: none
+};
+enum Status : int64_t {
+  kBadBox = 1, kMoofOverflow = 2, kEmsgOverflow = 4, kRunOverflow = 8, kNoTfdt = 16, kSampleOutOfRange = 32,
+  kSampleOverflow = 64, kNalError = 128, kBadTimestamps = 256,
+};
+
+// msamples[] row (int32) [segment][kTracks][max_pes], -1 rows beyond the recorded samples
+constexpr int kMsampleWords = 4;
+enum MsampleRow : int { kMsSize = 0, kMsDuration = 1, kMsCts = 2, kMsFlags = 3 };
+constexpr uint32_t kSampleNonSyncBit = 0x00010000;  // sample_is_non_sync_sample
+
+// runs[] row (int64) [segment][max_run], -1 rows beyond the recorded runs; the sample pass reads it
+constexpr int kRunWords = 16;
+enum RunRow : int {
+  kRnTrack = 0, kRnMoof = 1,
+  kRnFirst = 2,    // the run's first sample among its track's samples
+  kRnCount = 3,    // whole entries that fit the box
+  kRnEntries = 4,  // offset of the first entry in the segment
+  kRnFlags = 5,    // tr_flags | version << 24
+  kRnTrafRun = 6,  // 0: the first run of its traf
+  kRnDefDuration = 7, kRnDefSize = 8, kRnDefFlags = 9,  // tfhd, else trex
+  kRnFirstFlags = 10,                                   // first_sample_flags, -1: absent
+  kRnStart = 11, kRnStartSample = 12,  // sample s of the run starts at kRnStart + sizes of [kRnStartSample, s)
+  kRnTime = 13, kRnTimeSample = 14,    // ... and is decoded at kRnTime + durations of [kRnTimeSample, s)
+  kRnSpare = 15,
+};
+
+// emsg[] row (int64) [segment][max_emsg], one per top-level emsg box, a dropped or unrecorded row all -1
+constexpr int kEmsgWords = 12;
+enum EmsgRow : int {
+  kEmOffset = 0, kEmSize = 1, kEmVersion = 2, kEmTimescale = 3,
+  kEmTime = 4,         // presentation_time (v1) or presentation_time_delta (v0)
+  kEmTimeIsDelta = 5,
+  kEmDuration = 6, kEmId = 7,
+  kEmDataOffset = 8, kEmDataLength = 9,
+  kEmIsId3 = 10, kEmSpare = 11,
+};
+
+// One segment's output tables, or a batch's.  info / pes / nal / au / aframes / sinfo have the
+// layouts of ts:: and es:: above.
+struct Tables {
+  int64_t* minfo;     // [kMinfoWords]
+  int32_t* msamples;  // [kTracks][max_pes][kMsampleWords]
+  int64_t* runs;      // [max_run][kRunWords]
+  int64_t* emsg;      // [max_emsg][kEmsgWords]
+  int64_t *info, *pes;
+  es::IndexTables<int32_t, int64_t> ix;
+};
+struct Limits { int64_t max_pes, max_nal, max_moof, max_run, max_emsg; };
+}  // namespace mp4
+
 // ---------------------------------------------------------------- CRC-32
 namespace crc {
 constexpr int kGroupBytes = 256;      // data bytes per MFMA output row

@@ -468,6 +468,12 @@ class StreamController:
         self._eos = False
         self._init_levels: set = set()
         self._init_announced: Any = None  # remuxFmp4: the (sps, pps, AudioSpecificConfig) last announced
+        # fragmented MP4 (#EXT-X-MAP, docs/FMP4DEMUX.md): the parsed init segment per (URL, range), the
+        # fragments waiting for one that is loading, its loader, and the ones already announced
+        self._mp4_inits: Dict[Any, Any] = {}
+        self._mp4_waiting: Dict[Any, List[Any]] = {}
+        self._mp4_loaders: Dict[Any, Any] = {}
+        self._mp4_announced: set = set()
         self._starts_cache: Tuple[int, int, List[float]] = (0, 0, [])
         self.fragments_buffered = 0
         self.bytes_buffered = 0
@@ -769,6 +775,14 @@ class StreamController:
         if type(payload) is RemoteSegment:  # fleet player: the node process already transmuxed it
             self.loop.call_soon(self._on_parsed, frag, stats, payload.transmux_result)
             return
+        init_segment = frag.initSegment
+        if init_segment is not None:  # a fragmented-MP4 fragment: its init segment first, once per (URL, range)
+            init = self._mp4_inits.get(init_segment)
+            if init is None:
+                self._load_init_segment(init_segment, (frag, stats, payload, key, iv, sample_key, sample_iv))
+            else:
+                self._submit_mp4(init, frag, stats, payload, key, iv, sample_key, sample_iv)
+            return
         dev = self.hls.transmux_device(payload)
         # a segment a peer sent, delivered before its CRC check (gpuSwarm.deferVerify): the
         # transmux batch verifies it on the way through the decrypt
@@ -778,11 +792,149 @@ class StreamController:
                         bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
                         sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions"))))
 
+    # ------------------------------------------------------------------ fragmented MP4 (docs/FMP4DEMUX.md)
+    def _load_init_segment(self, init_segment: Any, waiter: Any) -> None:
+        """Load and parse the init segment an ``#EXT-X-MAP`` names, once per (URL, range), the way
+        the key loader loads a key: with the default loader, never through the P2P ``fLoader`` (it is
+        no media segment).  The waiting fragments are submitted when it is there; a load or parse
+        failure is a parsing error of each of them, with the usual retry rule."""
+        waiting = self._mp4_waiting.setdefault(init_segment, [])
+        waiting.append(waiter)
+        if len(waiting) > 1:
+            return
+        cfg = self.hls.config
+        loader = cfg.loader(cfg)
+        self._mp4_loaders[init_segment] = loader
+
+        def done(error: Any, event: Any = None) -> None:
+            old = self._mp4_loaders.pop(init_segment, None)
+            init = None
+            if error is None:
+                try:
+                    data = event.currentTarget.response
+                    if not isinstance(data, (bytes, bytearray)):
+                        data = bytes(memoryview(data.numpy() if hasattr(data, "numpy") else data))
+                    if init_segment.byteRangeStartOffset is not None:
+                        data = data[init_segment.byteRangeStartOffset:init_segment.byteRangeEndOffset]
+                    from .mp4init import parse_init
+
+                    init = self._mp4_inits[init_segment] = parse_init(bytes(data))
+                except ValueError as e:
+                    error = e
+            elif old is not None:
+                old.abort()
+            for w in self._mp4_waiting.pop(init_segment, []):
+                if init is not None:
+                    self._submit_mp4(init, *w)
+                else:
+                    self._on_parsed(w[0], w[1], {"error": error, "status": -1})
+
+        loader.load(init_segment.url, "arraybuffer", lambda e, s: done(None, e),
+                    lambda e: done(ValueError("init segment load error")),
+                    lambda e, s: done(ValueError("init segment load timeout")), cfg.fragLoadingTimeOut,
+                    cfg.fragLoadingMaxRetry, cfg.fragLoadingRetryDelay)
+
+    def _submit_mp4(self, init: Any, frag: Fragment, stats: Any, payload: Any, key: Any, iv: Any, sample_key: Any,
+                    sample_iv: Any) -> None:
+        if self.inflight.get((frag.level, frag.sn)) is not frag:
+            return  # aborted while the init segment loaded
+        config = self.hls.config
+        try:
+            job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag,
+                              getattr(payload, "swarm_verify", None), bool(config.get("indexSamples")), False,
+                              sample_key, sample_iv, bool(config.get("enableCEA708Captions")), mp4=init)
+        except ValueError as e:  # SAMPLE-AES (cbcs) fragmented MP4
+            self._on_parsed(frag, stats, {"error": e, "status": -1})
+            return
+        pipeline_for(self.hls.transmux_device(payload), self.loop).submit(job)
+
+    def _on_parsed_mp4(self, frag: Fragment, stats: Any, r: Any) -> None:
+        """A demuxed fragmented-MP4 fragment: the parsing events of hls.js's passthrough remuxer, then
+        the buffer, as for a TS fragment.  The media bytes are the fragment itself (``data2``)."""
+        hls = self.hls
+        key = (frag.level, frag.sn)
+        listening = hls.listening
+        init = r["init"]
+        if frag.initSegment not in self._mp4_announced:  # once per init segment
+            self._mp4_announced.add(frag.initSegment)
+            tracks = {}
+            for name in ("video", "audio"):
+                t = r[name]
+                if t["id"] >= 0:
+                    tracks[name] = {"id": t["id"], "container": name + "/mp4", "codec": t["codec"],
+                                    "initSegment": init.data, "timescale": t["timescale"]}
+            hls.trigger(Events.FRAG_PARSING_INIT_SEGMENT, {"frag": frag, "tracks": tracks})
+        if listening(Events.FRAG_PARSING_METADATA):
+            id3 = [e for e in r["emsg"] if e["is_id3"]]
+            if id3:
+                hls.trigger(Events.FRAG_PARSING_METADATA, {"frag": frag, "samples": id3})
+        if hls.config.get("enableCEA708Captions") and listening(Events.FRAG_PARSING_USERDATA):
+            captions = r.get("captions")
+            if captions is not None and captions["n_samples"] > 0:
+                hls.trigger(Events.FRAG_PARSING_USERDATA, {"frag": frag, "samples": captions})
+        video, audio = r["video"], r["audio"]
+        samples = r.get("samples") if hls.config.get("indexSamples") else None
+        if listening(Events.FRAG_PARSING_DATA):
+            for name, t in (("video", video), ("audio", audio)):
+                scale, nb = t["timescale"] or 1, t["nb"]
+                mean = t["duration"] / nb if nb else 0
+                data = {"frag": frag, "type": name, "data1": None, "data2": r["data"], "nb": nb,
+                        "startDTS": t["base"] / scale, "endDTS": (t["base"] + t["duration"]) / scale,
+                        "startPTS": t["min_pts"] / scale, "endPTS": (t["max_pts"] + mean) / scale}
+                if samples is not None:
+                    data["samples"] = samples
+                hls.trigger(Events.FRAG_PARSING_DATA, data)
+        if listening(Events.FRAG_PARSED):
+            hls.trigger(Events.FRAG_PARSED, {"frag": frag, "independent": video["first_sync"] == 0})
+        lead = video if video["nb"] else audio
+        dur = lead["duration"] / (lead["timescale"] or 1) if lead["nb"] and lead["duration"] > 0 else frag.duration
+        start = frag.start
+        end = start + dur
+        nbytes = int(r["plain_bytes"])
+        if listening(Events.BUFFER_APPENDING):
+            hls.trigger(Events.BUFFER_APPENDING, {"type": "video", "parent": "main", "bytes": nbytes})
+        media = hls.media
+        if media is not None:
+            retain = (r["data"],) if hls.config.get("retainMediaData") else None
+            if retain is not None:
+                media.retain = True
+            media.append(start, end, nbytes, retain)
+        now = self.loop.now()
+        if isinstance(stats, dict):
+            stats["tbuffered"] = now
+            tfirst = stats.get("tfirst")
+            if tfirst is None:
+                tfirst = stats.get("trequest")
+            length = stats.get("length") or 0
+        else:
+            stats.tbuffered = now
+            tfirst = stats.tfirst if stats.tfirst is not None else stats.trequest
+            length = stats.length or 0
+        self.fragLastKbps = round(8 * length / max(now - tfirst, 1e-3))
+        self.inflight.pop(key, None)
+        if self._retry:
+            self._retry.pop(key, None)
+        self.fragPrevious = frag
+        self.fragments_buffered += 1
+        self.bytes_buffered += int(length)
+        if listening(Events.BUFFER_APPENDED):
+            hls.trigger(Events.BUFFER_APPENDED, {"parent": "main", "pending": 0})
+        hls.trigger(Events.FRAG_BUFFERED, {"stats": stats, "frag": frag})
+        self._kick()
+
     def _on_parsed(self, frag: Fragment, stats: Any, r: Any) -> None:  # r: dict-like transmux result
         hls = self.hls
         key = (frag.level, frag.sn)
         if self.inflight.get(key) is not frag:
             return
+        if r.get("container") == "mp4":  # a fragmented-MP4 fragment has a branch of its own
+            if r.get("error") is None:
+                if not r["status"] & 0b100001:  # ops.mp4demux.MSTATUS bad_box | sample_out_of_range
+                    self._on_parsed_mp4(frag, stats, r)
+                    return
+                # ... a damaged one is a parsing error, retried by the rule below
+                r = {"error": ValueError(f"fMP4 demux status {r['status']}"), "status": -1,
+                     "plain_bytes": r["plain_bytes"]}
         if r.get("verify_failed"):
             # the peer's copy was corrupted: nothing was buffered, the node detached the copy and
             # this fragment's next load goes to the CDN -- a transport retry, not a media error

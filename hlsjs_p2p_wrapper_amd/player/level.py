@@ -23,6 +23,15 @@ class DecryptData:
         return self.method in ("AES-128", "SAMPLE-AES") and self.uri is not None and self.key is None
 
 
+@dataclass(frozen=True, slots=True)
+class InitSegment:
+    """The Media Initialization Section an ``#EXT-X-MAP`` tag names: a URL and, with ``BYTERANGE``,
+    the bytes ``[byteRangeStartOffset, byteRangeEndOffset)`` of it."""
+    url: str
+    byteRangeStartOffset: Optional[int] = None
+    byteRangeEndOffset: Optional[int] = None
+
+
 # Bumped whenever a Fragment's ``start`` is REWRITTEN after construction: consumers that
 # cache derived start-time arrays (models.media_map) compare generations instead of trusting
 # list identity -- hls.js rewrites ``frag.start`` in place on PTS realignment.  Building
@@ -43,13 +52,13 @@ class Fragment:
 
     __slots__ = ("url", "sn", "_start", "duration", "level", "cc", "byteRangeStartOffset", "byteRangeEndOffset",
                  "decryptdata", "loaded", "loadCounter", "loadIdx", "autoLevel", "loader", "title",
-                 "programDateTime")
+                 "programDateTime", "initSegment")
 
     def __init__(self, url: str, sn: int, start: float, duration: float, level: int = 0, cc: int = 0,
                  byteRangeStartOffset: Optional[int] = None, byteRangeEndOffset: Optional[int] = None,
                  decryptdata: Optional[DecryptData] = None, loaded: int = 0, loadCounter: int = 0,
                  loadIdx: int = 0, autoLevel: bool = False, loader: Any = None, title: str = "",
-                 programDateTime: Any = None) -> None:
+                 programDateTime: Any = None, initSegment: Optional[InitSegment] = None) -> None:
         self.url = url
         self.sn = sn
         self._start = start
@@ -66,6 +75,7 @@ class Fragment:
         self.loader = loader
         self.title = title
         self.programDateTime = programDateTime
+        self.initSegment = initSegment  # set for a fragmented-MP4 fragment (#EXT-X-MAP), else None
 
     @property
     def start(self) -> float:

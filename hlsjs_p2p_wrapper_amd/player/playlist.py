@@ -3,8 +3,8 @@
 Covers what the engine needs from RFC 8216: ``EXT-X-STREAM-INF`` (BANDWIDTH,
 RESOLUTION, CODECS, NAME), ``EXTINF``, ``EXT-X-TARGETDURATION``,
 ``EXT-X-MEDIA-SEQUENCE``, ``EXT-X-KEY`` (METHOD/URI/IV), ``EXT-X-BYTERANGE``,
-``EXT-X-DISCONTINUITY``, ``EXT-X-ENDLIST``.  Redundant variants (same BANDWIDTH and
-resolution) are grouped into one level with several ``url`` entries, as hls.js's level
+``EXT-X-DISCONTINUITY``, ``EXT-X-ENDLIST``, ``EXT-X-MAP`` (URI, BYTERANGE).  Redundant variants (same
+BANDWIDTH and resolution) are grouped into one level with several ``url`` entries, as hls.js's level
 controller does — each is a separate ``urlId`` track for the peer agent.
 """
 from __future__ import annotations
@@ -13,7 +13,7 @@ import re
 from typing import Dict, List, Optional, Tuple
 from urllib.parse import urljoin
 
-from .level import DecryptData, Fragment, Level, LevelDetails
+from .level import DecryptData, Fragment, InitSegment, Level, LevelDetails
 
 _ATTR = re.compile(r'([A-Z0-9-]+)=("[^"]*"|[^,]*)')
 
@@ -107,6 +107,7 @@ def parse_media(text: str, base_url: str, level_index: int) -> LevelDetails:
     byterange: Optional[Tuple[int, int]] = None
     last_br_end = 0
     live = True
+    init_segment: Optional[InitSegment] = None  # of the #EXT-X-MAP in force
     frags: List[Fragment] = []
     resolve = _resolver(base_url)
     for raw in text.splitlines():
@@ -147,6 +148,15 @@ def parse_media(text: str, base_url: str, level_index: int) -> LevelDetails:
             off = int(offset) if offset else last_br_end
             byterange = (off, off + int(length))
             last_br_end = byterange[1]
+        elif line.startswith("#EXT-X-MAP:"):
+            a = parse_attrs(line[len("#EXT-X-MAP:"):])
+            if "URI" not in a:
+                raise PlaylistError("EXT-X-MAP without URI")
+            rng = (None, None)
+            if a.get("BYTERANGE"):
+                length, _, offset = a["BYTERANGE"].partition("@")
+                rng = (int(offset or 0), int(offset or 0) + int(length))
+            init_segment = InitSegment(urljoin(base_url, a["URI"]), *rng)
         elif line.startswith("#"):
             continue
         else:
@@ -159,6 +169,8 @@ def parse_media(text: str, base_url: str, level_index: int) -> LevelDetails:
                          cc=cc, decryptdata=dd, title=title)
             if byterange is not None:
                 f.byteRangeStartOffset, f.byteRangeEndOffset = byterange
+            if init_segment is not None:
+                f.initSegment = init_segment
             frags.append(f)
             start += duration
             sn += 1

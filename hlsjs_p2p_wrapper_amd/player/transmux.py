@@ -45,15 +45,18 @@ class TransmuxJob:
     ``METHOD=SAMPLE-AES`` fragment is not CBC-encrypted as a whole: its ``key`` and ``iv`` stay
     ``None`` and ``sample_key`` / ``sample_iv`` (16 bytes each) are set instead.  A plain
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
-    code inside the compiled module."""
+    code inside the compiled module.  ``mp4`` (an ``Mp4Init``): the payload is a fragmented-MP4 media
+    segment of that init segment's tracks, not MPEG-TS (``docs/FMP4DEMUX.md``): the batch demuxes it
+    where it lies, ``remux`` is ignored (the fragment already is fMP4) and ``sample_key`` is refused
+    (``cbcs`` is out of scope)."""
 
     __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
-                 "captions")
+                 "captions", "mp4")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
                  index: bool = False, remux: bool = False, sample_key: Optional[bytes] = None,
-                 sample_iv: Optional[bytes] = None, captions: bool = False) -> None:
+                 sample_iv: Optional[bytes] = None, captions: bool = False, mp4: Any = None) -> None:
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -78,6 +81,12 @@ class TransmuxJob:
         self.captions = captions
         # True (implies ``index``): the batch also extracts the CEA-608/708 caption data of this
         # fragment's SEI NAL units (ops/captions.py) and its result gains ``captions``
+        if mp4 is not None and sample_key is not None:
+            raise ValueError("TransmuxJob: SAMPLE-AES (cbcs) fragmented MP4 is not supported")
+        self.mp4 = mp4
+        if mp4 is not None:  # the fragment already is fMP4: no remux, and none that implies the index
+            self.remux = False
+            self.index = bool(index or captions)
 
     def __repr__(self) -> str:
         return f"TransmuxJob(key={'set' if self.key else None}, frag={self.frag!r})"
@@ -160,6 +169,7 @@ class MediaPipeline:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.loop = loop or get_event_loop()
         self._jobs: List[TransmuxJob] = []
+        self._any_mp4 = False  # a submitted job carries an Mp4Init: launch() sets those aside
         self._scheduled = False
         self.segments = 0
         self.bytes_in = 0
@@ -172,6 +182,8 @@ class MediaPipeline:
 
     def submit(self, job: TransmuxJob) -> None:
         self._jobs.append(job)
+        if job.mp4 is not None:
+            self._any_mp4 = True
         if self.auto_flush and not self._scheduled:
             self._scheduled = True
             self.loop.call_soon(self.flush)
@@ -186,17 +198,29 @@ class MediaPipeline:
         jobs, self._jobs = self._jobs, []
         if not jobs:
             return None
+        mp4 = None
+        if self._any_mp4:  # fragmented-MP4 jobs take their own path, in front of the columns
+            self._any_mp4 = False
+            mp4 = self._launch_mp4([j for j in jobs if j.mp4 is not None])
+            jobs = [j for j in jobs if j.mp4 is None]
+            if not jobs:
+                return _Batch([], groups=[], n=0, mp4=mp4)
         try:
             b = self._launch_core(self._job_columns(jobs))
         except Exception as e:  # deliver the failure to every job of the batch
-            return _Batch(jobs, groups=[], error=e, n=len(jobs))
+            return _Batch(jobs, groups=[], error=e, n=len(jobs), mp4=mp4)
         b.jobs = jobs
+        b.mp4 = mp4
         return b
 
     def complete(self, batch: Optional["_Batch"]) -> None:
         """Wait for a launched batch and run the per-fragment callbacks."""
         if batch is None:
             return
+        if batch.mp4 is not None:
+            self._complete_mp4(batch.mp4)
+            if not batch.jobs:
+                return
         if batch.error is not None:
             for j in batch.jobs:  # (a pending receive check is left to the node's own sweep)
                 j.callback({"error": batch.error})
@@ -460,6 +484,91 @@ class MediaPipeline:
             hlens = _to_host(lens) if isinstance(lens, torch.Tensor) else lens
             groups.append(_Group(idx, res, _to_host(res.info), hlens))
         return groups
+
+    # ------------------------------------------------------------------ fragmented MP4 (docs/FMP4DEMUX.md)
+    def _launch_mp4(self, jobs: List[TransmuxJob]) -> "_Mp4Batch":
+        """Enqueue the fragmented-MP4 jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
+        rows, one ``mp4_demux_batch`` per group (the encrypted rows in the decrypt's buffer, the clear
+        ones where they lie) and one ``caption_batch`` over its views when a job of the group asked;
+        ``minfo``, ``info``, ``sinfo``, the ``emsg`` table and the ``ccinfo`` rows are on their way to
+        pinned host memory in front of the event."""
+        from ..ops import mp4demux as _mp4
+
+        try:
+            dev = self.device
+            tensors = [_as_tensor(j.payload) for j in jobs]
+            sizes = [t.numel() for t in tensors]
+            src, src_offs = self._stage(tensors, sizes)
+            offs, nb = np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
+            enc = np.array([j.key is not None for j in jobs], dtype=bool)
+            ok = ~(enc & ((nb <= 0) | (nb % 16 != 0)))
+            self.segments += len(jobs)
+            self.bytes_in += int(nb.sum())
+            work = []
+            e, cl = np.flatnonzero(enc & ok), np.flatnonzero(~enc)
+            if len(e):
+                caps = nb[e]
+                dec_offs, size = _layout(caps)
+                dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+                il = e.tolist()
+                out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
+                                                 [bytes(jobs[i].iv) for i in il], dec, dec_offs)
+                work.append((e, dec, dec_offs, out_len, caps))
+            if len(cl):
+                work.append((cl, src, offs[cl], nb[cl], nb[cl]))
+            groups = []
+            for idx, buf, o, lens, caps in work:
+                il = idx.tolist()
+                md = _mp4.mp4_demux_batch(buf, o, lens, [jobs[i].mp4 for i in il], caps=caps)
+                g = _Mp4Group(idx, md, _to_host(md.minfo), _to_host(md.info), _to_host(md.sinfo), _to_host(md.emsg),
+                              _to_host(lens) if isinstance(lens, torch.Tensor) else lens)
+                asked = [bool(jobs[i].captions) for i in il]
+                if any(asked):
+                    from ..ops import captions as _cc
+
+                    g.cc = _cc.caption_batch(md.as_demux(), md.as_index(), caps, enable=asked)
+                    g.ccinfo = _to_host(g.cc.ccinfo)
+                groups.append(g)
+            ev = self._event() if dev.type == "cuda" and groups else None
+            return _Mp4Batch(jobs, groups, ev, None, np.flatnonzero(~ok))
+        except Exception as e:  # deliver the failure to every fragmented-MP4 job of the batch
+            return _Mp4Batch(jobs, [], None, e, np.zeros(0, dtype=np.int64))
+
+    def _complete_mp4(self, b: "_Mp4Batch") -> None:
+        """Wait for the fragmented-MP4 jobs of a batch and run their callbacks."""
+        from ..ops.mp4demux import EMSG, MINFO
+
+        if b.error is not None:
+            for j in b.jobs:
+                j.callback({"error": b.error, "status": -1, "container": "mp4"})
+            return
+        if b.event is not None:
+            b.event.synchronize()
+            self._free_events.append(b.event)
+        results: List[Any] = [None] * len(b.jobs)
+        for i in b.rejected.tolist():
+            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1,
+                          "container": "mp4"}
+        for g in b.groups:
+            md = g.md
+            minfo, info, sinfo, emsg, hlens = (_np(x) for x in (g.minfo, g.info, g.sinfo, g.emsg, g.hlens))
+            for k, i in enumerate(g.rows.tolist()):
+                job, row, plain = b.jobs[i], minfo[k].tolist(), int(hlens[k])
+                r = {"status": row[MINFO["status"]], "info": {n: row[s] for n, s in MINFO.items()},
+                     "plain_bytes": plain, "container": "mp4", "init": job.mp4, "mp4": md, "index": k,
+                     "video": Mp4TrackView(md, k, 0, row, info[k], job.mp4),
+                     "audio": Mp4TrackView(md, k, 1, row, info[k], job.mp4),
+                     "data": md.buf.narrow(0, int(md.offs[k]), max(plain, 0)),
+                     "emsg": [{n: int(er[s]) for n, s in EMSG.items()} for er in emsg[k] if er[EMSG["offset"]] >= 0]}
+                if plain < 0:
+                    r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
+                if job.index:
+                    r["samples"] = Samples(sinfo[k].tolist(), md.as_index(), k)
+                if g.cc is not None and job.captions:
+                    r["captions"] = CaptionData(g, k)
+                results[i] = r
+        for j, r in zip(b.jobs, results):
+            j.callback(r)
 
     # ------------------------------------------------------------------ completion
     def _rows(self, batch: "_Batch") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -891,6 +1000,72 @@ class Fmp4(_View):
         return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config', 'hevc')} })"
 
 
+class Mp4TrackView(_View):
+    """Read-only mapping of one track of a fragmented-MP4 fragment: ``nb`` (samples), ``base`` (decode
+    time of its first sample-bearing ``traf``), ``duration``, ``min_pts`` / ``max_pts``, ``first_sync``,
+    ``first_pts`` / ``last_pts`` (all in the track's ``timescale``), ``id`` and ``codec`` from the init
+    segment, and ``samples`` / ``pes``: the fragment's rows of the batch's device tables
+    (``msamples``: size, duration, cts, flags; ``pes``: offset in ``data``, pts, dts), viewed on
+    first access."""
+
+    __slots__ = ("_md", "_k", "_t", "_row", "_info", "_init")
+    _FIELDS = {"nb": "n_samples", "base": "base_time", "duration": "duration", "min_pts": "min_pts",
+               "max_pts": "max_pts", "first_sync": "first_sync"}
+
+    def __init__(self, md, k: int, t: int, row, info, init) -> None:
+        self._md, self._k, self._t, self._row, self._info, self._init = md, k, t, row, info, init
+
+    def __getitem__(self, name: str):
+        from ..ops.mp4demux import MINFO_TRACK, MINFO_TRACK0, MINFO_TRACK_WORDS
+
+        kind = ("video", "audio")[self._t]
+        if name in self._FIELDS:
+            return self._row[MINFO_TRACK0 + MINFO_TRACK_WORDS * self._t + MINFO_TRACK[self._FIELDS[name]]]
+        if name == "timescale":
+            return int(self._init.timescale.get(kind, 0))
+        if name in ("first_pts", "last_pts"):
+            return int(self._info[_ts.INFO[f"{kind}_{name}"]])
+        if name == "id":
+            track = getattr(self._init, kind)
+            return track.track_id if track is not None else -1
+        if name == "codec":
+            return getattr(self._init, f"{kind}_codec")
+        if name == "samples":
+            return self._md.msamples[self._k, self._t, :min(self["nb"], self._md.msamples.shape[2])]
+        if name == "pes":
+            return self._md.pes[self._k, self._t, :min(self["nb"], self._md.pes.shape[2])]
+        raise KeyError(name)
+
+    def keys(self):
+        return [*self._FIELDS, "timescale", "first_pts", "last_pts", "id", "codec", "samples", "pes"]
+
+    def __repr__(self) -> str:
+        return f"Mp4TrackView({ {k: self[k] for k in self.keys() if k not in ('samples', 'pes')} })"
+
+
+@dataclass(eq=False)
+class _Mp4Group:
+    """One demux group of the fragmented-MP4 jobs of a batch (its encrypted rows, or its clear ones)."""
+    rows: np.ndarray  # rows of the batch's fragmented-MP4 jobs, in the group's order
+    md: Any  # the group's Mp4Demux, on the device
+    minfo: Any  # its minfo, info, sinfo rows, emsg table and ...
+    info: Any
+    sinfo: Any
+    emsg: Any
+    hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
+    cc: Any = None  # Captions, when a job of the group asked for it, with ...
+    ccinfo: Any = None  # ... its ccinfo rows on the host
+
+
+@dataclass(eq=False)
+class _Mp4Batch:
+    jobs: List[TransmuxJob]
+    groups: List[_Mp4Group]
+    event: Any
+    error: Optional[BaseException]
+    rejected: Any  # jobs whose encrypted payload is not whole AES blocks
+
+
 @dataclass(eq=False)
 class _Group:
     """One demux group of a batch (its encrypted rows, or its clear ones) and what was run on it."""
@@ -928,6 +1103,7 @@ class _Batch:
     start: Any = None  # timing event recorded before the batch's first launch
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
+    mp4: Any = None  # _Mp4Batch: the batch's fragmented-MP4 jobs, which took their own path
 
     # the groups as the benchmark's output dump reads them: derived, nothing is stored twice
     @property

@@ -2,20 +2,22 @@
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
 index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
 (H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
-on a video ES the tool writes itself, and the MFMA CRC with HIP events and reports us / GB/s of input.
+on a video ES the tool writes itself, the fragmented-MP4 demux on segments the tool writes itself (one
+``moof`` and thirty), and the MFMA CRC with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
 """
 import argparse
 import json
+import struct
 
 import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import (aes, captions, codecconfig, crc, esindex, hevcconfig, remux, sampleaes, segment,
-                                       tsdemux)
+from hlsjs_p2p_wrapper_amd.ops import (aes, captions, codecconfig, crc, esindex, hevcconfig, mp4demux, remux, sampleaes,
+                                       segment, tsdemux)
 
 
 def timed(fn, iters):
@@ -107,6 +109,69 @@ def caption_batch_inputs(offs, lens, size, dev, n_au=120, seed=5):
     hres = tsdemux.DemuxResult(torch.from_numpy(info[:1].copy()), torch.from_numpy(pes[:1].copy()),
                                torch.from_numpy(np.concatenate([ves, np.zeros(256, np.uint8)])), np.zeros(1, np.int64))
     return dres, [len(ves)] * B, hres
+
+
+def mp4_segment(moofs, n_video=120, n_audio=188, seed=7):
+    """One fragmented-MP4 segment written by hand: ``n_video`` video samples of three NAL units (an
+    AUD, an SEI-sized unit and a slice, 4-byte lengths) in track 1 and ``n_audio`` audio samples in
+    track 2, spread over ``moofs`` pairs of ``moof`` + ``mdat``, each ``moof`` with one ``traf`` per
+    track (``tfhd``, ``tfdt``, one ``trun`` with every per-sample field and a ``data_offset``)."""
+    rng = np.random.default_rng(seed)
+
+    def box(kind, payload):
+        return struct.pack(">I4s", 8 + len(payload), kind) + payload
+
+    def full(kind, version, flags, payload):
+        return box(kind, struct.pack(">I", (version << 24) | flags) + payload)
+
+    def nal(header, n):
+        body = bytes([header]) + rng.integers(1, 256, n, dtype=np.uint8).tobytes()
+        return struct.pack(">I", len(body)) + body
+
+    video = [nal(0x09, 1) + nal(0x06, 70) + nal(0x65 if i % 30 == 0 else 0x41, 200 + i % 7) for i in range(n_video)]
+    audio = [rng.integers(0, 256, 300 + i % 5, dtype=np.uint8).tobytes() for i in range(n_audio)]
+    out, vt, at = b"", 90000, 48000
+    for k in range(moofs):
+        v = video[n_video * k // moofs:n_video * (k + 1) // moofs]
+        a = audio[n_audio * k // moofs:n_audio * (k + 1) // moofs]
+        v0 = n_video * k // moofs
+
+        def moof(voff, aoff):
+            vrows = b"".join(struct.pack(">IIIi", 3000, len(x), 0x02000000 if (v0 + i) % 30 == 0 else 0x01010000,
+                                         3000 * ((v0 + i) % 3)) for i, x in enumerate(v))
+            arows = b"".join(struct.pack(">IIIi", 1024, len(x), 0x02000000, 0) for x in a)
+            trafs = [box(b"traf", full(b"tfhd", 0, 0x020000, struct.pack(">I", tid)) +
+                         full(b"tfdt", 1, 0, struct.pack(">Q", time)) +
+                         full(b"trun", 0, 0xF01, struct.pack(">Ii", len(rows) // 16, off) + rows))
+                     for tid, time, off, rows in ((1, vt, voff, vrows), (2, at, aoff, arows))]
+            return box(b"moof", full(b"mfhd", 0, 0, struct.pack(">I", k + 1)) + b"".join(trafs))
+
+        size = len(moof(0, 0))
+        vbytes = b"".join(v)
+        out += moof(size + 8, size + 8 + len(vbytes)) + box(b"mdat", vbytes + b"".join(a))
+        vt, at = vt + 3000 * len(v), at + 1024 * len(a)
+    return out
+
+
+def mp4_row(moofs, segs, iters, dev):
+    """``mp4_demux_batch`` on ``segs`` copies of :func:`mp4_segment`: us per call, after checking the
+    totals and segment 0 of the device result against the host implementation."""
+    seg = np.frombuffer(mp4_segment(moofs), np.uint8)
+    stride = (len(seg) + 255) // 256 * 256
+    buf = np.zeros(stride * segs + 256, np.uint8)
+    offs, lens = [stride * i for i in range(segs)], [len(seg)] * segs
+    for o in offs:
+        buf[o:o + len(seg)] = seg
+    tracks = (mp4demux.Mp4Track(1, "video", 0x1B, 4), mp4demux.Mp4Track(2, "audio", 0x0F))
+    d = torch.from_numpy(buf).to(dev)
+    got = mp4demux.mp4_demux_batch(d, offs, lens, tracks)
+    host = mp4demux.mp4_demux_batch(torch.from_numpy(buf[:stride + 256].copy()), offs[:1], lens[:1], tracks)
+    names = ("minfo", "msamples", "runs", "emsg", "info", "pes", "nal", "au", "aframes", "sinfo")
+    assert all(torch.equal(getattr(got, k)[0].cpu(), getattr(host, k)[0]) for k in names), "mp4demux mismatch"
+    mi = got.minfo.cpu()
+    assert mi[:, 0].sum() == 0 and (mi[:, 1] == moofs).all() and (mi[:, 6] == 120).all() and (mi[:, 12] == 188).all() \
+        and (got.sinfo[:, 1].cpu() == 360).all(), "mp4demux totals"
+    return round(timed(lambda: mp4demux.mp4_demux_batch(d, offs, lens, tracks), iters), 1)
 
 
 def main():
@@ -226,6 +291,10 @@ def main():
     hcc = captions.caption_batch(hcr, esindex.index_batch(hcr, ccaps[:1]), ccaps[:1])
     assert all(torch.equal(getattr(cc, k)[0].cpu(), getattr(hcc, k)[0])
                for k in ("ccinfo", "ccsamples", "ccpts", "ccbytes", "cc608")), "captions mismatch"
+    # the fragmented-MP4 demux (boxes, samples, NAL units) on segments of the tool's own: 120 video and
+    # 188 audio samples in one moof + mdat, and the same samples in 30 (the serial top-level chain)
+    res["mp4demux_us"] = mp4_row(1, args.segs, args.iters, dev)
+    res["mp4demux_chunked_us"] = mp4_row(30, args.segs, args.iters, dev)
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
