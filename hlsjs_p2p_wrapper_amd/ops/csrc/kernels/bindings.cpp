@@ -311,6 +311,53 @@ void mp4_demux(Tensor buf, Tensor off, Tensor len, Tensor cap, Tensor tracks, in
   hip_ok(D::launch_mp4_demux(a), "mp4_demux launch");
 }
 
+// cbcs decryption of a demuxed fMP4 batch into a copy (cbcs.hip): src and the five demux tables are
+// only read; dst already holds a copy of every enabled segment at dst_off[i] (the Python wrapper
+// has checked both offset sets against their tensors); per segment two protection rows, two
+// constant IVs, a fallback IV, 44 round-key words (little-endian) and an enable byte.
+void cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor dst, Tensor dst_off, Tensor info, Tensor pes,
+                  Tensor minfo, Tensor msamples, Tensor runs, int64_t max_pes, int64_t max_run, Tensor prot,
+                  Tensor const_iv, Tensor iv, Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int64_t max_range,
+                  int64_t max_blocks, Tensor scratch, Tensor ranges, Tensor cinfo) {
+  namespace mp4 = hlsp2p::mp4;
+  const int64_t B = src_off.numel();
+  TORCH_CHECK(B <= 65535, "cbcs_decrypt: at most 65535 segments per call");
+  TORCH_CHECK(max_pes > 0 && max_pes < (int64_t(1) << mp4::kRgTrackShift) && mp4::max_rows_ok(max_run),
+              "cbcs_decrypt: max_pes / max_run out of range");
+  TORCH_CHECK(mp4::max_range_ok(max_range), "cbcs_decrypt: max_range must be 1 to 65536");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= 0x7fffffff / 16, "cbcs_decrypt: max_blocks out of range");
+  const D::CbcsArgs a{
+      .src = check<uint8_t>(src, "src"), .src_numel = src.numel(),
+      .src_off = check<int64_t>(src_off, "src_off"),
+      .cap = check<int64_t>(cap, "cap", B),
+      .dst = check<uint8_t>(dst, "dst"),
+      .dst_off = check<int64_t>(dst_off, "dst_off", B),
+      .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+      .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+      .minfo = check<int64_t>(minfo, "minfo", B * mp4::kMinfoWords),
+      .runs = check<int64_t>(runs, "runs", hlsp2p::table_words(B, max_run, mp4::kRunWords)),
+      .msamples = check<int32_t>(msamples, "msamples", hlsp2p::table_words(B, mp4::kTracks * max_pes, mp4::kMsampleWords)),
+      .max_pes = max_pes, .max_run = max_run,
+      .prot = check<int64_t>(prot, "prot", B * mp4::kTracks * mp4::kProtWords),
+      .const_iv = check<uint8_t>(const_iv, "const_iv", B * mp4::kTracks * es_::kAesBlock),
+      .iv = check<uint8_t>(iv, "iv", B * es_::kAesBlock),
+      .round_keys = check<uint32_t>(round_keys, "round_keys", B * es_::kAesRoundKeyWords),
+      .enable = check<uint8_t>(enable, "enable", B),
+      .td = check<uint32_t>(td, "td", 256),
+      .isb = check<uint8_t>(isb, "isb", 256),
+      .max_range = max_range, .max_blocks = max_blocks,
+      .scratch = check<int32_t>(scratch, "scratch", mp4::cbcs_scratch(B, max_pes)),
+      .ranges = check<int32_t>(ranges, "ranges", hlsp2p::table_words(B, max_range, mp4::kRangeWords)),
+      .cinfo = check<int64_t>(cinfo, "cinfo", B * mp4::kCbInfoWords),
+      .nseg = static_cast<int>(B), .stream = stream()};
+  TORCH_CHECK(src.data_ptr() != dst.data_ptr(), "cbcs_decrypt cannot run in place");
+  same_device(src, {src_off, cap, dst, dst_off, info, pes, minfo, msamples, runs, prot, const_iv, iv, round_keys, enable,
+                    td, isb, scratch, ranges, cinfo});
+  aligned16({{src, "src"}, {dst, "dst"}, {msamples, "msamples"}, {const_iv, "const_iv"}, {iv, "iv"},
+             {scratch, "scratch"}, {ranges, "ranges"}, {cinfo, "cinfo"}});
+  hip_ok(D::launch_cbcs(a), "cbcs_decrypt launch");
+}
+
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
                   int64_t total_chunks) {
   const int64_t n = src_off.numel();
@@ -454,6 +501,10 @@ TORCH_LIBRARY(hlsp2p, m) {
         "int max_moof, int max_run, int max_emsg, Tensor(a!) minfo, Tensor(b!) msamples, Tensor(c!) runs, "
         "Tensor(d!) emsg, Tensor(e!) info, Tensor(f!) pes, Tensor(g!) nal, Tensor(h!) au, Tensor(i!) aframes, "
         "Tensor(j!) sinfo) -> ()");
+  m.def("cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor(a!) dst, Tensor dst_off, Tensor info, Tensor pes, "
+        "Tensor minfo, Tensor msamples, Tensor runs, int max_pes, int max_run, Tensor prot, Tensor const_iv, Tensor iv, "
+        "Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int max_range, int max_blocks, Tensor(b!) scratch, "
+        "Tensor(c!) ranges, Tensor(d!) cinfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -469,6 +520,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
   m.impl("cc_extract", &cc_extract);
   m.impl("mp4_demux", &mp4_demux);
+  m.impl("cbcs_decrypt", &cbcs_decrypt);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -512,6 +564,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mp4_demux", &mp4_demux);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
+  m.def("cbcs_decrypt", &cbcs_decrypt);
   m.def("segment_copy", &segment_copy);
   m.def("device_cus", &device_cus);
   m.def("h2d_batch", &h2d_batch, pybind11::arg("dst"), pybind11::arg("dst_off"), pybind11::arg("src_ptr"),

@@ -176,6 +176,32 @@ struct Mp4DemuxArgs {
 };
 hipError_t launch_mp4_demux(const Mp4DemuxArgs& a);
 
+struct CbcsArgs {
+  const uint8_t* src;  // the demuxed segments, only read: segment i is src[src_off[i], + clamp(info[i].video_bytes, 0, cap[i]))
+  int64_t src_numel;
+  const int64_t *src_off, *cap;
+  uint8_t* dst;            // 16-byte aligned; holds a copy of every enabled segment at dst_off[i] (16-byte aligned)
+  const int64_t* dst_off;
+  const int64_t *info, *pes, *minfo, *runs;  // launch_mp4_demux's outputs, only read
+  const int32_t* msamples;
+  int64_t max_pes, max_run;
+  const int64_t* prot;         // nseg x mp4::kTracks x mp4::kProtWords
+  const uint8_t* const_iv;     // nseg x mp4::kTracks x 16, 16-byte aligned, padded with zeros
+  const uint8_t* iv;           // nseg x 16, 16-byte aligned: for a track without an IV of its own
+  const uint32_t* round_keys;  // nseg x es::kAesRoundKeyWords, as SampleAesArgs
+  const uint8_t* enable;       // nseg; 0: the segment is left alone, its cinfo row is zero
+  const uint32_t* td;
+  const uint8_t* isb;
+  int64_t max_range;   // mp4::max_range_ok
+  int64_t max_blocks;  // host bound of one segment's cipher blocks: max(cap) / 16
+  int32_t* scratch;    // mp4::cbcs_scratch(nseg, max_pes), 16-byte aligned
+  int32_t* ranges;     // nseg x max_range x mp4::kRangeWords, 16-byte aligned
+  int64_t* cinfo;      // nseg x mp4::kCbInfoWords
+  int nseg;
+  hipStream_t stream;
+};
+hipError_t launch_cbcs(const CbcsArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

@@ -26,9 +26,8 @@
 // to a dword, never beyond the tensor): a box header at any alignment or ending at the segment's
 // last byte is safe, and a read the rules do not allow would return 0, not fault.
 // All byte rules are shared/grammar.hpp (namespace mp4), the same functions runtime/mp4.cpp calls.
-#include "common.h"
-#include "grammar.hpp"
 #include "launch.h"
+#include "mp4_dev.h"
 
 namespace hlsp2p {
 namespace dev {
@@ -38,8 +37,6 @@ constexpr int kMp4Waves = kMp4Threads / 64;
 static_assert(mp4::kMaxBoxRows == kMp4Threads, "a lane per moof, run or emsg row in one round");
 static_assert(mp4::kRunWords % 2 == 0 && mp4::kEmsgWords % 2 == 0, "run and emsg rows are 16-byte vectors");
 static_assert(mp4::kMsampleWords == 4 && es::kNalWords == 4 && es::kAuWords == 4, "16-byte rows");
-
-typedef long long v2l __attribute__((ext_vector_type(2)));
 
 // Passed by value as the first kernel parameter.
 struct Mp4View {
@@ -55,69 +52,9 @@ __device__ __forceinline__ int mp4_segment_bytes(const Mp4View& v, int seg) {
   return static_cast<int>(clamp(v.len[seg], 0, clamp(v.cap[seg], 0, 0x7fffffff)));
 }
 
-// The segment's bytes through a buffer resource of n bytes rounded up to a dword and never beyond
-// the tensor.  u8 keeps the 16 bytes from the last position asked for, so a box header, a trun
-// entry or a NAL's length and header byte cost one load.
-struct SegReader {
-  __amdgpu_buffer_rsrc_t rsrc;
-  int64_t at;
-  v4u w;
-  __device__ __forceinline__ int u8(int64_t p) {
-    if (p < at || p >= at + 16) {
-      at = p;
-      w = load16_unaligned(rsrc, static_cast<int>(p));
-    }
-    const int k = static_cast<int>(p - at);
-    return static_cast<int>((w[k >> 2] >> (8 * (k & 3))) & 0xff);
-  }
-  // four bytes at once: the two dwords around them, one v_alignbyte, one v_perm (bswap)
-  __device__ __forceinline__ uint32_t be32(int64_t p) {
-    if (p < at || p + 4 > at + 16) {
-      at = p;
-      w = load16_unaligned(rsrc, static_cast<int>(p));
-    }
-    const int k = static_cast<int>(p - at), i = k >> 2;  // k <= 12; an unaligned k has i <= 2
-    const uint32_t lo = w[i], hi = i < 3 ? w[i + 1] : 0u;
-    return __builtin_bswap32(__builtin_amdgcn_alignbyte(hi, lo, static_cast<uint32_t>(k & 3)));
-  }
-};
+// the reader (mp4_dev.h) of segment seg of n bytes
 __device__ __forceinline__ SegReader mp4_reader(const Mp4View& v, int seg, int n) {
-  const int64_t off = v.off[seg];
-  int64_t range = (static_cast<int64_t>(n) + 3) & ~int64_t(3);
-  if (range > v.buf_numel - off) range = v.buf_numel - off;
-  if (range < 0) range = 0;
-  const uint64_t base = reinterpret_cast<uint64_t>(v.buf + off);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base));
-  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(base >> 32));
-  const int bytes = __builtin_amdgcn_readfirstlane(static_cast<int>(range));
-  SegReader rd;
-  rd.rsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<uint8_t*>((static_cast<uint64_t>(hi) << 32) | lo), 0,
-                                              bytes, 0x00020000);
-  rd.at = -64;
-  rd.w = v4u{0, 0, 0, 0};
-  return rd;
-}
-
-// inclusive prefix sum of a 64-bit value over the wave64
-__device__ __forceinline__ long long wave_scan64(long long v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const long long t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
-// largest k in [0, K) with first[k] <= i; first ascends and first[0] <= i
-__device__ __forceinline__ int last_le_lds(const long long* first, int K, long long i) {
-  int lo = 0, hi = K;  // the answer is in [lo, hi)
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (first[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
+  return mp4_reader(v.buf, v.buf_numel, v.off[seg], n);
 }
 
 __global__ __launch_bounds__(kMp4Threads) void mp4_boxes_kernel(Mp4View v) {

@@ -21,6 +21,7 @@
 
 #include "aes_host.hpp"
 #include "captions.hpp"
+#include "cbcs.hpp"
 #include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
@@ -703,6 +704,83 @@ PYBIND11_MODULE(_runtime, m) {
                             {"time_is_delta", mp4::kEmTimeIsDelta}, {"duration", mp4::kEmDuration}, {"id", mp4::kEmId},
                             {"data_offset", mp4::kEmDataOffset}, {"data_length", mp4::kEmDataLength},
                             {"is_id3", mp4::kEmIsId3}});
+
+  // Batched CPU cbcs decryption with the device kernels' result (docs/CBCS.md): segment b is
+  // src[src_off[b], + len[b]), only read, and dst[dst_off[b], + len[b]) already holds its copy; a
+  // segment with enable 0 is left alone (all-zero cinfo row, -1 ranges).
+  //   minfo / msamples / runs / info / pes: as mp4_demux_batch wrote them
+  //   prot: int64[B, MP4_TRACKS, CBCS_PROT_WORDS]; const_iv: uint8[B, MP4_TRACKS, 16]; iv: uint8[B, 16]
+  //   drk: uint32[B, 44] (expand_key_dec); ranges: int32[B, max_range, CBCS_RANGE_WORDS]; cinfo: int64[B, CBCS_CINFO_WORDS]
+  m.def("cbcs_decrypt_batch", [](Arr<uint8_t> src, Arr<int64_t> src_off, Arr<int64_t> len, py::array dst_rw,
+                                 Arr<int64_t> dst_off, Arr<int64_t> minfo, Arr<int32_t> msamples, Arr<int64_t> runs,
+                                 Arr<int64_t> info, Arr<int64_t> pes, int64_t max_pes, int64_t max_run,
+                                 Arr<int64_t> prot, Arr<uint8_t> const_iv, Arr<uint8_t> iv, Arr<uint32_t> drk,
+                                 Arr<uint8_t> enable, int64_t max_range, py::array ranges, py::array cinfo) {
+    const int64_t B = src_off.size();
+    if (max_pes <= 0 || !mp4::max_rows_ok(max_run) || !mp4::max_range_ok(max_range))
+      throw std::invalid_argument("cbcs_decrypt_batch: max_pes must be positive, max_run 1 to 256, max_range 1 to 65536");
+    uint8_t* dp = mut_ptr<uint8_t>(dst_rw, "dst");
+    int32_t* rg = mut_ptr<int32_t>(ranges, "ranges");
+    int64_t* ci = mut_ptr<int64_t>(cinfo, "cinfo");
+    if (len.size() != B || dst_off.size() != B || minfo.size() < B * mp4::kMinfoWords ||
+        msamples.size() < table_words(B, mp4::kTracks * max_pes, mp4::kMsampleWords) ||
+        runs.size() < table_words(B, max_run, mp4::kRunWords) || info.size() < B * ts::kInfoWords ||
+        pes.size() < ts::pes_words(B, max_pes) || prot.size() < B * mp4::kTracks * mp4::kProtWords ||
+        const_iv.size() < B * mp4::kTracks * es::kAesBlock || iv.size() < B * es::kAesBlock ||
+        drk.size() < B * es::kAesRoundKeyWords || enable.size() < B ||
+        ranges.size() < table_words(B, max_range, mp4::kRangeWords) || cinfo.size() < B * mp4::kCbInfoWords)
+      throw std::invalid_argument("cbcs_decrypt_batch: an argument is too small");
+    const int64_t *so = src_off.data(), *l = len.data(), *dof = dst_off.data();
+    const uint8_t* en = enable.data();
+    int64_t total = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (!en[b]) continue;
+      if (so[b] < 0 || l[b] < 0 || l[b] >= (int64_t(1) << 31) || so[b] + l[b] > src.size() || dof[b] < 0 ||
+          dof[b] + l[b] > dst_rw.size())
+        throw std::invalid_argument("cbcs_decrypt_batch: segment out of bounds");
+      total += l[b];
+    }
+    const uint8_t* sp = src.data();
+    if (sp == dp) throw std::invalid_argument("cbcs_decrypt_batch: cannot run in place");
+    const int64_t *mi = minfo.data(), *rn = runs.data(), *in = info.data(), *pe = pes.data(), *pr = prot.data();
+    const int32_t* ms = msamples.data();
+    const uint8_t *civ = const_iv.data(), *ivp = iv.data();
+    const uint32_t* rk = drk.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      int32_t* rows = rg + table_words(b, max_range, mp4::kRangeWords);
+      int64_t* row = ci + b * mp4::kCbInfoWords;
+      if (!en[b]) {
+        std::fill(rows, rows + table_words(1, max_range, mp4::kRangeWords), -1);
+        std::fill(row, row + mp4::kCbInfoWords, int64_t(0));
+        return;
+      }
+      const mp4::CbcsDemux md{mi + b * mp4::kMinfoWords, rn + table_words(b, max_run, mp4::kRunWords),
+                              in + b * ts::kInfoWords, pe + ts::pes_words(b, max_pes),
+                              ms + table_words(b, mp4::kTracks * max_pes, mp4::kMsampleWords), max_pes, max_run};
+      mp4::cbcs_segment(sp + so[b], l[b], md, pr + b * mp4::kTracks * mp4::kProtWords,
+                        civ + b * mp4::kTracks * es::kAesBlock, ivp + b * es::kAesBlock, rk + b * es::kAesRoundKeyWords,
+                        max_range, dp + dof[b], rows, row);
+    }, total);
+  });
+  m.attr("CBCS_PROT_WORDS") = mp4::kProtWords;
+  m.attr("CBCS_CINFO_WORDS") = mp4::kCbInfoWords;
+  m.attr("CBCS_RANGE_WORDS") = mp4::kRangeWords;
+  m.attr("CBCS_AUX_WORDS") = mp4::kAuxWords;
+  m.attr("CBCS_TRACK_SHIFT") = mp4::kRgTrackShift;
+  m.attr("CBCS_MAX_RANGE_LIMIT") = mp4::kMaxRangeLimit;
+  m.attr("CBCS_DEFAULT_MAX_RANGE") = mp4::kDefaultMaxRange;
+  name_dict(m, "CBCS_PROT", {{"protected", mp4::kPrProtected}, {"crypt", mp4::kPrCrypt}, {"skip", mp4::kPrSkip},
+                             {"per_sample_iv_size", mp4::kPrIvSize}, {"constant_iv_size", mp4::kPrConstIvSize}});
+  name_dict(m, "CBCS_CINFO", {{"status", mp4::kCbStatus}, {"n_ranges", mp4::kCbNumRanges},
+                              {"video_samples", mp4::kCbVideoSamples}, {"audio_samples", mp4::kCbAudioSamples},
+                              {"video_blocks", mp4::kCbVideoBlocks}, {"audio_blocks", mp4::kCbAudioBlocks},
+                              {"n_senc", mp4::kCbNumSenc}});
+  name_dict(m, "CBCS_STATUS", {{"range_overflow", mp4::kCbRangeOverflow}, {"no_senc", mp4::kCbNoSenc},
+                               {"bad_senc", mp4::kCbBadSenc}, {"demux_damaged", mp4::kCbDemuxDamaged},
+                               {"overlap", mp4::kCbOverlap}});
+  name_dict(m, "CBCS_RANGE", {{"offset", mp4::kRgOffset}, {"length", mp4::kRgLength}, {"sample", mp4::kRgSample},
+                              {"rank", mp4::kRgRank}});
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

@@ -1,7 +1,8 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
-// runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp) and by the gfx950 kernels (kernels/ts_demux.hip,
-// kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip, kernels/sample_aes.hip, kernels/captions.hip).  Plain inline
+// runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp) and by the gfx950
+// kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip,
+// kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -755,10 +756,11 @@ struct Run {
 struct MoofOut { int64_t status, seq, n_other, n_run; };
 HLSP2P_RULE int run_stride(uint32_t flags) { return 4 * __builtin_popcount((flags >> 8) & 0xf); }
 
-// The children of one traf, [p, tend) inside the moof at mp.
-template <class R, class F>
+// The children of one traf, [p, tend) inside the moof at mp; on_other(type, p, box) for a child
+// the demux does not read.
+template <class R, class F, class G>
 HLSP2P_RULE void traf_walk(R& rd, int64_t mp, int64_t p, int64_t tend, const int64_t* tracks, int64_t n, MoofOut& o,
-                           F&& on_run) {
+                           F&& on_run, G&& on_other) {
   int slot = -2;  // -2: no usable tfhd so far, -1: a track that is not configured
   bool seen_tfhd = false, seen_tfdt = false, seen_trun = false, has_tfdt = false;
   int64_t tfdt = 0, base = mp, traf_run = 0;
@@ -842,12 +844,19 @@ HLSP2P_RULE void traf_walk(R& rd, int64_t mp, int64_t p, int64_t tend, const int
           ++traf_run;
         }
       }
+    } else {
+      on_other(b.type, p, b);
     }
     p = bend;
   }
   if (slot == -2) o.status |= kBadBox;
   else if (slot == -1) ++o.n_other;
   else if (!has_tfdt) o.status |= kNoTfdt;
+}
+template <class R, class F>
+HLSP2P_RULE void traf_walk(R& rd, int64_t mp, int64_t p, int64_t tend, const int64_t* tracks, int64_t n, MoofOut& o,
+                           F&& on_run) {
+  traf_walk(rd, mp, p, tend, tracks, n, o, on_run, [](uint32_t, int64_t, const Box&) {});
 }
 
 // The children of the moof box b at mp: on_run(j, run) for the j-th trun of a configured track.
@@ -1016,6 +1025,107 @@ HLSP2P_RULE int64_t time_anchor(A&& run, int64_t r) {
 // A duration as msamples holds it: fits == false stores 0 and flags bad_timestamps
 HLSP2P_RULE es::Delta32 duration32(uint32_t d) {
   return d <= 0x7fffffffu ? es::Delta32{static_cast<int32_t>(d), true} : es::Delta32{0, false};
+}
+
+// ---------------------------------------------------------------- cbcs decryption (docs/CBCS.md)
+constexpr uint32_t kSenc = fourcc('s', 'e', 'n', 'c');
+// Per_Sample_IV_Size / constant_IV_size as the walk uses it: 8 or 16, anything else is 0
+HLSP2P_RULE int iv_bytes(int64_t v) { return v == 8 || v == 16 ? static_cast<int>(v) : 0; }
+
+// The trafs of the moof box b at mp that have a trun of a configured track: on_traf(slot, j0,
+// runs, sp, senc) with the track slot, the traf's runs [j0, j0 + runs) among the moof's (the j of
+// moof_walk) and its first senc child at sp (sp < 0: none), wherever it stands among the children.
+template <class R, class F>
+HLSP2P_RULE void senc_walk(R& rd, int64_t mp, const Box& b, const int64_t* tracks, int64_t n, F&& on_traf) {
+  MoofOut o = {0, -1, 0, 0};
+  const int64_t mend = mp + b.size;
+  int64_t p = mp + b.hdr;
+  while (p < mend) {
+    const Box c = box_at(rd, p, mend);
+    if (!c.ok) break;
+    if (c.type == kTraf) {
+      const int64_t j0 = o.n_run;
+      int slot = -1;
+      int64_t sp = -1;
+      Box senc = {false, 0, 8, 0};
+      traf_walk(rd, mp, p + c.hdr, p + c.size, tracks, n, o, [&](int64_t, const Run& r) { slot = r.track; },
+                [&](uint32_t type, int64_t q, const Box& k) {
+                  if (type == kSenc && sp < 0) {
+                    sp = q;
+                    senc = k;
+                  }
+                });
+      if (o.n_run > j0) on_traf(slot, j0, o.n_run - j0, sp, senc);
+    }
+    p += c.size;
+  }
+}
+
+// The fixed fields of the senc box b at sp.  !ok: the body is too short for them.
+struct SencHead {
+  bool ok;
+  uint32_t flags;
+  int64_t count, at, end;  // sample_count, the first entry, the box end
+};
+template <class R>
+HLSP2P_RULE SencHead senc_head(R& rd, int64_t sp, const Box& b) {
+  const int64_t body = sp + b.hdr, bend = sp + b.size;
+  if (bend - body < 8) return {false, 0, 0, body, bend};
+  return {true, be32(rd, body) & 0xffffffu, static_cast<int64_t>(be32(rd, body + 4)), body + 8, bend};
+}
+template <class R>
+HLSP2P_RULE int64_t be16(R& rd, int64_t p) { return (int64_t(rd.u8(p)) << 8) | rd.u8(p + 1); }
+// The entry at q of a senc that ends at bend: the position behind it, -1 when the box end cuts
+// it; nsub is its subsample_count, -1 when the box has no subsample tables.
+template <class R>
+HLSP2P_RULE int64_t senc_entry(R& rd, int64_t q, int64_t bend, int iv_size, bool subs, int64_t& nsub) {
+  nsub = -1;
+  if (bend - q < iv_size) return -1;
+  int64_t e = q + iv_size;
+  if (subs) {
+    if (bend - e < 2) return -1;
+    nsub = be16(rd, e);
+    e += 2;
+    if (bend - e < 6 * nsub) return -1;
+    e += 6 * nsub;
+  }
+  return e;
+}
+// The protected ranges of the sample at o of z bytes, in order: on_range(offset, length).  sub is
+// where its nsub (clear u16, protected u32) pairs lie; nsub < 0: the sample is one range.  false: a
+// sum runs beyond the sample (bad_senc); the ranges in front of it have been handed on.
+template <class R, class F>
+HLSP2P_RULE bool sample_ranges(R& rd, int64_t o, int64_t z, int64_t sub, int64_t nsub, F&& on_range) {
+  if (nsub < 0) {
+    on_range(o, z);
+    return true;
+  }
+  int64_t q = 0;
+  for (int64_t i = 0; i < nsub; ++i) {
+    const int64_t clear = be16(rd, sub + 6 * i), prot = be32(rd, sub + 6 * i + 2);
+    if (clear > z - q) return false;
+    q += clear;
+    if (prot > z - q) return false;
+    on_range(o + q, prot);
+    q += prot;
+  }
+  return true;
+}
+// The cipher blocks of a range of P bytes under the pattern crypt:skip (skip 0: every block), and
+// where block j lies.  A trailing partial crypt group stays clear; a block that ends with the
+// range is encrypted.
+HLSP2P_RULE int64_t cipher_blocks(int64_t P, int64_t c, int64_t s) {
+  const int64_t nb = P / 16;
+  if (c <= 0 || s <= 0) return nb;
+  return (nb / (c + s)) * c + (nb % (c + s) >= c ? c : 0);
+}
+HLSP2P_RULE int64_t cipher_block_at(int64_t j, int64_t c, int64_t s) {
+  if (c <= 0 || s <= 0) return 16 * j;
+  return 16 * ((j / c) * (c + s) + j % c);
+}
+// two byte spans [a0, a1) and [b0, b1), neither empty, share a byte
+HLSP2P_RULE bool spans_meet(int64_t a0, int64_t a1, int64_t b0, int64_t b1) {
+  return a0 < a1 && b0 < b1 && a0 < b1 && b0 < a1;
 }
 }  // namespace mp4
 }  // namespace hlsp2p

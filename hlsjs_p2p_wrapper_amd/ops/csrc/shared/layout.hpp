@@ -348,6 +348,50 @@ struct Tables {
   es::IndexTables<int32_t, int64_t> ix;
 };
 struct Limits { int64_t max_pes, max_nal, max_moof, max_run, max_emsg; };
+
+// ---- cbcs decryption of a demuxed batch (docs/CBCS.md)
+// protection[] row (int64) [segment][kTracks]: what the init segment's tenc says about a track
+constexpr int kProtWords = 8;
+enum ProtRow : int {
+  kPrProtected = 0,    // 1: the track's samples are looked at
+  kPrCrypt = 1, kPrSkip = 2,  // the pattern in 16-byte blocks; skip 0: every block
+  kPrIvSize = 3,       // Per_Sample_IV_Size: 0, 8 or 16
+  kPrConstIvSize = 4,  // 0, 8 or 16; used when kPrIvSize is 0
+};
+// cinfo[] row (int64); every count is an integer sum
+constexpr int kCbInfoWords = 8;
+enum CbInfo : int {
+  kCbStatus = 0,
+  kCbNumRanges = 1,  // true total of the ranges with a cipher block
+  kCbVideoSamples = 2, kCbAudioSamples = 3,  // samples with a cipher block
+  kCbVideoBlocks = 4, kCbAudioBlocks = 5,    // cipher blocks, the unrecorded ranges' included
+  kCbNumSenc = 6,    // senc boxes that were read
+  kCbSpare = 7,
+};
+enum CbStatus : int64_t { kCbRangeOverflow = 1, kCbNoSenc = 2, kCbBadSenc = 4, kCbDemuxDamaged = 8, kCbOverlap = 16 };
+// the minfo status bits that make a demux "damaged" for the decrypt
+constexpr int64_t kCbDamagedMask =
+    kBadBox | kMoofOverflow | kEmsgOverflow | kRunOverflow | kSampleOverflow | kSampleOutOfRange;
+// ranges[] row (int32) [segment][max_range], -1 rows beyond the recorded ranges
+constexpr int kRangeWords = 4;
+enum RangeRow : int {
+  kRgOffset = 0, kRgLength = 1,
+  kRgSample = 2,  // track slot << kRgTrackShift | sample
+  kRgRank = 3,    // the range's first cipher block among the segment's
+};
+constexpr int kRgTrackShift = 30;
+constexpr int64_t kMaxRangeLimit = 65536, kDefaultMaxRange = 4096;
+constexpr bool max_range_ok(int64_t v) { return v >= 1 && v <= kMaxRangeLimit; }
+// scratch row (int32) [segment][kTracks][max_pes]: a recorded sample's auxiliary data
+constexpr int kAuxWords = 4;
+enum AuxRow : int {
+  kAxEntry = 0,  // offset of its senc entry in the segment, -1: none
+  kAxSubs = 1,   // subsample_count, -1: the entry has no subsample table
+  kAxRun = 2,    // its row of runs
+  kAxSpare = 3,
+};
+constexpr int64_t cbcs_scratch(int64_t nseg, int64_t max_pes) { return nseg * kTracks * max_pes * kAuxWords; }
+constexpr int kCbTileBlocks = 256;  // cipher blocks per tile of the decrypt, a lane each
 }  // namespace mp4
 
 // ---------------------------------------------------------------- CRC-32

@@ -18,7 +18,7 @@ host implementation) it returns:
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Sequence, Union
+from typing import Any, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -62,7 +62,9 @@ AUDIO_TYPES = (0, 0x0F)
 class Mp4Track:
     """What the init segment says about one track: ``kind`` is ``"video"`` or ``"audio"``;
     ``codec_type`` is ``0x1B`` / ``0x24`` / 0 (no NAL index) for video and ``0x0F`` (``mp4a``) / 0
-    for audio; the three defaults are the track's ``trex``."""
+    for audio; the three defaults are the track's ``trex``; ``protection`` is the
+    :class:`~.cbcs.Mp4Protection` of a protected sample entry (``encv`` / ``enca``), which the demux
+    itself does not read."""
     track_id: int
     kind: str
     codec_type: int = 0
@@ -70,6 +72,7 @@ class Mp4Track:
     default_duration: int = 0
     default_size: int = 0
     default_flags: int = 0
+    protection: Any = None
 
 
 def _track_rows(op: str, tracks) -> np.ndarray:

@@ -843,7 +843,7 @@ class StreamController:
             job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag,
                               getattr(payload, "swarm_verify", None), bool(config.get("indexSamples")), False,
                               sample_key, sample_iv, bool(config.get("enableCEA708Captions")), mp4=init)
-        except ValueError as e:  # SAMPLE-AES (cbcs) fragmented MP4
+        except ValueError as e:  # SAMPLE-AES on an init segment without a cbcs-protected track
             self._on_parsed(frag, stats, {"error": e, "status": -1})
             return
         pipeline_for(self.hls.transmux_device(payload), self.loop).submit(job)
@@ -858,11 +858,13 @@ class StreamController:
         if frag.initSegment not in self._mp4_announced:  # once per init segment
             self._mp4_announced.add(frag.initSegment)
             tracks = {}
+            # a cbcs fragment is buffered decrypted (docs/CBCS.md): its init segment without the sinf
+            init_data = init.clear_data if r.get("cbcs") is not None else init.data
             for name in ("video", "audio"):
                 t = r[name]
                 if t["id"] >= 0:
                     tracks[name] = {"id": t["id"], "container": name + "/mp4", "codec": t["codec"],
-                                    "initSegment": init.data, "timescale": t["timescale"]}
+                                    "initSegment": init_data, "timescale": t["timescale"]}
             hls.trigger(Events.FRAG_PARSING_INIT_SEGMENT, {"frag": frag, "tracks": tracks})
         if listening(Events.FRAG_PARSING_METADATA):
             id3 = [e for e in r["emsg"] if e["is_id3"]]
@@ -929,12 +931,17 @@ class StreamController:
             return
         if r.get("container") == "mp4":  # a fragmented-MP4 fragment has a branch of its own
             if r.get("error") is None:
-                if not r["status"] & 0b100001:  # ops.mp4demux.MSTATUS bad_box | sample_out_of_range
+                cb = r.get("cbcs")
+                if cb is not None and cb["status"] & 0b111:  # ops.cbcs.CSTATUS range_overflow | no_senc | bad_senc
+                    # ciphertext would be buffered: a decrypt error, retried by the rule below
+                    r = {"error": ValueError(f"cbcs status {cb['status']}"), "status": -1, "plain_bytes": -1}
+                elif not r["status"] & 0b100001:  # ops.mp4demux.MSTATUS bad_box | sample_out_of_range
                     self._on_parsed_mp4(frag, stats, r)
                     return
                 # ... a damaged one is a parsing error, retried by the rule below
-                r = {"error": ValueError(f"fMP4 demux status {r['status']}"), "status": -1,
-                     "plain_bytes": r["plain_bytes"]}
+                if r.get("error") is None:
+                    r = {"error": ValueError(f"fMP4 demux status {r['status']}"), "status": -1,
+                         "plain_bytes": r["plain_bytes"]}
         if r.get("verify_failed"):
             # the peer's copy was corrupted: nothing was buffered, the node detached the copy and
             # this fragment's next load goes to the CDN -- a transport retry, not a media error

@@ -4,7 +4,9 @@ know about its tracks (``docs/FMP4DEMUX.md``).
 A few hundred bytes once per rendition, host work by design.  :func:`parse_init` walks ``moov`` →
 ``trak`` → ``tkhd`` / ``mdia`` → ``mdhd`` / ``hdlr`` / ``minf`` → ``stbl`` → ``stsd`` (first entry)
 and ``moov`` → ``mvex`` → ``trex``, keeps the first video and the first audio track, and hands the
-raw bytes on untouched, as hls.js does.
+raw bytes on untouched, as hls.js does.  A protected sample entry (``encv`` / ``enca`` with a
+``sinf``) is read as the format its ``frma`` names, and its ``schm`` / ``tenc`` become the track's
+``protection`` (``docs/CBCS.md``).
 """
 from __future__ import annotations
 
@@ -12,24 +14,34 @@ import struct
 from dataclasses import dataclass
 from typing import Dict, Iterator, Optional, Tuple
 
+from ..ops.cbcs import Mp4Protection
 from ..ops.mp4demux import Mp4Track
 from . import fmp4
 
 _CONTAINERS = (b"moov", b"trak", b"mdia", b"minf", b"stbl", b"mvex")
 _VISUAL_ENTRY_BYTES = 78  # SampleEntry (8) + VisualSampleEntry fields in front of the child boxes
+_AUDIO_ENTRY_BYTES = 28   # SampleEntry (8) + AudioSampleEntry fields in front of the child boxes
 
 
 @dataclass(frozen=True)
 class Mp4Init:
     """``video`` / ``audio``: the first track of each kind or ``None``; ``timescale``: per kind;
     ``video_codec`` / ``audio_codec``: the codec string where one can be formed (``avc1.xxyyzz``,
-    ``hvc1...``; ``mp4a`` by name only), else the sample entry's name; ``data``: the raw bytes."""
+    ``hvc1...``; ``mp4a`` by name only), else the sample entry's name; ``data``: the raw bytes;
+    ``clear_data``: the bytes a consumer of decrypted fragments needs, of the same length: every
+    protected entry carries its ``frma`` format as its type and its ``sinf`` box is a ``free`` box
+    (``data`` itself when no track is protected)."""
     data: bytes
     video: Optional[Mp4Track]
     audio: Optional[Mp4Track]
     timescale: Dict[str, int]
     video_codec: Optional[str]
     audio_codec: Optional[str]
+    clear_data: Optional[bytes] = None
+
+    def __post_init__(self) -> None:
+        if self.clear_data is None:
+            object.__setattr__(self, "clear_data", self.data)
 
     @property
     def tracks(self) -> Tuple[Mp4Track, ...]:
@@ -88,6 +100,46 @@ def _video_entry(data: bytes, kind: bytes, p: int, end: int):
     return 0, 4, name
 
 
+def _type_at(data: bytes, body: int, kind: bytes) -> int:
+    """Where the 4-byte type of the box with this body start lies (an 8- or a 16-byte header)."""
+    return body - 4 if data[body - 4:body] == kind else body - 12
+
+
+def _protected_entry(data: bytes, kind: bytes, p: int, end: int):
+    """(original format, Mp4Protection or None, position of the sinf box's type) of an ``encv`` /
+    ``enca`` entry whose ``sinf`` holds ``frma``, ``schm`` and ``schi`` / ``tenc``; ``None`` when a
+    piece is missing or too short."""
+    fixed = _VISUAL_ENTRY_BYTES if kind == b"encv" else _AUDIO_ENTRY_BYTES
+    if end - p < fixed:
+        return None
+    try:
+        sinf = next(((cp, ce) for child, cp, ce in _boxes(data, p + fixed, end) if child == b"sinf"), None)
+        if sinf is None:
+            return None
+        frma = scheme = tenc = None
+        for child, cp, ce in _boxes(data, *sinf):
+            if child == b"frma" and frma is None and ce - cp >= 4:
+                frma = data[cp:cp + 4]
+            elif child == b"schm" and scheme is None and ce - cp >= 12:
+                scheme = data[cp + 4:cp + 8].decode("latin-1")
+            elif child == b"schi" and tenc is None:
+                tenc = next(((tp, te) for t, tp, te in _boxes(data, cp, ce) if t == b"tenc"), None)
+    except ValueError:
+        return None
+    if frma is None or scheme is None or tenc is None or tenc[1] - tenc[0] < 24:
+        return None
+    tp, te = tenc
+    version, pattern, is_protected, iv_size = data[tp], data[tp + 5], data[tp + 6], data[tp + 7]
+    kid, constant = data[tp + 8:tp + 24], b""
+    if is_protected == 1 and iv_size == 0:
+        if te - tp < 25 or te - tp < 25 + data[tp + 24]:
+            return None
+        constant = data[tp + 25:tp + 25 + data[tp + 24]]
+    crypt, skip = (pattern >> 4, pattern & 15) if version >= 1 else (0, 0)
+    protection = Mp4Protection(scheme, crypt, skip, iv_size, constant, kid) if is_protected else None
+    return frma, protection, _type_at(data, sinf[0], b"sinf")
+
+
 def parse_init(data: bytes) -> Mp4Init:
     """The tracks of an init segment; ``ValueError`` for a malformed box tree or one without a
     ``moov`` or without a video or audio track."""
@@ -134,13 +186,24 @@ def parse_init(data: bytes) -> Mp4Init:
     if not found:
         raise ValueError("init segment: no video or audio track")
     tracks, codecs = {"video": None, "audio": None}, {"video": None, "audio": None}
+    clear = None
     for name, t in found.items():
         kind, p, e = t["entry"]
         dur, size, flags = trex.get(t["id"], (0, 0, 0))
+        protection = None
+        if kind == (b"encv" if name == "video" else b"enca"):
+            sinf = _protected_entry(data, kind, p, e)
+            if sinf is not None:
+                at = _type_at(data, p, kind)
+                kind, protection = sinf[0], sinf[1]
+                if protection is not None:
+                    clear = bytearray(data) if clear is None else clear
+                    clear[at:at + 4] = kind
+                    clear[sinf[2]:sinf[2] + 4] = b"free"
         if name == "video":
             ctype, length_size, codecs[name] = _video_entry(data, kind, p, e)
         else:
             ctype, length_size, codecs[name] = (0x0F if kind == b"mp4a" else 0), 4, kind.decode("latin-1")
-        tracks[name] = Mp4Track(t["id"], name, ctype, length_size, dur, size, flags)
+        tracks[name] = Mp4Track(t["id"], name, ctype, length_size, dur, size, flags, protection)
     return Mp4Init(data, tracks["video"], tracks["audio"], {k: int(t["timescale"] or 0) for k, t in found.items()},
-                   codecs["video"], codecs["audio"])
+                   codecs["video"], codecs["audio"], data if clear is None else bytes(clear))

@@ -24,6 +24,7 @@ from __future__ import annotations
 import threading
 import time
 from dataclasses import dataclass, field
+from types import MappingProxyType
 from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -47,8 +48,10 @@ class TransmuxJob:
     slotted class: one is built per fragment, and a dataclass ``__init__`` stays interpreted
     code inside the compiled module.  ``mp4`` (an ``Mp4Init``): the payload is a fragmented-MP4 media
     segment of that init segment's tracks, not MPEG-TS (``docs/FMP4DEMUX.md``): the batch demuxes it
-    where it lies, ``remux`` is ignored (the fragment already is fMP4) and ``sample_key`` is refused
-    (``cbcs`` is out of scope)."""
+    where it lies and ``remux`` is ignored (the fragment already is fMP4).  ``sample_key`` with ``mp4``
+    asks for the ``cbcs`` decrypt (``docs/CBCS.md``): it is accepted when the init segment has a track
+    protected under the ``cbcs`` scheme (the key of ``sample_iv`` serves a track without an IV of its
+    own), and the result's ``data`` and views are then those of the decrypted copy."""
 
     __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
                  "captions", "mp4")
@@ -82,7 +85,11 @@ class TransmuxJob:
         # True (implies ``index``): the batch also extracts the CEA-608/708 caption data of this
         # fragment's SEI NAL units (ops/captions.py) and its result gains ``captions``
         if mp4 is not None and sample_key is not None:
-            raise ValueError("TransmuxJob: SAMPLE-AES (cbcs) fragmented MP4 is not supported")
+            schemes = [getattr(getattr(t, "protection", None), "scheme", None) for t in getattr(mp4, "tracks", ())]
+            if "cbcs" not in schemes:
+                raise ValueError("TransmuxJob: SAMPLE-AES (cbcs) fragmented MP4 is not supported")
+            if key is not None:
+                raise ValueError("TransmuxJob: a fragmented-MP4 fragment is AES-128 or SAMPLE-AES, not both")
         self.mp4 = mp4
         if mp4 is not None:  # the fragment already is fMP4: no remux, and none that implies the index
             self.remux = False
@@ -489,9 +496,11 @@ class MediaPipeline:
     def _launch_mp4(self, jobs: List[TransmuxJob]) -> "_Mp4Batch":
         """Enqueue the fragmented-MP4 jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
         rows, one ``mp4_demux_batch`` per group (the encrypted rows in the decrypt's buffer, the clear
-        ones where they lie) and one ``caption_batch`` over its views when a job of the group asked;
-        ``minfo``, ``info``, ``sinfo``, the ``emsg`` table and the ``ccinfo`` rows are on their way to
-        pinned host memory in front of the event."""
+        ones where they lie, the ``cbcs`` ones where they lie as a group of their own), one
+        ``cbcs_decrypt_batch`` behind the demux of the ``cbcs`` group, whose views then are those of
+        the decrypted copy, and one ``caption_batch`` over a group's views when a job of it asked;
+        ``minfo``, ``info``, ``sinfo``, the ``emsg`` table and the ``cinfo`` / ``ccinfo`` rows are on
+        their way to pinned host memory in front of the event."""
         from ..ops import mp4demux as _mp4
 
         try:
@@ -514,14 +523,25 @@ class MediaPipeline:
                 out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
                                                  [bytes(jobs[i].iv) for i in il], dec, dec_offs)
                 work.append((e, dec, dec_offs, out_len, caps))
-            if len(cl):
-                work.append((cl, src, offs[cl], nb[cl], nb[cl]))
+            asks = np.array([j.sample_key is not None for j in jobs], dtype=bool)
+            for rows in (cl[~asks[cl]], cl[asks[cl]]):
+                if len(rows):
+                    work.append((rows, src, offs[rows], nb[rows], nb[rows]))
             groups = []
             for idx, buf, o, lens, caps in work:
                 il = idx.tolist()
                 md = _mp4.mp4_demux_batch(buf, o, lens, [jobs[i].mp4 for i in il], caps=caps)
+                cb = None
+                if asks[il[0]]:  # out of place: buf may be the arena that peers are served from
+                    from ..ops import cbcs as _cbcs
+
+                    cb = _cbcs.cbcs_decrypt_batch(md, [jobs[i].mp4 for i in il], [jobs[i].sample_key for i in il],
+                                                  [jobs[i].sample_iv for i in il])
+                    md = cb.md
                 g = _Mp4Group(idx, md, _to_host(md.minfo), _to_host(md.info), _to_host(md.sinfo), _to_host(md.emsg),
                               _to_host(lens) if isinstance(lens, torch.Tensor) else lens)
+                if cb is not None:
+                    g.cbinfo = _to_host(cb.cinfo)
                 asked = [bool(jobs[i].captions) for i in il]
                 if any(asked):
                     from ..ops import captions as _cc
@@ -536,6 +556,7 @@ class MediaPipeline:
 
     def _complete_mp4(self, b: "_Mp4Batch") -> None:
         """Wait for the fragmented-MP4 jobs of a batch and run their callbacks."""
+        from ..ops.cbcs import segment_view as cbcs_view
         from ..ops.mp4demux import EMSG, MINFO
 
         if b.error is not None:
@@ -566,6 +587,8 @@ class MediaPipeline:
                     r["samples"] = Samples(sinfo[k].tolist(), md.as_index(), k)
                 if g.cc is not None and job.captions:
                     r["captions"] = CaptionData(g, k)
+                if g.cbinfo is not None:
+                    r["cbcs"] = MappingProxyType(cbcs_view(_np(g.cbinfo)[k]))
                 results[i] = r
         for j, r in zip(b.jobs, results):
             j.callback(r)
@@ -1045,9 +1068,10 @@ class Mp4TrackView(_View):
 
 @dataclass(eq=False)
 class _Mp4Group:
-    """One demux group of the fragmented-MP4 jobs of a batch (its encrypted rows, or its clear ones)."""
+    """One demux group of the fragmented-MP4 jobs of a batch (its encrypted rows, its clear ones or
+    its ``cbcs`` ones)."""
     rows: np.ndarray  # rows of the batch's fragmented-MP4 jobs, in the group's order
-    md: Any  # the group's Mp4Demux, on the device
+    md: Any  # the group's Mp4Demux, on the device; of a cbcs group: over the decrypted copy
     minfo: Any  # its minfo, info, sinfo rows, emsg table and ...
     info: Any
     sinfo: Any
@@ -1055,6 +1079,7 @@ class _Mp4Group:
     hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
     cc: Any = None  # Captions, when a job of the group asked for it, with ...
     ccinfo: Any = None  # ... its ccinfo rows on the host
+    cbinfo: Any = None  # the cinfo rows of a cbcs group on the host
 
 
 @dataclass(eq=False)

@@ -3,7 +3,8 @@
 index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
 (H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
 on a video ES the tool writes itself, the fragmented-MP4 demux on segments the tool writes itself (one
-``moof`` and thirty), and the MFMA CRC with HIP events and reports us / GB/s of input.
+``moof`` and thirty), the cbcs decrypt of such segments protected by the tool (the demux row's segment and
+one of about 3 MB), and the MFMA CRC with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
@@ -16,8 +17,8 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import (aes, captions, codecconfig, crc, esindex, hevcconfig, mp4demux, remux, sampleaes,
-                                       segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, codecconfig, crc, esindex, hevcconfig, mp4demux, remux,
+                                       sampleaes, segment, tsdemux)
 
 
 def timed(fn, iters):
@@ -111,11 +112,13 @@ def caption_batch_inputs(offs, lens, size, dev, n_au=120, seed=5):
     return dres, [len(ves)] * B, hres
 
 
-def mp4_segment(moofs, n_video=120, n_audio=188, seed=7):
+def mp4_segment(moofs, n_video=120, n_audio=188, seed=7, slice_bytes=200, senc=False):
     """One fragmented-MP4 segment written by hand: ``n_video`` video samples of three NAL units (an
     AUD, an SEI-sized unit and a slice, 4-byte lengths) in track 1 and ``n_audio`` audio samples in
     track 2, spread over ``moofs`` pairs of ``moof`` + ``mdat``, each ``moof`` with one ``traf`` per
-    track (``tfhd``, ``tfdt``, one ``trun`` with every per-sample field and a ``data_offset``)."""
+    track (``tfhd``, ``tfdt``, one ``trun`` with every per-sample field and a ``data_offset``).
+    ``senc``: each ``traf`` also gets a ``senc`` box behind its ``trun``, the video one with a subsample
+    per NAL unit (its length and header byte clear), the audio one without subsample tables."""
     rng = np.random.default_rng(seed)
 
     def box(kind, payload):
@@ -128,7 +131,8 @@ def mp4_segment(moofs, n_video=120, n_audio=188, seed=7):
         body = bytes([header]) + rng.integers(1, 256, n, dtype=np.uint8).tobytes()
         return struct.pack(">I", len(body)) + body
 
-    video = [nal(0x09, 1) + nal(0x06, 70) + nal(0x65 if i % 30 == 0 else 0x41, 200 + i % 7) for i in range(n_video)]
+    video = [nal(0x09, 1) + nal(0x06, 70) + nal(0x65 if i % 30 == 0 else 0x41, slice_bytes + i % 7)
+             for i in range(n_video)]
     audio = [rng.integers(0, 256, 300 + i % 5, dtype=np.uint8).tobytes() for i in range(n_audio)]
     out, vt, at = b"", 90000, 48000
     for k in range(moofs):
@@ -136,14 +140,20 @@ def mp4_segment(moofs, n_video=120, n_audio=188, seed=7):
         a = audio[n_audio * k // moofs:n_audio * (k + 1) // moofs]
         v0 = n_video * k // moofs
 
+        vsenc = asenc = b""
+        if senc:
+            subs = b"".join(struct.pack(">H", 3) + struct.pack(">HIHIHI", 5, 1, 5, 70, 5, len(x) - 86) for x in v)
+            vsenc = full(b"senc", 0, 2, struct.pack(">I", len(v)) + subs)
+            asenc = full(b"senc", 0, 0, struct.pack(">I", len(a)))
+
         def moof(voff, aoff):
             vrows = b"".join(struct.pack(">IIIi", 3000, len(x), 0x02000000 if (v0 + i) % 30 == 0 else 0x01010000,
                                          3000 * ((v0 + i) % 3)) for i, x in enumerate(v))
             arows = b"".join(struct.pack(">IIIi", 1024, len(x), 0x02000000, 0) for x in a)
             trafs = [box(b"traf", full(b"tfhd", 0, 0x020000, struct.pack(">I", tid)) +
                          full(b"tfdt", 1, 0, struct.pack(">Q", time)) +
-                         full(b"trun", 0, 0xF01, struct.pack(">Ii", len(rows) // 16, off) + rows))
-                     for tid, time, off, rows in ((1, vt, voff, vrows), (2, at, aoff, arows))]
+                         full(b"trun", 0, 0xF01, struct.pack(">Ii", len(rows) // 16, off) + rows) + aux)
+                     for tid, time, off, rows, aux in ((1, vt, voff, vrows, vsenc), (2, at, aoff, arows, asenc))]
             return box(b"moof", full(b"mfhd", 0, 0, struct.pack(">I", k + 1)) + b"".join(trafs))
 
         size = len(moof(0, 0))
@@ -172,6 +182,66 @@ def mp4_row(moofs, segs, iters, dev):
     assert mi[:, 0].sum() == 0 and (mi[:, 1] == moofs).all() and (mi[:, 6] == 120).all() and (mi[:, 12] == 188).all() \
         and (got.sinfo[:, 1].cpu() == 360).all(), "mp4demux totals"
     return round(timed(lambda: mp4demux.mp4_demux_batch(d, offs, lens, tracks), iters), 1)
+
+
+CBCS_KEY, CBCS_IV = bytes(range(0x40, 0x50)), (bytes(range(0x70, 0x80)), bytes(range(0x90, 0xA0)))
+
+
+def cbcs_protect(seg, md):
+    """The tool's cbcs packager: ``seg`` (a host array of one :func:`mp4_segment` with ``senc`` boxes,
+    changed in place) with one 16-byte block in ten of every video NAL unit behind its header byte and
+    every whole block of every audio sample encrypted, a CBC chain per range from the track's
+    constant IV.  ``md`` is the segment's host demux.  Returns the cipher blocks written."""
+    blocks = 0
+
+    def chain(at, iv):
+        nonlocal blocks
+        idx = (at[:, None] + np.arange(16)[None, :]).reshape(-1)
+        seg[idx] = aes.cbc_encrypt(CBCS_KEY, iv, seg[idx])[:len(idx)]
+        blocks += len(at)
+    for off, n in md.nal[0, :int(md.sinfo[0, 1]), :2].tolist():
+        if n - 1 >= 16:
+            chain(off + 1 + 160 * np.arange(((n - 1) // 16 + 9) // 10), CBCS_IV[0])
+    for k in range(int(md.minfo[0, 12])):
+        off, n = int(md.pes[0, 1, k, 0]), int(md.msamples[0, 1, k, 0])
+        if n >= 16:
+            chain(off + 16 * np.arange(n // 16), CBCS_IV[1])
+    return blocks
+
+
+def cbcs_row(slice_bytes, segs, iters, dev):
+    """``cbcs_decrypt_batch`` on ``segs`` copies of :func:`mp4_segment` protected by the tool, 1:9 video
+    with a subsample per NAL unit and 0:0 audio: (us per call, us of ``copy_segments`` over the same
+    bytes, cipher blocks per call), after checking segment 0 of the device result against the host
+    implementation and against the clear bytes."""
+    clear = np.frombuffer(mp4_segment(1, slice_bytes=slice_bytes, senc=True), np.uint8)
+    prot = [cbcs.Mp4Protection("cbcs", c, s, 0, iv, bytes(16)) for (c, s), iv in zip(((1, 9), (0, 0)), CBCS_IV)]
+    tracks = (mp4demux.Mp4Track(1, "video", 0x1B, 4, protection=prot[0]),
+              mp4demux.Mp4Track(2, "audio", 0x0F, protection=prot[1]))
+    stride = (len(clear) + 255) // 256 * 256
+    one = np.zeros(stride + 256, np.uint8)
+    one[:len(clear)] = clear
+    hmd = mp4demux.mp4_demux_batch(torch.from_numpy(one), [0], [len(clear)], tracks)
+    blocks = cbcs_protect(one, hmd)
+    buf = np.zeros(stride * segs + 256, np.uint8)
+    offs, lens = [stride * i for i in range(segs)], [len(clear)] * segs
+    for o in offs:
+        buf[o:o + len(clear)] = one[:len(clear)]
+    d = torch.from_numpy(buf).to(dev)
+    md = mp4demux.mp4_demux_batch(d, offs, lens, tracks)
+    keys = [CBCS_KEY] * segs
+    got = cbcs.cbcs_decrypt_batch(md, tracks, keys)
+    host = cbcs.cbcs_decrypt_batch(hmd, tracks, keys[:1])
+    ci = got.cinfo.cpu()
+    assert torch.equal(ci[0], host.cinfo[0]) and torch.equal(got.ranges[0].cpu(), host.ranges[0]), "cbcs mismatch"
+    assert ci[:, 0].sum() == 0 and ((ci[:, 4] + ci[:, 5]) == blocks).all() and blocks > 0, "cbcs totals"
+    for i in (0, segs - 1):
+        mine = got.buf[int(got.offs[i]):int(got.offs[i]) + len(clear)].cpu().numpy()
+        assert np.array_equal(mine, host.buf[:len(clear)].numpy()) and np.array_equal(mine, clear), "cbcs bytes"
+    assert not np.array_equal(one[:len(clear)], clear), "cbcs packager"
+    cp = torch.empty_like(d)
+    return (round(timed(lambda: cbcs.cbcs_decrypt_batch(md, tracks, keys), iters), 1),
+            round(timed(lambda: segment.copy_segments(d, cp, offs, offs, lens), iters), 1), blocks * segs)
 
 
 def main():
@@ -295,6 +365,11 @@ def main():
     # 188 audio samples in one moof + mdat, and the same samples in 30 (the serial top-level chain)
     res["mp4demux_us"] = mp4_row(1, args.segs, args.iters, dev)
     res["mp4demux_chunked_us"] = mp4_row(30, args.segs, args.iters, dev)
+    # the cbcs decrypt (copy, plan, a lane per cipher block) of that segment protected by the tool, and of
+    # one with 120 video samples of about 23 KB: beside each the batched copy of the same bytes
+    res["cbcs_us"], res["cbcs_copy_us"], res["cbcs_blocks"] = cbcs_row(200, args.segs, args.iters, dev)
+    res["cbcs_large_us"], res["cbcs_large_copy_us"], res["cbcs_large_blocks"] = cbcs_row(23000, args.segs, args.iters,
+                                                                                        dev)
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
