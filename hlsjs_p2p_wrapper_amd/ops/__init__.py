@@ -1,14 +1,14 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
-``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``): import the submodule you
-need.  The entry points of the sample index, of the remux, of the two codec configurations, of the SAMPLE-AES
-decrypt, of the caption extraction, of the fragmented-MP4 demux and of the cbcs decrypt are also reachable from
-the package
+``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``, ``cenc``): import the
+submodule you need.  The entry points of the sample index, of the remux, of the two codec configurations, of the
+SAMPLE-AES decrypt, of the caption extraction, of the fragmented-MP4 demux and of the cbcs and cenc decrypts are
+also reachable from the package
 (``ops.index_batch``,
 ``ops.EsIndex``, ``ops.remux_batch``,
 ``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
 ``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``, ``ops.caption_batch``,
 ``ops.Captions``, ``ops.mp4_demux_batch``, ``ops.Mp4Demux``, ``ops.Mp4Track``, ``ops.cbcs_decrypt_batch``,
-``ops.Cbcs``, ``ops.Mp4Protection``), resolved on first use."""
+``ops.Cbcs``, ``ops.Mp4Protection``, ``ops.cenc_decrypt_batch``, ``ops.Cenc``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
@@ -18,7 +18,8 @@ _SAMPLEAES = ("sample_decrypt_batch", "SampleAes")
 _CAPTIONS = ("caption_batch", "Captions")
 _MP4DEMUX = ("mp4_demux_batch", "Mp4Demux", "Mp4Track")
 _CBCS = ("cbcs_decrypt_batch", "Cbcs", "Mp4Protection")
-__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS)
+_CENC = ("cenc_decrypt_batch", "Cenc")
+__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS + _CENC)
 
 
 def __getattr__(name):
@@ -54,4 +55,8 @@ def __getattr__(name):
         from . import cbcs
 
         return getattr(cbcs, name)
+    if name in _CENC:
+        from . import cenc
+
+        return getattr(cenc, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

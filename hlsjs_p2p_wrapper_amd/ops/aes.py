@@ -22,7 +22,9 @@ from .desc import check_ranges, pack_to_device
 
 _key_cache: Dict[bytes, np.ndarray] = {}
 _key_cache_le: Dict[bytes, np.ndarray] = {}
+_key_cache_enc_le: Dict[bytes, np.ndarray] = {}
 _tables: Dict[str, tuple] = {}
+_enc_tables: Dict[str, tuple] = {}
 _lock = threading.Lock()
 
 
@@ -51,6 +53,34 @@ def round_keys_le(key: bytes) -> np.ndarray:
         with _lock:
             _key_cache_le[key] = rk
     return rk
+
+
+def enc_round_keys_le(key: bytes) -> np.ndarray:
+    """The 44 forward round keys as the CTR kernel consumes them: uint32[44] little-endian column
+    words (cached)."""
+    key = bytes(key)
+    rk = _key_cache_enc_le.get(key)
+    if rk is None:
+        if len(key) != 16:
+            raise ValueError("AES-128 key must be 16 bytes")
+        rk = np.ascontiguousarray(_rt().expand_key_enc(key).astype(np.uint32).byteswap())
+        with _lock:
+            _key_cache_enc_le[key] = rk
+    return rk
+
+
+def device_enc_tables(device: torch.device):
+    """(TeL int32[256], Sbox uint8[256]) on ``device`` (cached): ``TeL[x] = 2s | s << 8 | s << 16 |
+    3s << 24`` with ``s = Sbox[x]``, the forward T-table in little-endian column form."""
+    k = str(device)
+    t = _enc_tables.get(k)
+    if t is None:
+        _, _, te0, sbox = _rt().aes_tables()
+        tel = te0.astype(np.uint32).byteswap()
+        t = (torch.from_numpy(tel.view(np.int32).copy()).to(device), torch.from_numpy(sbox.copy()).to(device))
+        with _lock:
+            _enc_tables[k] = t
+    return t
 
 
 def device_tables(device: torch.device):

@@ -58,7 +58,7 @@ class Mp4Protection:
     kid: bytes
 
 
-def _prot_rows(op: str, tracks):
+def _prot_rows(op: str, tracks, scheme: str = "cbcs"):
     """One segment's ``int64[TRACKS, PROT_WORDS]`` and ``uint8[TRACKS, 16]`` constant IVs."""
     tracks = getattr(tracks, "tracks", tracks)  # an Mp4Init
     rows = np.zeros((TRACKS, PROT_WORDS), dtype=np.int64)
@@ -70,8 +70,8 @@ def _prot_rows(op: str, tracks):
         if t.kind not in ("video", "audio"):
             raise ValueError(f"{op}: a track is video or audio")
         slot = 0 if t.kind == "video" else 1
-        if p.scheme != "cbcs":
-            raise ValueError(f"{op}: scheme {p.scheme!r} is not supported, only cbcs")
+        if p.scheme != scheme:
+            raise ValueError(f"{op}: scheme {p.scheme!r} is not supported, only {scheme}")
         c, s = int(p.crypt_byte_block), int(p.skip_byte_block)
         size, const = int(p.per_sample_iv_size), bytes(p.constant_iv)
         if size not in (0, 8, 16) or len(const) not in (0, 8, 16):
@@ -80,22 +80,25 @@ def _prot_rows(op: str, tracks):
             raise ValueError(f"{op}: crypt_byte_block and skip_byte_block are 0 to 255")
         if s > 0 and c == 0:
             raise ValueError(f"{op}: a pattern that skips blocks must encrypt some (crypt_byte_block 0)")
+        if scheme == "cenc" and (c or s):
+            raise ValueError(f"{op}: a pattern ({c}:{s}) under AES-CTR is the cens scheme, which is not supported")
         rows[slot, :5] = (1, c, s, size, len(const) if size == 0 else 0)
         if size == 0 and const:
             civ[slot, :len(const)] = np.frombuffer(const, dtype=np.uint8)  # an 8-byte IV: zeros on the right
     return rows, civ
 
 
-def pack_protection(protection, B: int, op: str = "cbcs_decrypt_batch"):
+def pack_protection(protection, B: int, op: str = "cbcs_decrypt_batch", scheme: str = "cbcs"):
     """``int64[B, TRACKS, PROT_WORDS]`` and ``uint8[B, TRACKS, 16]`` from one track set for all
-    segments (an ``Mp4Init`` or a sequence of :class:`~.mp4demux.Mp4Track`) or from ``B`` of them."""
+    segments (an ``Mp4Init`` or a sequence of :class:`~.mp4demux.Mp4Track`) or from ``B`` of them.
+    ``scheme`` is the one scheme_type that is accepted."""
     one = hasattr(protection, "tracks") or all(isinstance(t, Mp4Track) for t in protection)
     if one:
-        rows, civ = _prot_rows(op, protection)
+        rows, civ = _prot_rows(op, protection, scheme)
         return (np.broadcast_to(rows, (B, TRACKS, PROT_WORDS)).copy(), np.broadcast_to(civ, (B, TRACKS, 16)).copy())
     if len(protection) != B:
         raise ValueError(f"{op}: one track set per segment, or one for all")
-    both = [_prot_rows(op, p) for p in protection]
+    both = [_prot_rows(op, p, scheme) for p in protection]
     return (np.stack([r for r, _ in both]).reshape(B, TRACKS, PROT_WORDS),
             np.stack([c for _, c in both]).reshape(B, TRACKS, 16))
 
@@ -139,28 +142,36 @@ def _check_md(op: str, md: Mp4Demux) -> int:
     return B
 
 
-def cbcs_decrypt_batch(md: Mp4Demux, protection, keys: Sequence[Optional[bytes]],
-                       ivs: Optional[Sequence[Optional[bytes]]] = None, enable: Optional[Sequence[bool]] = None,
-                       max_range: int = DEFAULT_MAX_RANGE) -> Cbcs:
-    """Decrypt every enabled segment of a demuxed fragmented-MP4 batch into a copy, on the device
-    its tensors live on and on the caller's stream.  ``protection`` is an ``Mp4Init`` or a sequence
-    of :class:`~.mp4demux.Mp4Track` (their ``protection`` fields count) for all segments, or one per
-    segment; ``keys[i]`` is 16 bytes; ``ivs[i]`` (16 bytes) serves a track whose ``tenc`` has neither
-    a per-sample nor a constant IV; ``enable[i]`` false leaves segment i alone with an all-zero
-    ``cinfo`` row and ``offs[i] = -1`` (its key may be ``None``).  ``md.buf`` is only read."""
-    op = "cbcs_decrypt_batch"
-    B = _check_md(op, md)
-    max_range = int(max_range)
+class _Setup:
+    """What ``cbcs_decrypt_batch`` and ``cenc_decrypt_batch`` share: the checks, the per-segment
+    arrays, the output tensors and the copy of every enabled segment (made here)."""
+
+    def pack(self):
+        return pack_to_device({"so": self.src_off, "cap": self.cap, "do": self.offs, "prot": self.prot.reshape(-1),
+                               "civ": self.civ.reshape(-1), "iv": self.iv.reshape(-1), "drk": self.rk.reshape(-1),
+                               "en": self.en}, self.dev)
+
+    def scratch(self):
+        return torch.empty(self.B * TRACKS * self.max_pes * AUX_WORDS, dtype=torch.int32, device=self.dev)
+
+
+def _setup(op: str, scheme: str, md: Mp4Demux, protection, keys, ivs, enable, max_range, range_words: int,
+           cinfo_words: int, expand) -> _Setup:
+    """``expand(key)`` gives the 44 round-key words of one key in the form the implementation that
+    will run takes."""
+    s = _Setup()
+    B = s.B = _check_md(op, md)
+    max_range = s.max_range = int(max_range)
     if not 1 <= max_range <= MAX_RANGE_LIMIT:
         raise ValueError(f"{op}: max_range must be 1 to {MAX_RANGE_LIMIT}")
     if len(keys) != B or (ivs is not None and len(ivs) != B) or (enable is not None and len(enable) != B):
         raise ValueError(f"{op}: one key, one IV and one enable flag per segment")
-    prot, civ = pack_protection(protection, B, op)
-    en = np.ones(B, dtype=np.uint8) if enable is None else np.asarray([bool(e) for e in enable], dtype=np.uint8)
-    dev = md.buf.device
-    on_gpu = dev.type != "cpu"
-    drk = np.zeros((B, 44), dtype=np.uint32)
-    iv = np.zeros((B, 16), dtype=np.uint8)
+    s.prot, s.civ = pack_protection(protection, B, op, scheme)
+    en = s.en = np.ones(B, dtype=np.uint8) if enable is None else np.asarray([bool(e) for e in enable], dtype=np.uint8)
+    dev = s.dev = md.buf.device
+    s.on_gpu = dev.type != "cpu"
+    rk = s.rk = np.zeros((B, 44), dtype=np.uint32)
+    iv = s.iv = np.zeros((B, 16), dtype=np.uint8)
     expanded = {}
     for i in range(B):
         if not en[i]:
@@ -171,48 +182,64 @@ def cbcs_decrypt_batch(md: Mp4Demux, protection, keys: Sequence[Optional[bytes]]
         # is the usual case: it is expanded once
         key = bytes(keys[i])
         if key not in expanded:
-            expanded[key] = aes.round_keys_le(key) if on_gpu else aes.round_keys(key)
-        drk[i] = expanded[key]
+            expanded[key] = expand(key)
+        rk[i] = expanded[key]
         if ivs is not None and ivs[i] is not None:
             if len(ivs[i]) != 16:
                 raise ValueError(f"{op}: an IV must be 16 bytes")
             iv[i] = np.frombuffer(bytes(ivs[i]), dtype=np.uint8)
-    src_off = np.asarray(md.offs, dtype=np.int64).reshape(B)
-    cap = np.asarray(md.caps, dtype=np.int64).reshape(B)
+    src_off = s.src_off = np.asarray(md.offs, dtype=np.int64).reshape(B)
+    cap = s.cap = np.asarray(md.caps, dtype=np.int64).reshape(B)
     if np.any(cap < 0) or np.any(cap >= 2 ** 31 - 64) or np.any(src_off < 0) or np.any(src_off + cap > md.buf.numel()):
         raise ValueError(f"{op}: md's segments do not lie inside md.buf")
-    on = np.flatnonzero(en)
+    on = s.on = np.flatnonzero(en)
     sizes = (cap[on] + (ALIGN - 1)) // ALIGN * ALIGN
     ends = np.cumsum(sizes)
-    offs = np.full(B, -1, dtype=np.int64)
+    offs = s.offs = np.full(B, -1, dtype=np.int64)
     offs[on] = ends - sizes
-    buf = torch.empty((int(ends[-1]) if len(on) else 0) + ALIGN, dtype=torch.uint8, device=dev)
-    max_pes, max_run = int(md.pes.shape[2]), int(md.runs.shape[1])
-    cinfo = torch.empty((B, CINFO_WORDS), dtype=torch.int64, device=dev)
-    ranges = torch.empty((B, max_range, RANGE_WORDS), dtype=torch.int32, device=dev)
-    out_md = Mp4Demux(md.minfo, md.msamples, md.runs, md.emsg, md.info, md.pes, md.nal, md.au, md.aframes, md.sinfo,
-                      buf, offs, cap)
-    r = Cbcs(buf, offs, cinfo, ranges, out_md)
-    if not on_gpu:
-        n = np.minimum(np.maximum(md.info[:, INFO["video_bytes"]].numpy().astype(np.int64), 0), cap) if B else cap
-        copy_segments(md.buf, buf, src_off[on], offs[on], n[on])
-        _rt().cbcs_decrypt_batch(md.buf.numpy(), src_off, n, buf.numpy(), offs, md.minfo.numpy(), md.msamples.numpy(),
-                                 md.runs.numpy(), md.info.numpy(), md.pes.numpy(), max_pes, max_run, prot, civ, iv, drk,
-                                 en, max_range, ranges.numpy(), cinfo.numpy())
-        return r
+    s.buf = torch.empty((int(ends[-1]) if len(on) else 0) + ALIGN, dtype=torch.uint8, device=dev)
+    s.max_pes, s.max_run = int(md.pes.shape[2]), int(md.runs.shape[1])
+    s.cinfo = torch.empty((B, cinfo_words), dtype=torch.int64, device=dev)
+    s.ranges = torch.empty((B, max_range, range_words), dtype=torch.int32, device=dev)
+    s.md = Mp4Demux(md.minfo, md.msamples, md.runs, md.emsg, md.info, md.pes, md.nal, md.au, md.aframes, md.sinfo,
+                    s.buf, offs, cap)
+    if not s.on_gpu:
+        s.n = np.minimum(np.maximum(md.info[:, INFO["video_bytes"]].numpy().astype(np.int64), 0), cap) if B else cap
+        copy_segments(md.buf, s.buf, src_off[on], offs[on], s.n[on])
+        return s
     if np.any(src_off % 16):
         raise ValueError(f"{op}: offsets must be 16-byte aligned on device")
     if np.any(src_off + cap > md.buf.numel() - md.buf.numel() % 4):
         raise ValueError(f"{op}: a segment reaches the buffer's last partial dword on device")
-    if not B:
+    if B:
+        copy_segments(md.buf, s.buf, src_off[on], offs[on], cap[on])  # whole caps: the true lengths live on the device
+    return s
+
+
+def cbcs_decrypt_batch(md: Mp4Demux, protection, keys: Sequence[Optional[bytes]],
+                       ivs: Optional[Sequence[Optional[bytes]]] = None, enable: Optional[Sequence[bool]] = None,
+                       max_range: int = DEFAULT_MAX_RANGE) -> Cbcs:
+    """Decrypt every enabled segment of a demuxed fragmented-MP4 batch into a copy, on the device
+    its tensors live on and on the caller's stream.  ``protection`` is an ``Mp4Init`` or a sequence
+    of :class:`~.mp4demux.Mp4Track` (their ``protection`` fields count) for all segments, or one per
+    segment; ``keys[i]`` is 16 bytes; ``ivs[i]`` (16 bytes) serves a track whose ``tenc`` has neither
+    a per-sample nor a constant IV; ``enable[i]`` false leaves segment i alone with an all-zero
+    ``cinfo`` row and ``offs[i] = -1`` (its key may be ``None``).  ``md.buf`` is only read."""
+    s = _setup("cbcs_decrypt_batch", "cbcs", md, protection, keys, ivs, enable, max_range, RANGE_WORDS, CINFO_WORDS,
+               aes.round_keys_le if md.buf.device.type != "cpu" else aes.round_keys)
+    r = Cbcs(s.buf, s.offs, s.cinfo, s.ranges, s.md)
+    if not s.on_gpu:
+        _rt().cbcs_decrypt_batch(md.buf.numpy(), s.src_off, s.n, s.buf.numpy(), s.offs, md.minfo.numpy(),
+                                 md.msamples.numpy(), md.runs.numpy(), md.info.numpy(), md.pes.numpy(), s.max_pes,
+                                 s.max_run, s.prot, s.civ, s.iv, s.rk, s.en, s.max_range, s.ranges.numpy(),
+                                 s.cinfo.numpy())
         return r
-    copy_segments(md.buf, buf, src_off[on], offs[on], cap[on])  # whole caps: the true lengths live on the device
-    d = pack_to_device({"so": src_off, "cap": cap, "do": offs, "prot": prot.reshape(-1), "civ": civ.reshape(-1),
-                        "iv": iv.reshape(-1), "drk": drk.reshape(-1), "en": en}, dev)
-    tdl, isb = aes.device_tables(dev)
-    scratch = torch.empty(B * TRACKS * max_pes * AUX_WORDS, dtype=torch.int32, device=dev)
-    max_blocks = int(cap[on].max()) // 16 if len(on) else 0
-    _dev().cbcs_decrypt(md.buf, d["so"], d["cap"], buf, d["do"], md.info, md.pes, md.minfo, md.msamples, md.runs,
-                        max_pes, max_run, d["prot"], d["civ"], d["iv"], d["drk"], d["en"], tdl, isb, max_range,
-                        max_blocks, scratch, ranges, cinfo)
+    if not s.B:
+        return r
+    d = s.pack()
+    tdl, isb = aes.device_tables(s.dev)
+    max_blocks = int(s.cap[s.on].max()) // 16 if len(s.on) else 0
+    _dev().cbcs_decrypt(md.buf, d["so"], d["cap"], s.buf, d["do"], md.info, md.pes, md.minfo, md.msamples, md.runs,
+                        s.max_pes, s.max_run, d["prot"], d["civ"], d["iv"], d["drk"], d["en"], tdl, isb, s.max_range,
+                        max_blocks, s.scratch(), s.ranges, s.cinfo)
     return r

@@ -315,17 +315,19 @@ void mp4_demux(Tensor buf, Tensor off, Tensor len, Tensor cap, Tensor tracks, in
 // only read; dst already holds a copy of every enabled segment at dst_off[i] (the Python wrapper
 // has checked both offset sets against their tensors); per segment two protection rows, two
 // constant IVs, a fallback IV, 44 round-key words (little-endian) and an enable byte.
-void cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor dst, Tensor dst_off, Tensor info, Tensor pes,
-                  Tensor minfo, Tensor msamples, Tensor runs, int64_t max_pes, int64_t max_run, Tensor prot,
-                  Tensor const_iv, Tensor iv, Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int64_t max_range,
-                  int64_t max_blocks, Tensor scratch, Tensor ranges, Tensor cinfo) {
+// (shared with cenc_decrypt below: range_words and info_words are the scheme's row widths)
+D::CbcsArgs protected_args(const char* op, int range_words, int info_words, Tensor src, Tensor src_off, Tensor cap,
+                           Tensor dst, Tensor dst_off, Tensor info, Tensor pes, Tensor minfo, Tensor msamples,
+                           Tensor runs, int64_t max_pes, int64_t max_run, Tensor prot, Tensor const_iv, Tensor iv,
+                           Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int64_t max_range,
+                           int64_t max_blocks, Tensor scratch, Tensor ranges, Tensor cinfo) {
   namespace mp4 = hlsp2p::mp4;
   const int64_t B = src_off.numel();
-  TORCH_CHECK(B <= 65535, "cbcs_decrypt: at most 65535 segments per call");
+  TORCH_CHECK(B <= 65535, op, ": at most 65535 segments per call");
   TORCH_CHECK(max_pes > 0 && max_pes < (int64_t(1) << mp4::kRgTrackShift) && mp4::max_rows_ok(max_run),
-              "cbcs_decrypt: max_pes / max_run out of range");
-  TORCH_CHECK(mp4::max_range_ok(max_range), "cbcs_decrypt: max_range must be 1 to 65536");
-  TORCH_CHECK(max_blocks >= 0 && max_blocks <= 0x7fffffff / 16, "cbcs_decrypt: max_blocks out of range");
+              op, ": max_pes / max_run out of range");
+  TORCH_CHECK(mp4::max_range_ok(max_range), op, ": max_range must be 1 to 65536");
+  TORCH_CHECK(max_blocks >= 0 && max_blocks <= 0x7fffffff / 16, op, ": max_blocks out of range");
   const D::CbcsArgs a{
       .src = check<uint8_t>(src, "src"), .src_numel = src.numel(),
       .src_off = check<int64_t>(src_off, "src_off"),
@@ -347,15 +349,41 @@ void cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor dst, Tensor dst
       .isb = check<uint8_t>(isb, "isb", 256),
       .max_range = max_range, .max_blocks = max_blocks,
       .scratch = check<int32_t>(scratch, "scratch", mp4::cbcs_scratch(B, max_pes)),
-      .ranges = check<int32_t>(ranges, "ranges", hlsp2p::table_words(B, max_range, mp4::kRangeWords)),
-      .cinfo = check<int64_t>(cinfo, "cinfo", B * mp4::kCbInfoWords),
+      .ranges = check<int32_t>(ranges, "ranges", hlsp2p::table_words(B, max_range, range_words)),
+      .cinfo = check<int64_t>(cinfo, "cinfo", B * info_words),
       .nseg = static_cast<int>(B), .stream = stream()};
-  TORCH_CHECK(src.data_ptr() != dst.data_ptr(), "cbcs_decrypt cannot run in place");
+  TORCH_CHECK(src.data_ptr() != dst.data_ptr(), op, " cannot run in place");
   same_device(src, {src_off, cap, dst, dst_off, info, pes, minfo, msamples, runs, prot, const_iv, iv, round_keys, enable,
                     td, isb, scratch, ranges, cinfo});
   aligned16({{src, "src"}, {dst, "dst"}, {msamples, "msamples"}, {const_iv, "const_iv"}, {iv, "iv"},
              {scratch, "scratch"}, {ranges, "ranges"}, {cinfo, "cinfo"}});
-  hip_ok(D::launch_cbcs(a), "cbcs_decrypt launch");
+  return a;
+}
+void cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor dst, Tensor dst_off, Tensor info, Tensor pes,
+                  Tensor minfo, Tensor msamples, Tensor runs, int64_t max_pes, int64_t max_run, Tensor prot,
+                  Tensor const_iv, Tensor iv, Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int64_t max_range,
+                  int64_t max_blocks, Tensor scratch, Tensor ranges, Tensor cinfo) {
+  namespace mp4 = hlsp2p::mp4;
+  hip_ok(D::launch_cbcs(protected_args("cbcs_decrypt", mp4::kRangeWords, mp4::kCbInfoWords, src, src_off, cap, dst,
+                                       dst_off, info, pes, minfo, msamples, runs, max_pes, max_run, prot, const_iv, iv,
+                                       round_keys, enable, td, isb, max_range, max_blocks, scratch, ranges, cinfo)),
+         "cbcs_decrypt launch");
+}
+
+// cenc (AES-CTR) decryption of a demuxed fMP4 batch into a copy (cenc.hip): the arguments of
+// cbcs_decrypt with the 44 forward round-key words (little-endian), te the forward table TeL, sbox
+// the S-box, and max_cap the largest cap of an enabled segment.
+void cenc_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor dst, Tensor dst_off, Tensor info, Tensor pes,
+                  Tensor minfo, Tensor msamples, Tensor runs, int64_t max_pes, int64_t max_run, Tensor prot,
+                  Tensor const_iv, Tensor iv, Tensor round_keys, Tensor enable, Tensor te, Tensor sbox, int64_t max_range,
+                  int64_t max_cap, Tensor scratch, Tensor ranges, Tensor cinfo) {
+  namespace mp4 = hlsp2p::mp4;
+  TORCH_CHECK(max_cap >= 0 && max_cap < 0x7fffffff - 64, "cenc_decrypt: max_cap out of range");
+  const D::CencArgs a{protected_args("cenc_decrypt", mp4::kCnRangeWords, mp4::kCnInfoWords, src, src_off, cap, dst,
+                                     dst_off, info, pes, minfo, msamples, runs, max_pes, max_run, prot, const_iv, iv,
+                                     round_keys, enable, te, sbox, max_range, 0, scratch, ranges, cinfo),
+                      max_cap, num_cus(src.get_device())};
+  hip_ok(D::launch_cenc(a), "cenc_decrypt launch");
 }
 
 void segment_copy(Tensor src, Tensor dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix,
@@ -505,6 +533,10 @@ TORCH_LIBRARY(hlsp2p, m) {
         "Tensor minfo, Tensor msamples, Tensor runs, int max_pes, int max_run, Tensor prot, Tensor const_iv, Tensor iv, "
         "Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int max_range, int max_blocks, Tensor(b!) scratch, "
         "Tensor(c!) ranges, Tensor(d!) cinfo) -> ()");
+  m.def("cenc_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor(a!) dst, Tensor dst_off, Tensor info, Tensor pes, "
+        "Tensor minfo, Tensor msamples, Tensor runs, int max_pes, int max_run, Tensor prot, Tensor const_iv, Tensor iv, "
+        "Tensor round_keys, Tensor enable, Tensor te, Tensor sbox, int max_range, int max_cap, Tensor(b!) scratch, "
+        "Tensor(c!) ranges, Tensor(d!) cinfo) -> ()");
   m.def("segment_copy(Tensor src, Tensor(a!) dst, Tensor src_off, Tensor dst_off, Tensor len, Tensor chunk_prefix, "
         "int total_chunks) -> ()");
 }
@@ -521,6 +553,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("cc_extract", &cc_extract);
   m.impl("mp4_demux", &mp4_demux);
   m.impl("cbcs_decrypt", &cbcs_decrypt);
+  m.impl("cenc_decrypt", &cenc_decrypt);
   m.impl("segment_copy", &segment_copy);
 }
 
@@ -565,6 +598,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("cbcs_decrypt", &cbcs_decrypt);
+  m.def("cenc_decrypt", &cenc_decrypt);
   m.def("segment_copy", &segment_copy);
   m.def("device_cus", &device_cus);
   m.def("h2d_batch", &h2d_batch, pybind11::arg("dst"), pybind11::arg("dst_off"), pybind11::arg("src_ptr"),

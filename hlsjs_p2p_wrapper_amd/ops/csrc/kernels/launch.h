@@ -202,6 +202,16 @@ struct CbcsArgs {
 };
 hipError_t launch_cbcs(const CbcsArgs& a);
 
+// cenc.hip: the arguments of launch_cbcs with, in t, round_keys the forward ones (little-endian
+// words), td the forward table TeL, isb the S-box, ranges rows of mp4::kCnRangeWords, cinfo rows of
+// mp4::kCnInfoWords, and max_blocks unused
+struct CencArgs {
+  CbcsArgs t;
+  int64_t max_cap;  // host bound of one segment's bytes: max(cap)
+  int num_cu;       // workgroups of the persistent units kernel
+};
+hipError_t launch_cenc(const CencArgs& a);
+
 struct SegmentCopyArgs {
   const uint8_t* src;
   uint8_t* dst;

@@ -1,5 +1,6 @@
 // Device helpers of the kernels that read fragmented-MP4 segments where they lie (mp4_demux.hip,
-// cbcs.hip): the segment reader over a buffer resource, the 64-bit wave scan and the LDS search.
+// cbcs.hip, cenc.hip): the segment reader over a buffer resource, the 64-bit wave scan, the LDS
+// search and the 16-byte store at any alignment.
 #pragma once
 #include "common.h"
 #include "grammar.hpp"
@@ -72,6 +73,27 @@ __device__ __forceinline__ int last_le_lds(const long long* first, int K, long l
     else hi = mid;
   }
   return lo;
+}
+
+// 16 bytes with the widest stores the address allows
+__device__ __forceinline__ void cbcs_store16(uint8_t* p, const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  const uintptr_t al = reinterpret_cast<uintptr_t>(p);
+  if (!(al & 15)) {
+    *reinterpret_cast<uint4*>(p) = v;
+  } else if (!(al & 7)) {
+    reinterpret_cast<uint2*>(p)[0] = uint2{v.x, v.y};
+    reinterpret_cast<uint2*>(p)[1] = uint2{v.z, v.w};
+  } else if (!(al & 3)) {
+#pragma unroll
+    for (int d = 0; d < 4; ++d) reinterpret_cast<uint32_t*>(p)[d] = w[d];
+  } else if (!(al & 1)) {
+#pragma unroll
+    for (int d = 0; d < 8; ++d) reinterpret_cast<uint16_t*>(p)[d] = static_cast<uint16_t>(w[d >> 1] >> (16 * (d & 1)));
+  } else {
+#pragma unroll
+    for (int d = 0; d < 16; ++d) p[d] = static_cast<uint8_t>(w[d >> 2] >> (8 * (d & 3)));
+  }
 }
 
 }  // namespace dev

@@ -22,6 +22,7 @@
 #include "aes_host.hpp"
 #include "captions.hpp"
 #include "cbcs.hpp"
+#include "cenc.hpp"
 #include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
@@ -711,14 +712,19 @@ PYBIND11_MODULE(_runtime, m) {
   //   minfo / msamples / runs / info / pes: as mp4_demux_batch wrote them
   //   prot: int64[B, MP4_TRACKS, CBCS_PROT_WORDS]; const_iv: uint8[B, MP4_TRACKS, 16]; iv: uint8[B, 16]
   //   drk: uint32[B, 44] (expand_key_dec); ranges: int32[B, max_range, CBCS_RANGE_WORDS]; cinfo: int64[B, CBCS_CINFO_WORDS]
-  m.def("cbcs_decrypt_batch", [](Arr<uint8_t> src, Arr<int64_t> src_off, Arr<int64_t> len, py::array dst_rw,
-                                 Arr<int64_t> dst_off, Arr<int64_t> minfo, Arr<int32_t> msamples, Arr<int64_t> runs,
-                                 Arr<int64_t> info, Arr<int64_t> pes, int64_t max_pes, int64_t max_run,
-                                 Arr<int64_t> prot, Arr<uint8_t> const_iv, Arr<uint8_t> iv, Arr<uint32_t> drk,
-                                 Arr<uint8_t> enable, int64_t max_range, py::array ranges, py::array cinfo) {
+  // cbcs and cenc share the checks and the batch loop: op names the call in messages, the row
+  // widths are the scheme's and segment is mp4::cbcs_segment or mp4::cenc_segment
+  static const auto protected_batch = [](const char* op, int range_words, int info_words, auto segment,
+                                         Arr<uint8_t> src, Arr<int64_t> src_off, Arr<int64_t> len, py::array dst_rw,
+                                         Arr<int64_t> dst_off, Arr<int64_t> minfo, Arr<int32_t> msamples,
+                                         Arr<int64_t> runs, Arr<int64_t> info, Arr<int64_t> pes, int64_t max_pes,
+                                         int64_t max_run, Arr<int64_t> prot, Arr<uint8_t> const_iv, Arr<uint8_t> iv,
+                                         Arr<uint32_t> drk, Arr<uint8_t> enable, int64_t max_range, py::array ranges,
+                                         py::array cinfo) {
+    const std::string name(op);
     const int64_t B = src_off.size();
     if (max_pes <= 0 || !mp4::max_rows_ok(max_run) || !mp4::max_range_ok(max_range))
-      throw std::invalid_argument("cbcs_decrypt_batch: max_pes must be positive, max_run 1 to 256, max_range 1 to 65536");
+      throw std::invalid_argument(name + ": max_pes must be positive, max_run 1 to 256, max_range 1 to 65536");
     uint8_t* dp = mut_ptr<uint8_t>(dst_rw, "dst");
     int32_t* rg = mut_ptr<int32_t>(ranges, "ranges");
     int64_t* ci = mut_ptr<int64_t>(cinfo, "cinfo");
@@ -728,8 +734,8 @@ PYBIND11_MODULE(_runtime, m) {
         pes.size() < ts::pes_words(B, max_pes) || prot.size() < B * mp4::kTracks * mp4::kProtWords ||
         const_iv.size() < B * mp4::kTracks * es::kAesBlock || iv.size() < B * es::kAesBlock ||
         drk.size() < B * es::kAesRoundKeyWords || enable.size() < B ||
-        ranges.size() < table_words(B, max_range, mp4::kRangeWords) || cinfo.size() < B * mp4::kCbInfoWords)
-      throw std::invalid_argument("cbcs_decrypt_batch: an argument is too small");
+        ranges.size() < table_words(B, max_range, range_words) || cinfo.size() < B * info_words)
+      throw std::invalid_argument(name + ": an argument is too small");
     const int64_t *so = src_off.data(), *l = len.data(), *dof = dst_off.data();
     const uint8_t* en = enable.data();
     int64_t total = 0;
@@ -737,31 +743,39 @@ PYBIND11_MODULE(_runtime, m) {
       if (!en[b]) continue;
       if (so[b] < 0 || l[b] < 0 || l[b] >= (int64_t(1) << 31) || so[b] + l[b] > src.size() || dof[b] < 0 ||
           dof[b] + l[b] > dst_rw.size())
-        throw std::invalid_argument("cbcs_decrypt_batch: segment out of bounds");
+        throw std::invalid_argument(name + ": segment out of bounds");
       total += l[b];
     }
     const uint8_t* sp = src.data();
-    if (sp == dp) throw std::invalid_argument("cbcs_decrypt_batch: cannot run in place");
+    if (sp == dp) throw std::invalid_argument(name + ": cannot run in place");
     const int64_t *mi = minfo.data(), *rn = runs.data(), *in = info.data(), *pe = pes.data(), *pr = prot.data();
     const int32_t* ms = msamples.data();
     const uint8_t *civ = const_iv.data(), *ivp = iv.data();
     const uint32_t* rk = drk.data();
     py::gil_scoped_release nogil;
     parallel_for(B, [&](int64_t b) {
-      int32_t* rows = rg + table_words(b, max_range, mp4::kRangeWords);
-      int64_t* row = ci + b * mp4::kCbInfoWords;
+      int32_t* rows = rg + table_words(b, max_range, range_words);
+      int64_t* row = ci + b * info_words;
       if (!en[b]) {
-        std::fill(rows, rows + table_words(1, max_range, mp4::kRangeWords), -1);
-        std::fill(row, row + mp4::kCbInfoWords, int64_t(0));
+        std::fill(rows, rows + table_words(1, max_range, range_words), -1);
+        std::fill(row, row + info_words, int64_t(0));
         return;
       }
       const mp4::CbcsDemux md{mi + b * mp4::kMinfoWords, rn + table_words(b, max_run, mp4::kRunWords),
                               in + b * ts::kInfoWords, pe + ts::pes_words(b, max_pes),
                               ms + table_words(b, mp4::kTracks * max_pes, mp4::kMsampleWords), max_pes, max_run};
-      mp4::cbcs_segment(sp + so[b], l[b], md, pr + b * mp4::kTracks * mp4::kProtWords,
-                        civ + b * mp4::kTracks * es::kAesBlock, ivp + b * es::kAesBlock, rk + b * es::kAesRoundKeyWords,
-                        max_range, dp + dof[b], rows, row);
+      segment(sp + so[b], l[b], md, pr + b * mp4::kTracks * mp4::kProtWords, civ + b * mp4::kTracks * es::kAesBlock,
+              ivp + b * es::kAesBlock, rk + b * es::kAesRoundKeyWords, max_range, dp + dof[b], rows, row);
     }, total);
+  };
+  m.def("cbcs_decrypt_batch", [](Arr<uint8_t> src, Arr<int64_t> src_off, Arr<int64_t> len, py::array dst_rw,
+                                 Arr<int64_t> dst_off, Arr<int64_t> minfo, Arr<int32_t> msamples, Arr<int64_t> runs,
+                                 Arr<int64_t> info, Arr<int64_t> pes, int64_t max_pes, int64_t max_run,
+                                 Arr<int64_t> prot, Arr<uint8_t> const_iv, Arr<uint8_t> iv, Arr<uint32_t> drk,
+                                 Arr<uint8_t> enable, int64_t max_range, py::array ranges, py::array cinfo) {
+    protected_batch("cbcs_decrypt_batch", mp4::kRangeWords, mp4::kCbInfoWords, &mp4::cbcs_segment, src, src_off, len,
+                    dst_rw, dst_off, minfo, msamples, runs, info, pes, max_pes, max_run, prot, const_iv, iv, drk, enable,
+                    max_range, ranges, cinfo);
   });
   m.attr("CBCS_PROT_WORDS") = mp4::kProtWords;
   m.attr("CBCS_CINFO_WORDS") = mp4::kCbInfoWords;
@@ -781,6 +795,29 @@ PYBIND11_MODULE(_runtime, m) {
                                {"overlap", mp4::kCbOverlap}});
   name_dict(m, "CBCS_RANGE", {{"offset", mp4::kRgOffset}, {"length", mp4::kRgLength}, {"sample", mp4::kRgSample},
                               {"rank", mp4::kRgRank}});
+
+  // Batched CPU cenc (AES-CTR) decryption with the device kernels' result (docs/CENC.md): the
+  // arguments of cbcs_decrypt_batch, but
+  //   erk: uint32[B, 44] (expand_key_enc); ranges: int32[B, max_range, CENC_RANGE_WORDS]; cinfo: int64[B, CENC_CINFO_WORDS]
+  m.def("cenc_decrypt_batch", [](Arr<uint8_t> src, Arr<int64_t> src_off, Arr<int64_t> len, py::array dst_rw,
+                                 Arr<int64_t> dst_off, Arr<int64_t> minfo, Arr<int32_t> msamples, Arr<int64_t> runs,
+                                 Arr<int64_t> info, Arr<int64_t> pes, int64_t max_pes, int64_t max_run,
+                                 Arr<int64_t> prot, Arr<uint8_t> const_iv, Arr<uint8_t> iv, Arr<uint32_t> erk,
+                                 Arr<uint8_t> enable, int64_t max_range, py::array ranges, py::array cinfo) {
+    protected_batch("cenc_decrypt_batch", mp4::kCnRangeWords, mp4::kCnInfoWords, &mp4::cenc_segment, src, src_off, len,
+                    dst_rw, dst_off, minfo, msamples, runs, info, pes, max_pes, max_run, prot, const_iv, iv, erk, enable,
+                    max_range, ranges, cinfo);
+  });
+  m.attr("CENC_CINFO_WORDS") = mp4::kCnInfoWords;
+  m.attr("CENC_RANGE_WORDS") = mp4::kCnRangeWords;
+  m.attr("CENC_TILE_UNITS") = mp4::kCnTileUnits;
+  name_dict(m, "CENC_CINFO", {{"status", mp4::kCnStatus}, {"n_ranges", mp4::kCnNumRanges},
+                              {"video_samples", mp4::kCnVideoSamples}, {"audio_samples", mp4::kCnAudioSamples},
+                              {"video_bytes", mp4::kCnVideoBytes}, {"audio_bytes", mp4::kCnAudioBytes},
+                              {"n_senc", mp4::kCnNumSenc}, {"n_units", mp4::kCnNumUnits}});
+  name_dict(m, "CENC_RANGE", {{"offset", mp4::kCnOffset}, {"length", mp4::kCnLength}, {"sample", mp4::kCnSample},
+                              {"rank", mp4::kCnRank}, {"stream_pos", mp4::kCnStreamPos},
+                              {"iv_offset", mp4::kCnIvOffset}});
 
   // ------------------------------------------------------------------ store
   m.def("key_digest", [](Arr<int64_t> keys) {

@@ -1,8 +1,9 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
-// runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp) and by the gfx950
+// runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp,
+// runtime/cenc.cpp) and by the gfx950
 // kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip,
-// kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip).  Plain inline
+// kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -1126,6 +1127,29 @@ HLSP2P_RULE int64_t cipher_block_at(int64_t j, int64_t c, int64_t s) {
 // two byte spans [a0, a1) and [b0, b1), neither empty, share a byte
 HLSP2P_RULE bool spans_meet(int64_t a0, int64_t a1, int64_t b0, int64_t b1) {
   return a0 < a1 && b0 < b1 && a0 < b1 && b0 < a1;
+}
+
+// ---------------------------------------------------------------- cenc decryption (docs/CENC.md)
+// The protected bytes of a sample form one AES-CTR keystream that runs on across its clear bytes.
+// A range of len >= 1 bytes whose first byte is byte p0 of that stream is cut into units, one per
+// keystream block it touches.
+HLSP2P_RULE int64_t ctr_units(int64_t p0, int64_t len) { return len > 0 ? (p0 + len + 15) / 16 - p0 / 16 : 0; }
+// keystream block of unit m
+HLSP2P_RULE int64_t ctr_unit_block(int64_t p0, int64_t m) { return p0 / 16 + m; }
+// where byte 0 of keystream block j would lie in the segment for a range at off (below off for
+// the block a range starts inside)
+HLSP2P_RULE int64_t ctr_block_at(int64_t off, int64_t p0, int64_t j) { return off + 16 * j - p0; }
+// Counter block j of a 16-byte IV held as four little-endian words (as loaded): the last 8 bytes
+// are a big-endian integer that j is added to modulo 2^64; the first 8 never change.
+HLSP2P_RULE uint32_t ctr_bswap(uint32_t v) {
+  return (v << 24) | ((v & 0xff00u) << 8) | ((v >> 8) & 0xff00u) | (v >> 24);
+}
+HLSP2P_RULE void ctr_block(const uint32_t iv[4], int64_t j, uint32_t out[4]) {
+  const uint64_t low = ((static_cast<uint64_t>(ctr_bswap(iv[2])) << 32) | ctr_bswap(iv[3])) + static_cast<uint64_t>(j);
+  out[0] = iv[0];
+  out[1] = iv[1];
+  out[2] = ctr_bswap(static_cast<uint32_t>(low >> 32));
+  out[3] = ctr_bswap(static_cast<uint32_t>(low));
 }
 }  // namespace mp4
 }  // namespace hlsp2p

@@ -392,6 +392,35 @@ enum AuxRow : int {
 };
 constexpr int64_t cbcs_scratch(int64_t nseg, int64_t max_pes) { return nseg * kTracks * max_pes * kAuxWords; }
 constexpr int kCbTileBlocks = 256;  // cipher blocks per tile of the decrypt, a lane each
+
+// ---- cenc (AES-CTR) decryption of a demuxed batch (docs/CENC.md).  The protection row, the
+// status bits, the scratch row, kRgTrackShift and the max_range limits are the cbcs ones above.
+// cinfo[] row (int64)
+constexpr int kCnInfoWords = 8;
+enum CnInfo : int {
+  kCnStatus = 0,
+  kCnNumRanges = 1,  // true total of the ranges of at least one byte
+  kCnVideoSamples = 2, kCnAudioSamples = 3,  // samples with a protected byte
+  kCnVideoBytes = 4, kCnAudioBytes = 5,      // protected bytes, the unrecorded ranges' included
+  kCnNumSenc = 6,    // senc boxes that were read
+  kCnNumUnits = 7,   // keystream units, the unrecorded ranges' included
+};
+// ranges[] row (int32) [segment][max_range], -1 rows beyond the recorded ranges
+constexpr int kCnRangeWords = 8;
+enum CnRangeRow : int {
+  kCnOffset = 0, kCnLength = 1,
+  kCnSample = 2,     // track slot << kRgTrackShift | sample
+  kCnRank = 3,       // the range's first unit among the segment's
+  kCnStreamPos = 4,  // protected bytes of the sample in front of the range
+  kCnIvOffset = 5,   // where the sample's senc IV stands in the segment, -1: a constant or the job's IV
+  kCnSpare0 = 6, kCnSpare1 = 7,  // 0
+};
+// units per tile of the decrypt: 1024 lanes x kCnLaneUnits
+constexpr int kCnLaneUnits = 4;
+constexpr int kCnTileUnits = 1024 * kCnLaneUnits;
+// host bound of one segment's units: a range of len bytes has at most len / 16 + 2 (a keystream
+// block cut at both ends), and the recorded ranges share no byte
+constexpr int64_t cenc_unit_bound(int64_t cap, int64_t max_range) { return cap / 16 + 2 * max_range; }
 }  // namespace mp4
 
 // ---------------------------------------------------------------- CRC-32

@@ -768,7 +768,9 @@ class StreamController:
         iv = frag.iv_for_decrypt() if key is not None else None
         # METHOD=SAMPLE-AES: the segment is clear TS whose NAL units and ADTS frames are encrypted;
         # the key goes to the step behind the sample index (ops/sampleaes.py), not to the CBC decrypt
-        sample_key = dd.key if method == "SAMPLE-AES" else None
+        # (on fragmented MP4 also SAMPLE-AES-CTR: the init segment's scheme, cbcs or cenc, decides
+        # the decrypt, whichever of the two methods the playlist names; docs/CENC.md)
+        sample_key = dd.key if method in ("SAMPLE-AES", "SAMPLE-AES-CTR") else None
         sample_iv = frag.iv_for_decrypt() if sample_key is not None else None
         stats = data["stats"]
         payload = data["payload"]
@@ -787,6 +789,8 @@ class StreamController:
         # a segment a peer sent, delivered before its CRC check (gpuSwarm.deferVerify): the
         # transmux batch verifies it on the way through the decrypt
         ticket = getattr(payload, "swarm_verify", None)
+        if method == "SAMPLE-AES-CTR":  # no such thing on MPEG-TS: the fragment goes through as it is
+            sample_key = sample_iv = None
         pipeline_for(dev, self.loop).submit(
             TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
                         bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
@@ -843,7 +847,7 @@ class StreamController:
             job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag,
                               getattr(payload, "swarm_verify", None), bool(config.get("indexSamples")), False,
                               sample_key, sample_iv, bool(config.get("enableCEA708Captions")), mp4=init)
-        except ValueError as e:  # SAMPLE-AES on an init segment without a cbcs-protected track
+        except ValueError as e:  # SAMPLE-AES on an init segment without a cbcs- or cenc-protected track
             self._on_parsed(frag, stats, {"error": e, "status": -1})
             return
         pipeline_for(self.hls.transmux_device(payload), self.loop).submit(job)
@@ -858,8 +862,8 @@ class StreamController:
         if frag.initSegment not in self._mp4_announced:  # once per init segment
             self._mp4_announced.add(frag.initSegment)
             tracks = {}
-            # a cbcs fragment is buffered decrypted (docs/CBCS.md): its init segment without the sinf
-            init_data = init.clear_data if r.get("cbcs") is not None else init.data
+            # a cbcs or cenc fragment is buffered decrypted (docs/CBCS.md): its init segment without the sinf
+            init_data = init.clear_data if r.get("cbcs") is not None or r.get("cenc") is not None else init.data
             for name in ("video", "audio"):
                 t = r[name]
                 if t["id"] >= 0:
@@ -931,10 +935,11 @@ class StreamController:
             return
         if r.get("container") == "mp4":  # a fragmented-MP4 fragment has a branch of its own
             if r.get("error") is None:
-                cb = r.get("cbcs")
+                scheme = "cbcs" if r.get("cbcs") is not None else "cenc"
+                cb = r.get(scheme)
                 if cb is not None and cb["status"] & 0b111:  # ops.cbcs.CSTATUS range_overflow | no_senc | bad_senc
                     # ciphertext would be buffered: a decrypt error, retried by the rule below
-                    r = {"error": ValueError(f"cbcs status {cb['status']}"), "status": -1, "plain_bytes": -1}
+                    r = {"error": ValueError(f"{scheme} status {cb['status']}"), "status": -1, "plain_bytes": -1}
                 elif not r["status"] & 0b100001:  # ops.mp4demux.MSTATUS bad_box | sample_out_of_range
                     self._on_parsed_mp4(frag, stats, r)
                     return

@@ -11,6 +11,11 @@ from dataclasses import dataclass, field
 from typing import Any, List, Optional
 
 
+# the #EXT-X-KEY methods whose key is loaded: whole-segment CBC, sample encryption of TS or of
+# fragmented MP4 under cbcs, and of fragmented MP4 under cenc
+KEYED_METHODS = ("AES-128", "SAMPLE-AES", "SAMPLE-AES-CTR")
+
+
 @dataclass(slots=True)
 class DecryptData:
     method: Optional[str] = None
@@ -20,7 +25,7 @@ class DecryptData:
 
     @property
     def needs_key(self) -> bool:
-        return self.method in ("AES-128", "SAMPLE-AES") and self.uri is not None and self.key is None
+        return self.method in KEYED_METHODS and self.uri is not None and self.key is None
 
 
 @dataclass(frozen=True, slots=True)
@@ -92,7 +97,7 @@ class Fragment:
 
     def iv_for_decrypt(self) -> Optional[bytes]:
         dd = self.decryptdata
-        if dd is None or dd.method not in ("AES-128", "SAMPLE-AES"):
+        if dd is None or dd.method not in KEYED_METHODS:
             return None
         if dd.iv is not None:
             return dd.iv

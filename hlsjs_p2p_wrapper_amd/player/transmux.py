@@ -49,12 +49,13 @@ class TransmuxJob:
     code inside the compiled module.  ``mp4`` (an ``Mp4Init``): the payload is a fragmented-MP4 media
     segment of that init segment's tracks, not MPEG-TS (``docs/FMP4DEMUX.md``): the batch demuxes it
     where it lies and ``remux`` is ignored (the fragment already is fMP4).  ``sample_key`` with ``mp4``
-    asks for the ``cbcs`` decrypt (``docs/CBCS.md``): it is accepted when the init segment has a track
-    protected under the ``cbcs`` scheme (the key of ``sample_iv`` serves a track without an IV of its
+    asks for the ``cbcs`` decrypt (``docs/CBCS.md``) or the ``cenc`` decrypt (``docs/CENC.md``): it is
+    accepted when the init segment has a track protected under one of the two schemes, which decides
+    the decrypt that runs (``scheme``; the key of ``sample_iv`` serves a track without an IV of its
     own), and the result's ``data`` and views are then those of the decrypted copy."""
 
     __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
-                 "captions", "mp4")
+                 "captions", "mp4", "scheme")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
@@ -84,10 +85,14 @@ class TransmuxJob:
         self.captions = captions
         # True (implies ``index``): the batch also extracts the CEA-608/708 caption data of this
         # fragment's SEI NAL units (ops/captions.py) and its result gains ``captions``
+        self.scheme = None  # "cbcs" / "cenc": the decrypt of a fragmented-MP4 job that asked
         if mp4 is not None and sample_key is not None:
             schemes = [getattr(getattr(t, "protection", None), "scheme", None) for t in getattr(mp4, "tracks", ())]
-            if "cbcs" not in schemes:
+            if "cbcs" in schemes and "cenc" in schemes:
+                raise ValueError("TransmuxJob: an init segment with a cbcs and a cenc track is not supported")
+            if "cbcs" not in schemes and "cenc" not in schemes:
                 raise ValueError("TransmuxJob: SAMPLE-AES (cbcs) fragmented MP4 is not supported")
+            self.scheme = "cbcs" if "cbcs" in schemes else "cenc"
             if key is not None:
                 raise ValueError("TransmuxJob: a fragmented-MP4 fragment is AES-128 or SAMPLE-AES, not both")
         self.mp4 = mp4
@@ -496,9 +501,9 @@ class MediaPipeline:
     def _launch_mp4(self, jobs: List[TransmuxJob]) -> "_Mp4Batch":
         """Enqueue the fragmented-MP4 jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
         rows, one ``mp4_demux_batch`` per group (the encrypted rows in the decrypt's buffer, the clear
-        ones where they lie, the ``cbcs`` ones where they lie as a group of their own), one
-        ``cbcs_decrypt_batch`` behind the demux of the ``cbcs`` group, whose views then are those of
-        the decrypted copy, and one ``caption_batch`` over a group's views when a job of it asked;
+        ones where they lie, the ``cbcs`` and the ``cenc`` ones where they lie as a group each), one
+        ``cbcs_decrypt_batch`` / ``cenc_decrypt_batch`` behind the demux of such a group, whose views
+        then are those of the decrypted copy, and one ``caption_batch`` over a group's views when a job of it asked;
         ``minfo``, ``info``, ``sinfo``, the ``emsg`` table and the ``cinfo`` / ``ccinfo`` rows are on
         their way to pinned host memory in front of the event."""
         from ..ops import mp4demux as _mp4
@@ -523,8 +528,8 @@ class MediaPipeline:
                 out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
                                                  [bytes(jobs[i].iv) for i in il], dec, dec_offs)
                 work.append((e, dec, dec_offs, out_len, caps))
-            asks = np.array([j.sample_key is not None for j in jobs], dtype=bool)
-            for rows in (cl[~asks[cl]], cl[asks[cl]]):
+            scheme = np.array([{"cbcs": 1, "cenc": 2}.get(j.scheme, 0) for j in jobs], dtype=np.int64)
+            for rows in (cl[scheme[cl] == 0], cl[scheme[cl] == 1], cl[scheme[cl] == 2]):
                 if len(rows):
                     work.append((rows, src, offs[rows], nb[rows], nb[rows]))
             groups = []
@@ -532,16 +537,19 @@ class MediaPipeline:
                 il = idx.tolist()
                 md = _mp4.mp4_demux_batch(buf, o, lens, [jobs[i].mp4 for i in il], caps=caps)
                 cb = None
-                if asks[il[0]]:  # out of place: buf may be the arena that peers are served from
-                    from ..ops import cbcs as _cbcs
-
-                    cb = _cbcs.cbcs_decrypt_batch(md, [jobs[i].mp4 for i in il], [jobs[i].sample_key for i in il],
-                                                  [jobs[i].sample_iv for i in il])
+                if scheme[il[0]]:  # out of place: buf may be the arena that peers are served from
+                    if scheme[il[0]] == 1:
+                        from ..ops.cbcs import cbcs_decrypt_batch as decrypt
+                    else:
+                        from ..ops.cenc import cenc_decrypt_batch as decrypt
+                    cb = decrypt(md, [jobs[i].mp4 for i in il], [jobs[i].sample_key for i in il],
+                                 [jobs[i].sample_iv for i in il])
                     md = cb.md
                 g = _Mp4Group(idx, md, _to_host(md.minfo), _to_host(md.info), _to_host(md.sinfo), _to_host(md.emsg),
                               _to_host(lens) if isinstance(lens, torch.Tensor) else lens)
                 if cb is not None:
                     g.cbinfo = _to_host(cb.cinfo)
+                    g.scheme = "cbcs" if scheme[il[0]] == 1 else "cenc"
                 asked = [bool(jobs[i].captions) for i in il]
                 if any(asked):
                     from ..ops import captions as _cc
@@ -557,6 +565,7 @@ class MediaPipeline:
     def _complete_mp4(self, b: "_Mp4Batch") -> None:
         """Wait for the fragmented-MP4 jobs of a batch and run their callbacks."""
         from ..ops.cbcs import segment_view as cbcs_view
+        from ..ops.cenc import segment_view as cenc_view
         from ..ops.mp4demux import EMSG, MINFO
 
         if b.error is not None:
@@ -588,7 +597,8 @@ class MediaPipeline:
                 if g.cc is not None and job.captions:
                     r["captions"] = CaptionData(g, k)
                 if g.cbinfo is not None:
-                    r["cbcs"] = MappingProxyType(cbcs_view(_np(g.cbinfo)[k]))
+                    view = cbcs_view if g.scheme == "cbcs" else cenc_view
+                    r[g.scheme] = MappingProxyType(view(_np(g.cbinfo)[k]))
                 results[i] = r
         for j, r in zip(b.jobs, results):
             j.callback(r)
@@ -1079,7 +1089,8 @@ class _Mp4Group:
     hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
     cc: Any = None  # Captions, when a job of the group asked for it, with ...
     ccinfo: Any = None  # ... its ccinfo rows on the host
-    cbinfo: Any = None  # the cinfo rows of a cbcs group on the host
+    cbinfo: Any = None  # the cinfo rows of a cbcs or cenc group on the host
+    scheme: str = ""    # "cbcs" / "cenc" where cbinfo is set
 
 
 @dataclass(eq=False)

@@ -4,7 +4,8 @@ index over the demuxed ES, the remux to fMP4 samples, the codec configuration fo
 (H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
 on a video ES the tool writes itself, the fragmented-MP4 demux on segments the tool writes itself (one
 ``moof`` and thirty), the cbcs decrypt of such segments protected by the tool (the demux row's segment and
-one of about 3 MB), and the MFMA CRC with HIP events and reports us / GB/s of input.
+one of about 3 MB), the cenc decrypt of the same two segments protected under cenc, and the MFMA CRC
+with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
     PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
@@ -17,8 +18,9 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, codecconfig, crc, esindex, hevcconfig, mp4demux, remux,
-                                       sampleaes, segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, hevcconfig, mp4demux,
+                                       remux, sampleaes, segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops._native import runtime
 
 
 def timed(fn, iters):
@@ -118,7 +120,8 @@ def mp4_segment(moofs, n_video=120, n_audio=188, seed=7, slice_bytes=200, senc=F
     track 2, spread over ``moofs`` pairs of ``moof`` + ``mdat``, each ``moof`` with one ``traf`` per
     track (``tfhd``, ``tfdt``, one ``trun`` with every per-sample field and a ``data_offset``).
     ``senc``: each ``traf`` also gets a ``senc`` box behind its ``trun``, the video one with a subsample
-    per NAL unit (its length and header byte clear), the audio one without subsample tables."""
+    per NAL unit (its length and header byte clear), the audio one without subsample tables;
+    ``senc="iv8"``: every entry of both also starts with the sample's 8-byte IV (:func:`cenc_iv`)."""
     rng = np.random.default_rng(seed)
 
     def box(kind, payload):
@@ -138,13 +141,15 @@ def mp4_segment(moofs, n_video=120, n_audio=188, seed=7, slice_bytes=200, senc=F
     for k in range(moofs):
         v = video[n_video * k // moofs:n_video * (k + 1) // moofs]
         a = audio[n_audio * k // moofs:n_audio * (k + 1) // moofs]
-        v0 = n_video * k // moofs
+        v0, a0 = n_video * k // moofs, n_audio * k // moofs
 
         vsenc = asenc = b""
         if senc:
-            subs = b"".join(struct.pack(">H", 3) + struct.pack(">HIHIHI", 5, 1, 5, 70, 5, len(x) - 86) for x in v)
+            iv = (lambda t, i: cenc_iv(t, i)) if senc == "iv8" else (lambda t, i: b"")
+            subs = b"".join(iv(0, v0 + i) + struct.pack(">H", 3) + struct.pack(">HIHIHI", 5, 1, 5, 70, 5, len(x) - 86)
+                            for i, x in enumerate(v))
             vsenc = full(b"senc", 0, 2, struct.pack(">I", len(v)) + subs)
-            asenc = full(b"senc", 0, 0, struct.pack(">I", len(a)))
+            asenc = full(b"senc", 0, 0, struct.pack(">I", len(a)) + b"".join(iv(1, a0 + i) for i in range(len(a))))
 
         def moof(voff, aoff):
             vrows = b"".join(struct.pack(">IIIi", 3000, len(x), 0x02000000 if (v0 + i) % 30 == 0 else 0x01010000,
@@ -242,6 +247,69 @@ def cbcs_row(slice_bytes, segs, iters, dev):
     cp = torch.empty_like(d)
     return (round(timed(lambda: cbcs.cbcs_decrypt_batch(md, tracks, keys), iters), 1),
             round(timed(lambda: segment.copy_segments(d, cp, offs, offs, lens), iters), 1), blocks * segs)
+
+
+def cenc_iv(track, index):
+    """The tool's 8-byte per-sample IV of sample ``index`` of track slot ``track``."""
+    return struct.pack(">II", 0xC0DE0000 | track, index)
+
+
+def cenc_protect(seg, md):
+    """The tool's cenc packager: ``seg`` (a host array of one :func:`mp4_segment` with ``senc="iv8"``,
+    changed in place) with every NAL unit behind its header byte and every audio sample XORed with
+    the sample's AES-CTR keystream (low 64 counter bits, the keystream running on across a sample's
+    clear bytes), block by block with the host's forward AES.  Returns the bytes protected."""
+    enc, total = runtime().aes_encrypt_block, 0
+
+    def sample(track, index, ranges):
+        nonlocal total
+        n = sum(z for _, z in ranges)
+        iv = cenc_iv(track, index)
+        ks = np.frombuffer(b"".join(enc(CBCS_KEY, iv + j.to_bytes(8, "big")) for j in range((n + 15) // 16)), np.uint8)
+        p = 0
+        for off, z in ranges:
+            seg[off:off + z] ^= ks[p:p + z]
+            p += z
+        total += n
+    for k in range(int(md.minfo[0, 6])):
+        off, n = int(md.pes[0, 0, k, 0]), int(md.msamples[0, 0, k, 0])
+        sample(0, k, [(off + 5, 1), (off + 11, 70), (off + 86, n - 86)])
+    for k in range(int(md.minfo[0, 12])):
+        sample(1, k, [(int(md.pes[0, 1, k, 0]), int(md.msamples[0, 1, k, 0]))])
+    return total
+
+
+def cenc_row(slice_bytes, segs, iters, dev):
+    """``cenc_decrypt_batch`` on ``segs`` copies of the :func:`cbcs_row` segment protected under cenc
+    instead (8-byte per-sample IVs, a subsample per NAL unit, audio whole): (us per call, bytes
+    protected per call), after checking segment 0 and the last segment of the device result against
+    the host implementation and against the clear bytes."""
+    clear = np.frombuffer(mp4_segment(1, slice_bytes=slice_bytes, senc="iv8"), np.uint8)
+    prot = cenc.Mp4Protection("cenc", 0, 0, 8, b"", bytes(16))
+    tracks = (mp4demux.Mp4Track(1, "video", 0x1B, 4, protection=prot),
+              mp4demux.Mp4Track(2, "audio", 0x0F, protection=prot))
+    stride = (len(clear) + 255) // 256 * 256
+    one = np.zeros(stride + 256, np.uint8)
+    one[:len(clear)] = clear
+    hmd = mp4demux.mp4_demux_batch(torch.from_numpy(one), [0], [len(clear)], tracks)
+    nbytes = cenc_protect(one, hmd)
+    buf = np.zeros(stride * segs + 256, np.uint8)
+    offs, lens = [stride * i for i in range(segs)], [len(clear)] * segs
+    for o in offs:
+        buf[o:o + len(clear)] = one[:len(clear)]
+    d = torch.from_numpy(buf).to(dev)
+    md = mp4demux.mp4_demux_batch(d, offs, lens, tracks)
+    keys = [CBCS_KEY] * segs
+    got = cenc.cenc_decrypt_batch(md, tracks, keys)
+    host = cenc.cenc_decrypt_batch(hmd, tracks, keys[:1])
+    ci = got.cinfo.cpu()
+    for i in (0, segs - 1):
+        assert torch.equal(ci[i], host.cinfo[0]) and torch.equal(got.ranges[i].cpu(), host.ranges[0]), "cenc mismatch"
+        mine = got.buf[int(got.offs[i]):int(got.offs[i]) + len(clear)].cpu().numpy()
+        assert np.array_equal(mine, host.buf[:len(clear)].numpy()) and np.array_equal(mine, clear), "cenc bytes"
+    assert ci[:, 0].sum() == 0 and ((ci[:, 4] + ci[:, 5]) == nbytes).all() and nbytes > 0, "cenc totals"
+    assert not np.array_equal(one[:len(clear)], clear), "cenc packager"
+    return round(timed(lambda: cenc.cenc_decrypt_batch(md, tracks, keys), iters), 1), nbytes * segs
 
 
 def main():
@@ -370,6 +438,10 @@ def main():
     res["cbcs_us"], res["cbcs_copy_us"], res["cbcs_blocks"] = cbcs_row(200, args.segs, args.iters, dev)
     res["cbcs_large_us"], res["cbcs_large_copy_us"], res["cbcs_large_blocks"] = cbcs_row(23000, args.segs, args.iters,
                                                                                         dev)
+    # the cenc decrypt (copy, plan, the AES-CTR units on the bulk decrypt's LDS image) of the same two
+    # segments protected under cenc: every NAL unit behind its header byte and the audio whole
+    res["cenc_us"], res["cenc_bytes"] = cenc_row(200, args.segs, args.iters, dev)
+    res["cenc_large_us"], res["cenc_large_bytes"] = cenc_row(23000, args.segs, args.iters, dev)
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
