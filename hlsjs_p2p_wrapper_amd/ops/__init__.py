@@ -1,17 +1,19 @@
-"""Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``,
+"""Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``, ``fragment``,
 ``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``, ``cenc``): import the
 submodule you need.  The entry points of the sample index, of the remux, of the two codec configurations, of the
 SAMPLE-AES decrypt, of the caption extraction, of the fragmented-MP4 demux and of the cbcs and cenc decrypts are
 also reachable from the package
 (``ops.index_batch``,
 ``ops.EsIndex``, ``ops.remux_batch``,
-``ops.Remuxed``, ``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
+``ops.Remuxed``, ``ops.fragment_batch``, ``ops.Fragments``,
+``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
 ``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``, ``ops.caption_batch``,
 ``ops.Captions``, ``ops.mp4_demux_batch``, ``ops.Mp4Demux``, ``ops.Mp4Track``, ``ops.cbcs_decrypt_batch``,
 ``ops.Cbcs``, ``ops.Mp4Protection``, ``ops.cenc_decrypt_batch``, ``ops.Cenc``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
+_FRAGMENT = ("fragment_batch", "Fragments")
 _CODECCONFIG = ("config_batch", "CodecConfig")
 _HEVCCONFIG = ("hevc_config_batch", "HevcConfig")
 _SAMPLEAES = ("sample_decrypt_batch", "SampleAes")
@@ -19,7 +21,8 @@ _CAPTIONS = ("caption_batch", "Captions")
 _MP4DEMUX = ("mp4_demux_batch", "Mp4Demux", "Mp4Track")
 _CBCS = ("cbcs_decrypt_batch", "Cbcs", "Mp4Protection")
 _CENC = ("cenc_decrypt_batch", "Cenc")
-__all__ = list(_ESINDEX + _REMUX + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS + _CENC)
+__all__ = list(_ESINDEX + _REMUX + _FRAGMENT + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS
+               + _CENC)
 
 
 def __getattr__(name):
@@ -31,6 +34,10 @@ def __getattr__(name):
         from . import remux
 
         return getattr(remux, name)
+    if name in _FRAGMENT:
+        from . import fragment
+
+        return getattr(fragment, name)
     if name in _CODECCONFIG:
         from . import codecconfig
 

@@ -170,13 +170,16 @@ void es_index(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t 
 }
 
 // Remux of a demuxed and indexed batch (remux.hip): the inputs of es_index, its four outputs, and
-// per segment a region of es::remux_out_bytes(cap, max_nal) bytes of `out` at out_off (the Python
-// wrapper has checked the regions against out); tile_prefix counts ceil(region / remux_tile_bytes()).
+// per segment a region of es::remux_out_bytes(cap, max_nal) + audio_gap bytes of `out` at out_off (the
+// Python wrapper has checked the regions against out); tile_prefix counts ceil(region / remux_tile_bytes()).
 void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
            int64_t max_pes, int64_t max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int64_t max_aframes,
-           Tensor scratch, Tensor vsamples, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off) {
+           Tensor scratch, Tensor vsamples, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off,
+           int64_t audio_gap) {
   const int64_t B = es_off.numel();
   TORCH_CHECK(max_aframes > 0, "remux: max_aframes out of range");
+  TORCH_CHECK(audio_gap >= 0 && audio_gap % 16 == 0 && audio_gap < (int64_t(1) << 30),
+              "remux: audio_gap must be a non-negative multiple of 16");
   const D::RemuxArgs a{
       .b = es_batch("remux", es, es_off, cap, tile_prefix, total_tiles, info, pes, max_pes, max_nal, nal, au, aframes,
                     sinfo),
@@ -186,11 +189,39 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
             check<int32_t>(asamples, "asamples", hlsp2p::table_words(B, max_aframes, es_::kAsampleWords)),
             check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
       .out = check<uint8_t>(out, "out"),
-      .out_off = check<int64_t>(out_off, "out_off", B)};
+      .out_off = check<int64_t>(out_off, "out_off", B),
+      .audio_gap = audio_gap};
   same_device(es, {scratch, vsamples, asamples, rinfo, out, out_off});
   aligned16({{out, "out"}});
   TORCH_CHECK(es.data_ptr() != out.data_ptr(), "remux cannot run in place");
   hip_ok(D::launch_remux(a), "remux launch");
+}
+
+// The moof boxes of a remuxed batch (fragment.hip): remux's three tables, es_index's sinfo, one
+// fparams row per segment (the Python wrapper has checked the regions against out and against each
+// other; the kernel leaves a row alone that does not lie inside out) and `out` as remux left it.
+void fragment_moof(Tensor rinfo, Tensor vsamples, Tensor asamples, Tensor sinfo, Tensor fparams, int64_t max_pes,
+                   int64_t max_aframes, int64_t headroom, int64_t audio_gap, Tensor out, Tensor finfo) {
+  const int64_t B = fparams.numel() / es_::kFparamWords;
+  TORCH_CHECK(max_pes > 0 && max_aframes > 0 && max_pes <= 0x7fffffff / 16 && max_aframes <= 0x7fffffff / 16,
+              "fragment_moof: max_pes / max_aframes out of range");
+  TORCH_CHECK(headroom >= es_::frag_headroom(max_pes), "fragment_moof: headroom below frag_headroom(max_pes)");
+  TORCH_CHECK(audio_gap >= es_::frag_audio_gap(max_aframes) && audio_gap % 16 == 0,
+              "fragment_moof: audio_gap below frag_audio_gap(max_aframes) or no multiple of 16");
+  TORCH_CHECK(fparams.numel() == B * es_::kFparamWords, "fragment_moof: fparams is not a whole number of rows");
+  const D::FragmentArgs a{
+      .rinfo = check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords),
+      .vsamples = check<int32_t>(vsamples, "vsamples", hlsp2p::table_words(B, max_pes, es_::kVsampleWords)),
+      .asamples = check<int32_t>(asamples, "asamples", hlsp2p::table_words(B, max_aframes, es_::kAsampleWords)),
+      .sinfo = check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords),
+      .fparams = check<int64_t>(fparams, "fparams"),
+      .max_pes = max_pes, .max_aframes = max_aframes, .headroom = headroom, .audio_gap = audio_gap,
+      .out = check<uint8_t>(out, "out"), .out_numel = out.numel(),
+      .finfo = check<int64_t>(finfo, "finfo", B * es_::kFinfoWords),
+      .nseg = static_cast<int>(B), .stream = stream()};
+  same_device(out, {rinfo, vsamples, asamples, sinfo, fparams, finfo});
+  aligned16({{out, "out"}});
+  hip_ok(D::launch_fragment_moof(a), "fragment_moof launch");
 }
 
 // Codec configuration of a demuxed and indexed batch (codec_config.hip): the inputs of es_index
@@ -514,7 +545,9 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
         "int max_pes, int max_nal, Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_aframes, "
         "Tensor(a!) scratch, Tensor(b!) vsamples, Tensor(c!) asamples, Tensor(d!) rinfo, Tensor(e!) out, "
-        "Tensor out_off) -> ()");
+        "Tensor out_off, int audio_gap=0) -> ()");
+  m.def("fragment_moof(Tensor rinfo, Tensor vsamples, Tensor asamples, Tensor sinfo, Tensor fparams, int max_pes, "
+        "int max_aframes, int headroom, int audio_gap, Tensor(a!) out, Tensor(b!) finfo) -> ()");
   m.def("codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
   m.def("hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
@@ -547,6 +580,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("ts_demux", &ts_demux);
   m.impl("es_index", &es_index);
   m.impl("remux", &remux);
+  m.impl("fragment_moof", &fragment_moof);
   m.impl("codec_config", &codec_config);
   m.impl("hevc_config", &hevc_config);
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
@@ -581,12 +615,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("es_index_scratch_words", [](int64_t total_tiles, int64_t nseg, int64_t max_nal) {
     return es_::index_scratch(total_tiles, nseg, max_nal).end;
   }, py::arg("total_tiles"), py::arg("nseg"), py::arg("max_nal"));
-  m.def("remux", &remux);
+  m.def("remux", &remux, py::arg("es"), py::arg("es_off"), py::arg("cap"), py::arg("tile_prefix"),
+        py::arg("total_tiles"), py::arg("info"), py::arg("pes"), py::arg("max_pes"), py::arg("max_nal"), py::arg("nal"),
+        py::arg("au"), py::arg("aframes"), py::arg("sinfo"), py::arg("max_aframes"), py::arg("scratch"),
+        py::arg("vsamples"), py::arg("asamples"), py::arg("rinfo"), py::arg("out"), py::arg("out_off"),
+        py::arg("audio_gap") = 0);
   m.def("remux_tile_bytes", &D::remux_tile_bytes);
   m.def("remux_out_bytes", py::vectorize(&es_::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
     return es_::remux_scratch(nseg, max_nal, max_aframes).end;
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
+  m.def("fragment_moof", &fragment_moof);
   m.def("codec_config", &codec_config);
   m.def("hevc_config", &hevc_config);
   m.def("sample_aes_decrypt", &sample_aes_decrypt);

@@ -116,15 +116,37 @@ int es_index_tile_bytes();
 hipError_t launch_es_index(const EsIndexArgs& a);
 
 struct RemuxArgs {
-  EsBatch b;  // tiles of es::remux_out_bytes(cap, max_nal); ix is launch_es_index's output, only read
+  EsBatch b;  // tiles of es::remux_out_bytes(cap, max_nal) + audio_gap; ix is launch_es_index's output, only read
   int64_t max_aframes;
   int32_t* scratch;  // es::remux_scratch(nseg, max_nal, max_aframes)
   es::RemuxTables t;
   uint8_t* out;
   const int64_t* out_off;
+  int64_t audio_gap = 0;  // free bytes in front of the audio box, a non-negative multiple of 16
 };
 int remux_tile_bytes();
 hipError_t launch_remux(const RemuxArgs& a);
+
+// fragment.hip: the two moof boxes of every segment of a remuxed batch (docs/FRAGMENT.md), written
+// into the room launch_remux's caller left: headroom bytes in front of each region, audio_gap in
+// front of each audio box.  One workgroup per segment; a segment whose fparams row does not lie
+// inside out (16-byte aligned, headroom in front, region behind) is left alone, finfo row included.
+struct FragmentArgs {
+  const int64_t* rinfo;     // launch_remux's three tables, only read
+  const int32_t* vsamples;  // nseg x max_pes x es::kVsampleWords
+  const int32_t* asamples;  // nseg x max_aframes x es::kAsampleWords
+  const int64_t* sinfo;     // launch_es_index's: the audio sample rate
+  const int64_t* fparams;   // nseg x es::kFparamWords
+  int64_t max_pes, max_aframes;
+  int64_t headroom;   // >= es::frag_headroom(max_pes)
+  int64_t audio_gap;  // >= es::frag_audio_gap(max_aframes), a multiple of 16: what launch_remux took
+  uint8_t* out;       // 16-byte aligned
+  int64_t out_numel;
+  int64_t* finfo;  // nseg x es::kFinfoWords
+  int nseg;
+  hipStream_t stream;
+};
+hipError_t launch_fragment_moof(const FragmentArgs& a);
 
 struct CodecConfigArgs {
   EsBatch b;       // no tile space (tile_prefix == nullptr, total_tiles == 0); ix is only read

@@ -7,7 +7,8 @@
 //   asamples: int32[seg][max_aframes][kAsampleWords]  (AsampleRow: offset, size; -1 rows beyond)
 //   rinfo:    int64[seg][kRinfoWords]
 //   out:      at out_off[seg]: 'mdat' box of the video payload (4-byte length + NAL bytes per
-//             kept NAL), then at the next multiple of 16 the 'mdat' box of the ADTS frame bodies
+//             kept NAL), then at the next multiple of 16 (behind audio_gap free bytes, default
+//             none: docs/FRAGMENT.md) the 'mdat' box of the ADTS frame bodies
 //
 // Two launches on the caller's stream, no host round trip (host caps size the tile space and
 // bound every access):
@@ -62,13 +63,14 @@ __device__ __forceinline__ int32_t rx_sat32(int64_t v) { return v < 0x7fffffff ?
 // The batch arrives as separate parameters here and becomes a view in the kernel: only a kernel
 // argument carries readonly and noalias, which keep the uniform loads behind the first global
 // store scalar.  With the view by value this kernel takes 85 VGPRs (occupancy 5) against 75 (6).
+// audio_gap (docs/FRAGMENT.md) rides as one more scalar: still 75 VGPRs, occupancy 6, no scratch.
 __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
     const uint8_t* __restrict__ es, const int64_t* __restrict__ es_off, const int64_t* __restrict__ cap,
     const int64_t* __restrict__ info, const int64_t* __restrict__ pes, int64_t max_pes, int64_t max_nal,
     const int32_t* __restrict__ nal_all, const int32_t* __restrict__ au_all, const int32_t* __restrict__ af_all,
     const int64_t* __restrict__ sinfo, int64_t max_aframes, int32_t* __restrict__ scratch,
     int32_t* __restrict__ vs_all, int32_t* __restrict__ as_all, int64_t* __restrict__ rinfo, uint8_t* __restrict__ out,
-    const int64_t* __restrict__ out_off) {
+    const int64_t* __restrict__ out_off, int64_t audio_gap) {
   __shared__ int64_t s_w[kRxWaves];
   __shared__ unsigned long long s_first_unfit;  // payload offset of the first kept NAL without room
   __shared__ int s_bad, s_nrec, s_q, s_aover;
@@ -95,7 +97,7 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
   int32_t* astart = sc + part.astart;
   int32_t* asrc = sc + part.asrc;
   uint8_t* o = out + out_off[seg];
-  const int64_t region = es::remux_out_bytes(room_es, max_nal);
+  const int64_t region = es::remux_out_bytes(room_es, max_nal) + audio_gap;
   const int64_t v_limit = es::remux_video_limit(room_es, max_nal);
   if (tid == 0) {
     s_first_unfit = ~0ull;
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(kRxThreads) void remux_plan_kernel(
   }
 
   // ---- audio: a lane per PES walks its counted frames, twice around the scan of the totals
-  const int64_t A0 = (8 + P + 15) & ~int64_t(15);
+  const int64_t A0 = es::audio_box_offset(P, audio_gap);
   const int64_t a_room = region - (A0 + 8);
   const es::AudioSpan audio = es::audio_span(sg);
   const int64_t ma = audio.n_adts, a_off = audio.off;
@@ -361,7 +363,7 @@ hipError_t launch_remux(const RemuxArgs& a) {
   const EsBatchView view = es_batch_view(b);
   hipLaunchKernelGGL(remux_plan_kernel, dim3(b.nseg), dim3(kRxThreads), 0, b.stream, b.es, b.es_off, b.cap, b.info,
                      b.pes, b.max_pes, b.max_nal, b.ix.nal, b.ix.au, b.ix.aframes, b.ix.sinfo, a.max_aframes, a.scratch,
-                     a.t.vsamples, a.t.asamples, a.t.rinfo, a.out, a.out_off);
+                     a.t.vsamples, a.t.asamples, a.t.rinfo, a.out, a.out_off, a.audio_gap);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess || b.total_tiles <= 0) return e;
   hipLaunchKernelGGL(remux_copy_kernel, dim3(static_cast<unsigned>(b.total_tiles)), dim3(kRxThreads), 0, b.stream,

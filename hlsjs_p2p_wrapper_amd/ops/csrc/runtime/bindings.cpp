@@ -26,6 +26,7 @@
 #include "codec.hpp"
 #include "crc_host.hpp"
 #include "es.hpp"
+#include "fragment.hpp"
 #include "hevc.hpp"
 #include "locator.hpp"
 #include "mp4.hpp"
@@ -429,15 +430,18 @@ PYBIND11_MODULE(_runtime, m) {
   name_dict(m, "ES_AU_FLAGS", {{"keyframe", es::kAuKeyframe}, {"sps", es::kAuSps}, {"pps", es::kAuPps},
                                {"aud", es::kAuAud}});
   // Batched CPU remux with the device kernels' layout (docs/REMUX.md): the inputs of index_batch, its
-  // four outputs, and per segment a region of remux_out_bytes(cap, max_nal) bytes of `out` at out_off.
+  // four outputs, and per segment a region of remux_out_bytes(cap, max_nal) + audio_gap bytes of `out`
+  // at out_off.
   //   vsamples: int32[B, max_pes, ES_VSAMPLE_WORDS]; asamples: int32[B, max_aframes, ES_ASAMPLE_WORDS];
   //   rinfo: int64[B, ES_RINFO_WORDS]
   m.def("remux_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
                           int64_t max_pes, int64_t max_nal, Arr<int32_t> nal, Arr<int32_t> au, Arr<int32_t> aframes,
                           Arr<int64_t> sinfo, int64_t max_aframes, py::array vsamples, py::array asamples,
-                          py::array rinfo, py::array out, Arr<int64_t> out_off) {
+                          py::array rinfo, py::array out, Arr<int64_t> out_off, int64_t audio_gap) {
     const int64_t B = es_off.size();
     if (max_aframes <= 0) throw std::invalid_argument("remux_batch: max_aframes must be positive");
+    if (audio_gap < 0 || audio_gap % 16 || audio_gap >= (int64_t(1) << 30))
+      throw std::invalid_argument("remux_batch: audio_gap must be a non-negative multiple of 16");
     const es::RemuxTables tables{mut_ptr<int32_t>(vsamples, "vsamples"), mut_ptr<int32_t>(asamples, "asamples"),
                                  mut_ptr<int64_t>(rinfo, "rinfo")};
     uint8_t* op = mut_ptr<uint8_t>(out, "out");
@@ -446,15 +450,18 @@ PYBIND11_MODULE(_runtime, m) {
                        asamples.size() >= table_words(B, max_aframes, es::kAsampleWords) &&
                        rinfo.size() >= B * es::kRinfoWords;
     const auto region_ok = [&](int64_t b) {
-      if (oo[b] < 0 || oo[b] + es::remux_out_bytes(cap.data()[b], max_nal) > out.size())
+      if (oo[b] < 0 || oo[b] + es::remux_out_bytes(cap.data()[b], max_nal) + audio_gap > out.size())
         throw std::invalid_argument("remux_batch: output region out of bounds");
     };
     each_segment<const int32_t, const int64_t>("remux_batch", es, es_off, cap, info, pes, max_pes, max_nal, nal, au,
                                                aframes, sinfo, sized, region_ok,
                                                [&](const es::Segment& s, const auto& ix, int64_t b) {
-      es::remux_segment(s, ix, max_aframes, es::remux_tables_at(tables, s, max_aframes, b), op + oo[b]);
+      es::remux_segment(s, ix, max_aframes, es::remux_tables_at(tables, s, max_aframes, b), op + oo[b], audio_gap);
     });
-  });
+  }, py::arg("es"), py::arg("es_off"), py::arg("cap"), py::arg("info"), py::arg("pes"), py::arg("max_pes"),
+     py::arg("max_nal"), py::arg("nal"), py::arg("au"), py::arg("aframes"), py::arg("sinfo"), py::arg("max_aframes"),
+     py::arg("vsamples"), py::arg("asamples"), py::arg("rinfo"), py::arg("out"), py::arg("out_off"),
+     py::arg("audio_gap") = 0);
   m.def("remux_out_bytes", py::vectorize(&es::remux_out_bytes), py::arg("cap"), py::arg("max_nal"));
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
     return es::remux_scratch(nseg, max_nal, max_aframes).end;
@@ -473,6 +480,57 @@ PYBIND11_MODULE(_runtime, m) {
                               {"bad_timestamps", es::kBadTimestamps},
                               {"unsupported_video", es::kRemuxUnsupportedVideo}});
   name_dict(m, "ES_SAMPLE_FLAGS", {{"sync", es::kSampleSync}, {"non_sync", es::kSampleNonSync}});
+
+  // Batched CPU moof boxes with the device kernel's layout (docs/FRAGMENT.md): remux_batch's three
+  // tables, the index's sinfo, one fparams row per segment, and `out` as remux_batch left it, with
+  // `headroom` bytes in front of every region and `audio_gap` in front of every audio box.
+  //   fparams: int64[B, ES_FPARAM_WORDS]; finfo: int64[B, ES_FINFO_WORDS]
+  m.def("fragment_batch", [](Arr<int64_t> rinfo, Arr<int32_t> vsamples, Arr<int32_t> asamples, Arr<int64_t> sinfo,
+                             Arr<int64_t> fparams, int64_t max_pes, int64_t max_aframes, int64_t headroom,
+                             int64_t audio_gap, py::array out, py::array finfo) {
+    const int64_t B = fparams.size() / es::kFparamWords;
+    if (max_pes <= 0 || max_aframes <= 0 || max_pes > 0x7fffffff / 16 || max_aframes > 0x7fffffff / 16)
+      throw std::invalid_argument("fragment_batch: max_pes and max_aframes must be positive");
+    if (headroom < es::frag_headroom(max_pes))
+      throw std::invalid_argument("fragment_batch: headroom below frag_headroom(max_pes)");
+    if (audio_gap < es::frag_audio_gap(max_aframes) || audio_gap % 16)
+      throw std::invalid_argument("fragment_batch: audio_gap below frag_audio_gap(max_aframes) or no multiple of 16");
+    if (fparams.size() != B * es::kFparamWords || rinfo.size() < B * es::kRinfoWords ||
+        vsamples.size() < table_words(B, max_pes, es::kVsampleWords) ||
+        asamples.size() < table_words(B, max_aframes, es::kAsampleWords) || sinfo.size() < B * es::kSinfoWords ||
+        finfo.size() < B * es::kFinfoWords)
+      throw std::invalid_argument("fragment_batch: an argument is too small");
+    uint8_t* op = mut_ptr<uint8_t>(out, "out");
+    int64_t* fi = mut_ptr<int64_t>(finfo, "finfo");
+    const int64_t* fp = fparams.data();
+    for (int64_t b = 0; b < B; ++b) {
+      const int64_t oo = fp[b * es::kFparamWords + es::kFpOutOff], region = fp[b * es::kFparamWords + es::kFpRegion];
+      if (oo < headroom || region < audio_gap + 32 || oo > out.size() || region > out.size() - oo)
+        throw std::invalid_argument("fragment_batch: output region out of bounds");
+    }
+    for (int64_t b = 0; b < B; ++b) {
+      const int64_t* row = fp + b * es::kFparamWords;
+      es::fragment_segment(rinfo.data() + b * es::kRinfoWords, vsamples.data() + table_words(b, max_pes, es::kVsampleWords),
+                           asamples.data() + table_words(b, max_aframes, es::kAsampleWords),
+                           sinfo.data()[b * es::kSinfoWords + es::kAudioSampleRate], row, max_pes, max_aframes, audio_gap,
+                           op + row[es::kFpOutOff], fi + b * es::kFinfoWords);
+    }
+  });
+  m.def("moof_video_bytes", py::vectorize(&es::moof_video_bytes), py::arg("m"));
+  m.def("moof_audio_bytes", py::vectorize(&es::moof_audio_bytes), py::arg("n"));
+  m.def("frag_headroom", &es::frag_headroom, py::arg("max_pes"));
+  m.def("frag_audio_gap", &es::frag_audio_gap, py::arg("max_aframes"));
+  m.def("time_rel", &es::time_rel, py::arg("x"), py::arg("base"), py::arg("ref"));
+  m.def("audio_rescale", &es::audio_rescale, py::arg("t90k"), py::arg("rate"));
+  m.attr("ES_FINFO_WORDS") = es::kFinfoWords;
+  m.attr("ES_FPARAM_WORDS") = es::kFparamWords;
+  name_dict(m, "ES_FINFO", {{"status", es::kFStatus}, {"video_moof_bytes", es::kFVideoMoofBytes},
+                            {"audio_moof_bytes", es::kFAudioMoofBytes}, {"video_tfdt", es::kFVideoTfdt},
+                            {"audio_tfdt", es::kFAudioTfdt}, {"time_base", es::kFTimeBase},
+                            {"n_asamples", es::kFNumAsamples}, {"spare", es::kFSpare}});
+  name_dict(m, "ES_FSTATUS", {{"time_clamped", es::kTimeClamped}, {"no_rate", es::kNoRate}});
+  name_dict(m, "ES_FPARAM", {{"out_off", es::kFpOutOff}, {"region", es::kFpRegion}, {"sequence", es::kFpSequence},
+                             {"time_base", es::kFpTimeBase}, {"time_ref", es::kFpTimeRef}, {"anchor", es::kFpAnchor}});
 
   // Batched CPU codec configuration with the device kernel's layout (docs/INITSEGMENT.md): the inputs of
   // index_batch and its four outputs.

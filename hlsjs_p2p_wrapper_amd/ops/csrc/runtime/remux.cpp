@@ -20,7 +20,7 @@ void box_header(uint8_t* p, int64_t size) {
 }  // namespace
 
 void remux_segment(Segment s, const IndexTables<const int32_t, const int64_t>& ix, int64_t max_aframes,
-                   const RemuxTables& t, uint8_t* out) {
+                   const RemuxTables& t, uint8_t* out, int64_t audio_gap) {
   const int64_t max_pes = s.max_pes, max_nal = s.max_nal;
   const int32_t *nal = ix.nal, *au = ix.au, *aframes = ix.aframes;
   int32_t *vsamples = t.vsamples, *asamples = t.asamples;
@@ -37,7 +37,7 @@ void remux_segment(Segment s, const IndexTables<const int32_t, const int64_t>& i
   const int64_t m = video_rows(video, ix.sinfo[kNumAu], max_pes);  // the index's count, not the demux's
   const PesRows rows = pes_rows(s);
   const int64_t *vp = rows.video, *ap = rows.audio;
-  const int64_t region = remux_out_bytes(cap, max_nal);
+  const int64_t region = remux_out_bytes(cap, max_nal) + audio_gap;
   const int64_t v_limit = remux_video_limit(cap, max_nal);
 
   // ---- sample rows: timestamps and flags; sizes follow from the NAL rows
@@ -86,7 +86,7 @@ void remux_segment(Segment s, const IndexTables<const int32_t, const int64_t>& i
   box_header(out, 8 + P);
 
   // ---- audio payload: the counted ADTS frames without their headers
-  const int64_t A0 = (8 + P + 15) & ~int64_t(15);
+  const int64_t A0 = audio_box_offset(P, audio_gap);
   const int64_t room = region - (A0 + 8);
   const AudioSpan audio = audio_span(s);
   int64_t Q = 0, n_rec = 0, n_frames = 0;

@@ -21,10 +21,12 @@ namespace es {
 //   t.vsamples: int32[max_pes][kVsampleWords], -1 rows beyond
 //   t.asamples: int32[max_aframes][kAsampleWords], -1 rows beyond
 //   t.rinfo:    int64[kRinfoWords]
-//   out:        the segment's output region, remux_out_bytes(cap, max_nal) bytes writable; only
-//               the two box headers and the two payloads are written
+//   out:        the segment's output region, remux_out_bytes(cap, max_nal) + audio_gap bytes
+//               writable; only the two box headers and the two payloads are written
+//   audio_gap:  free bytes in front of the audio box (a non-negative multiple of 16): room for
+//               the audio moof of runtime/fragment.cpp
 void remux_segment(Segment s, const IndexTables<const int32_t, const int64_t>& ix, int64_t max_aframes,
-                   const RemuxTables& t, uint8_t* out);
+                   const RemuxTables& t, uint8_t* out, int64_t audio_gap = 0);
 
 }  // namespace es
 }  // namespace hlsp2p

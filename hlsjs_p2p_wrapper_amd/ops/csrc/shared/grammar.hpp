@@ -1,8 +1,8 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
 // runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp,
-// runtime/cenc.cpp) and by the gfx950
-// kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/codec_config.hip,
+// runtime/cenc.cpp, runtime/fragment.cpp) and by the gfx950
+// kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/fragment.hip, kernels/codec_config.hip,
 // kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
@@ -583,6 +583,113 @@ HLSP2P_RULE Delta32 delta32(int64_t x, int64_t y, bool non_negative) {
   const uint64_t d = uy - ux;
   if (non_negative || d > 0x80000000u) return {0, false};
   return {static_cast<int32_t>(-static_cast<int64_t>(d)), true};
+}
+
+// ---- moof boxes in front of the two mdat boxes (docs/FRAGMENT.md)
+// A 90 kHz stamp x relative to `base`; with a reference time ref >= 0 the result is moved by the
+// multiple of 2^33 that brings it within 2^32 of ref (hls.js's _PTSNormalize): the division
+// floors.  Two's complement throughout, so stamps no demuxer writes wrap and never trap.
+HLSP2P_RULE int64_t time_rel(int64_t x, int64_t base, int64_t ref) {
+  uint64_t rel = static_cast<uint64_t>(x) - static_cast<uint64_t>(base);
+  if (ref >= 0) {
+    const int64_t t = static_cast<int64_t>(static_cast<uint64_t>(ref) - rel + (uint64_t(1) << 32));
+    rel += static_cast<uint64_t>(t >> 33) << 33;  // an arithmetic shift: floor(t / 2^33)
+  }
+  return static_cast<int64_t>(rel);
+}
+// A 90 kHz time t >= 0 in units of the audio sample rate, rounded to nearest (exact while t * rate < 2^64 - 45000)
+HLSP2P_RULE int64_t audio_rescale(int64_t t90k, int64_t rate) {
+  return static_cast<int64_t>((static_cast<uint64_t>(t90k) * static_cast<uint64_t>(rate) + 45000u) / 90000u);
+}
+
+// What a segment's two tfdt boxes and its finfo row say about time: m clamped video samples with
+// first stamp vdts, first audio stamp apts (< 0: no audio PES), the index's sample rate.
+struct FragTimes { int64_t status, base, video_tfdt, audio_tfdt; };
+HLSP2P_RULE FragTimes frag_times(int64_t m, int64_t vdts, int64_t apts, int64_t rate, int64_t time_base, int64_t time_ref,
+                                 bool anchor) {
+  const bool has_v = m > 0, has_a = apts >= 0;
+  FragTimes f = {0, time_base, 0, 0};
+  if (anchor) {
+    const int64_t first = has_v && has_a ? (vdts < apts ? vdts : apts) : has_v ? vdts : apts;
+    f.base = has_v || has_a ? static_cast<int64_t>(static_cast<uint64_t>(first) - static_cast<uint64_t>(time_ref)) : 0;
+  }
+  if (has_v) {
+    const int64_t r = time_rel(vdts, f.base, time_ref);
+    if (r < 0) f.status |= kTimeClamped;
+    f.video_tfdt = r < 0 ? 0 : r;
+  }
+  if (has_a) {
+    const int64_t r = time_rel(apts, f.base, time_ref);
+    if (r < 0) f.status |= kTimeClamped;
+    if (rate <= 0) f.status |= kNoRate;
+    else f.audio_tfdt = audio_rescale(r < 0 ? 0 : r, rate);
+  }
+  return f;
+}
+
+// The audio box offset a fragment trusts: rinfo's, brought to a multiple of 16 that leaves the
+// gap in front of it and the box header behind it inside the region (>= audio_gap + 32 bytes)
+HLSP2P_RULE int64_t frag_audio_box(int64_t a0, int64_t region, int64_t audio_gap) {
+  return clamp(a0 & ~int64_t(15), audio_gap + 16, (region - 8) & ~int64_t(15));
+}
+
+// Dword i of the 22 in front of the video trun's entries, and of the 24 in front of the audio
+// trun's, as numbers: the boxes hold them big-endian.  m / n entries, mfhd sequence number seq.
+HLSP2P_RULE uint32_t moof_video_word(int i, uint32_t m, uint32_t seq, uint64_t tfdt) {
+  const uint32_t size = kMoofVideoHead + kMoofVideoEntry * m;
+  switch (i) {
+    case 0: return size;
+    case 1: return 0x6d6f6f66u;  // 'moof'
+    case 2: return 16;
+    case 3: return 0x6d666864u;  // 'mfhd'
+    case 5: return seq;
+    case 6: return size - 24;
+    case 7: return 0x74726166u;  // 'traf'
+    case 8: return 16;
+    case 9: return 0x74666864u;  // 'tfhd'
+    case 10: return 0x00020000u;  // default-base-is-moof
+    case 11: return 1;            // track
+    case 12: return 20;
+    case 13: return 0x74666474u;  // 'tfdt'
+    case 14: return 0x01000000u;  // version 1
+    case 15: return static_cast<uint32_t>(tfdt >> 32);
+    case 16: return static_cast<uint32_t>(tfdt);
+    case 17: return size - 68;
+    case 18: return 0x7472756eu;  // 'trun'
+    case 19: return 0x01000f01u;  // version 1: data offset, duration, size, flags, signed cts
+    case 20: return m;
+    case 21: return size + 8;     // data_offset: behind the header of the mdat that follows
+    default: return 0;
+  }
+}
+HLSP2P_RULE uint32_t moof_audio_word(int i, uint32_t n, uint32_t seq, uint64_t tfdt) {
+  const uint32_t size = kMoofAudioHead + kMoofAudioEntry * n;
+  switch (i) {
+    case 0: return size;
+    case 1: return 0x6d6f6f66u;
+    case 2: return 16;
+    case 3: return 0x6d666864u;
+    case 5: return seq;
+    case 6: return size - 24;
+    case 7: return 0x74726166u;
+    case 8: return 24;
+    case 9: return 0x74666864u;
+    case 10: return 0x00020028u;  // default-base-is-moof, default duration, default flags
+    case 11: return 2;            // track
+    case 12: return 1024;         // samples of an AAC frame
+    case 13: return 0x02000000u;  // every frame is a sync sample
+    case 14: return 20;
+    case 15: return 0x74666474u;
+    case 16: return 0x01000000u;
+    case 17: return static_cast<uint32_t>(tfdt >> 32);
+    case 18: return static_cast<uint32_t>(tfdt);
+    case 19: return size - 76;
+    case 20: return 0x7472756eu;
+    case 21: return 0x00000201u;  // version 0: data offset, size
+    case 22: return n;
+    case 23: return size + 8;
+    default: return 0;
+  }
 }
 
 // ---- CEA-608/708 caption data in SEI NAL units (docs/CAPTIONS.md)

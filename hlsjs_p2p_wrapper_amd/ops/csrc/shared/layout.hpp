@@ -129,6 +129,9 @@ enum RemuxStatus : int64_t { kTruncated = 1, kAframeOverflow = 2, kBadTimestamps
 constexpr int64_t remux_out_bytes(int64_t cap, int64_t max_nal) { return cap + max_nal + 32; }
 // the video payload may take this much of the region; what is left holds the padding and the audio header
 constexpr int64_t remux_video_limit(int64_t cap, int64_t max_nal) { return cap + max_nal; }
+// A0, where the audio box starts behind a video payload of P bytes; audio_gap (a multiple of 16,
+// default 0) bytes are left free in front of it and make the region that much longer
+constexpr int64_t audio_box_offset(int64_t P, int64_t audio_gap) { return (8 + P + audio_gap + 15) & ~int64_t(15); }
 
 // scratch (int32), element offsets inside one segment's slice of `stride` elements:
 // [hdr: 8 | vstart: max_nal + 1 | vsrc: max_nal | astart: max_aframes + 1 | asrc: max_aframes]
@@ -139,6 +142,45 @@ constexpr RemuxScratch remux_scratch(int64_t nseg, int64_t max_nal, int64_t max_
   return {8, 9 + max_nal, 9 + 2 * max_nal, 10 + 2 * max_nal + max_aframes, 10 + 2 * (max_nal + max_aframes),
           nseg * (10 + 2 * (max_nal + max_aframes))};
 }
+
+// ---- moof boxes in front of the two mdat boxes (docs/FRAGMENT.md)
+// moof{ mfhd, traf{ tfhd, tfdt (v1), trun } } as player/fmp4.py packs it: the video trun has a
+// 16-byte entry per sample, the audio tfhd carries two defaults and its trun a 4-byte entry per frame
+constexpr int kMoofVideoHead = 88, kMoofVideoEntry = 16;
+constexpr int kMoofAudioHead = 96, kMoofAudioEntry = 4;
+constexpr int64_t moof_video_bytes(int64_t m) { return kMoofVideoHead + kMoofVideoEntry * m; }
+constexpr int64_t moof_audio_bytes(int64_t n) { return kMoofAudioHead + kMoofAudioEntry * n; }
+// room in front of a segment's region for the largest video moof: the moof ends where the region starts
+constexpr int64_t frag_headroom(int64_t max_pes) {
+  return (moof_video_bytes(max_pes) + kOutAlign - 1) / kOutAlign * kOutAlign;
+}
+// room between the video payload and the audio box for the largest audio moof: the moof ends at A0
+constexpr int64_t frag_audio_gap(int64_t max_aframes) { return (moof_audio_bytes(max_aframes) + 15) / 16 * 16; }
+
+// finfo[] row (int64), identical on host and device
+constexpr int kFinfoWords = 8;
+enum Finfo : int {
+  kFStatus = 0,
+  kFVideoMoofBytes = 1, kFAudioMoofBytes = 2,
+  kFVideoTfdt = 3,  // 90 kHz
+  kFAudioTfdt = 4,  // in units of the audio sample rate
+  kFTimeBase = 5,   // the base that was used, also when the segment anchored it
+  kFNumAsamples = 6,
+  kFSpare = 7,      // 0
+};
+enum FragStatus : int64_t { kTimeClamped = 1, kNoRate = 2 };
+
+// fparams[] row (int64): what the host says about a segment
+constexpr int kFparamWords = 8;
+enum Fparam : int {
+  kFpOutOff = 0,   // where the segment's video mdat starts in out
+  kFpRegion = 1,   // bytes of the region from there on: es::remux_out_bytes(cap, max_nal) + audio_gap
+  kFpSequence = 2, // mfhd sequence_number, used modulo 2^32
+  kFpTimeBase = 3,
+  kFpTimeRef = 4,  // -1: none
+  kFpAnchor = 5,   // != 0: the segment sets the base from its own first stamp and kFpTimeRef
+  kFpSpare0 = 6, kFpSpare1 = 7,
+};
 
 // ---- codec configuration for the fMP4 init segment (docs/INITSEGMENT.md)
 constexpr int kCinfoWords = 19;

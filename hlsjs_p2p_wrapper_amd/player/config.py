@@ -99,6 +99,12 @@ def _default_config() -> Dict[str, Any]:
         # "startDTS" / "endDTS" and the sample count in "nb"; FRAG_PARSING_INIT_SEGMENT carries each
         # track's init segment, codec and container (docs/INITSEGMENT.md)
         "remuxFmp4": False,
+        # write each track's moof on the transmux device too, directly in front of its mdat
+        # (docs/FRAGMENT.md; implies remuxFmp4): FRAG_PARSING_DATA carries the moof as a device view
+        # in "data1", adjacent to the mdat view in "data2", and "fragment", one view over both; the
+        # tfdt, "startDTS" and "endDTS" are on the playlist's timeline (one initPTS per discontinuity
+        # counter, 33-bit rollovers unwrapped)
+        "fmp4Fragments": False,
         # extract the CEA-608/708 caption data of every fragment's SEI NAL units on the transmux
         # device (docs/CAPTIONS.md; implies the index) and emit it on FRAG_PARSING_USERDATA; hls.js's
         # name, off by default here like every device feature

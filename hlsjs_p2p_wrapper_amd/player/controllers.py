@@ -468,6 +468,9 @@ class StreamController:
         self._eos = False
         self._init_levels: set = set()
         self._init_announced: Any = None  # remuxFmp4: the (sps, pps, AudioSpecificConfig) last announced
+        # fmp4Fragments: the 90 kHz time base (hls.js's initPTS) per discontinuity counter, as the first
+        # fragment of that counter to come back anchored it (docs/FRAGMENT.md)
+        self._init_pts: Dict[int, int] = {}
         # fragmented MP4 (#EXT-X-MAP, docs/FMP4DEMUX.md): the parsed init segment per (URL, range), the
         # fragments waiting for one that is loading, its loader, and the ones already announced
         self._mp4_inits: Dict[Any, Any] = {}
@@ -791,10 +794,22 @@ class StreamController:
         ticket = getattr(payload, "swarm_verify", None)
         if method == "SAMPLE-AES-CTR":  # no such thing on MPEG-TS: the fragment goes through as it is
             sample_key = sample_iv = None
-        pipeline_for(dev, self.loop).submit(
-            TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
-                        bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
-                        sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions"))))
+        job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
+                          bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
+                          sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions")))
+        if self.hls.config.get("fmp4Fragments"):
+            # the moof boxes on the device, on the playlist's timeline: a fragment whose discontinuity
+            # counter has no initPTS yet anchors its first stamp to its own playlist start (so do all
+            # that are in flight before the first one lands, as hls.js does after a seek); later ones
+            # pass the stored base, and every one its playlist start as the reference the 33-bit
+            # stamps are unwrapped against
+            base = self._init_pts.get(frag.cc)
+            job.fragment = job.remux = job.index = True
+            job.sequence_number = frag.sn
+            job.time_ref = int(round(frag.start * 90000))
+            job.anchor = base is None
+            job.time_base = 0 if base is None else base
+        pipeline_for(dev, self.loop).submit(job)
 
     # ------------------------------------------------------------------ fragmented MP4 (docs/FMP4DEMUX.md)
     def _load_init_segment(self, init_segment: Any, waiter: Any) -> None:
@@ -983,7 +998,12 @@ class StreamController:
         info = r["info"]
         # remuxFmp4: the fragment as fMP4 (ops/remux.py), with the codec configuration its init
         # segments are built from (ops/codecconfig.py, ops/hevcconfig.py for HEVC, docs/INITSEGMENT.md)
-        fmp4 = r.get("fmp4") if hls.config.get("remuxFmp4") else None
+        fragments = bool(hls.config.get("fmp4Fragments"))
+        fmp4 = r.get("fmp4") if fragments or hls.config.get("remuxFmp4") else None
+        # fmp4Fragments: a result without the boxes (a fleet player's) leaves the events as under remuxFmp4
+        fragments = fragments and fmp4 is not None and "time_base" in fmp4
+        if fragments:
+            self._init_pts.setdefault(frag.cc, fmp4["time_base"])  # the first one to land wins
         announce = frag.level not in self._init_levels
         sig = None
         if fmp4 is not None:
@@ -1040,11 +1060,17 @@ class StreamController:
             if fmp4 is not None:
                 for ev, track in ((vdata, fmp4["video"]), (adata, fmp4["audio"])):
                     scale = track["timescale"] or 1
-                    ev["data1"] = track["moof"](frag.sn)
                     ev["data2"] = track["mdat"]
                     ev["nb"] = track["nb"]
-                    ev["startDTS"] = track["base"] / scale
-                    ev["endDTS"] = (track["base"] + track["duration"]) / scale
+                    if fragments:  # the moof lies in front of the mdat on the device: two adjacent views of one range
+                        ev["data1"] = track["moof_view"]
+                        ev["fragment"] = track["fragment"]
+                        base = track["tfdt"]
+                    else:
+                        ev["data1"] = track["moof"](frag.sn)
+                        base = track["base"]
+                    ev["startDTS"] = base / scale
+                    ev["endDTS"] = (base + track["duration"]) / scale
             hls.trigger(Events.FRAG_PARSING_DATA, vdata)
             hls.trigger(Events.FRAG_PARSING_DATA, adata)
         if listening(Events.FRAG_PARSED):

@@ -55,12 +55,25 @@ class TransmuxJob:
     own), and the result's ``data`` and views are then those of the decrypted copy."""
 
     __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
-                 "captions", "mp4", "scheme")
+                 "captions", "mp4", "scheme", "fragment", "sequence_number", "time_base", "time_ref", "anchor")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
                  index: bool = False, remux: bool = False, sample_key: Optional[bytes] = None,
-                 sample_iv: Optional[bytes] = None, captions: bool = False, mp4: Any = None) -> None:
+                 sample_iv: Optional[bytes] = None, captions: bool = False, mp4: Any = None,
+                 fragment: bool = False, sequence_number: int = 0, time_base: int = 0, time_ref: int = -1,
+                 anchor: bool = False) -> None:
+        # ``fragment`` (implies ``remux``): the batch also writes both moof boxes of this fragment in
+        # front of its mdat boxes (ops/fragment.py, docs/FRAGMENT.md) and the tracks of its ``fmp4``
+        # gain ``fragment``, ``moof_view`` and ``tfdt``.  ``sequence_number`` goes into the mfhd;
+        # the tfdt values are relative to ``time_base`` and unwrapped against ``time_ref`` (90 kHz,
+        # -1: none), or with ``anchor`` the fragment's first stamp lands on ``time_ref`` and the base
+        # that follows comes back as ``fmp4["time_base"]``
+        if fragment and anchor and time_ref < 0:
+            raise ValueError("TransmuxJob: an anchored fragment needs a time_ref >= 0")
+        remux = remux or fragment
+        self.fragment = fragment
+        self.sequence_number, self.time_base, self.time_ref, self.anchor = sequence_number, time_base, time_ref, anchor
         self.payload = payload
         self.key = key
         self.iv = iv
@@ -97,7 +110,7 @@ class TransmuxJob:
                 raise ValueError("TransmuxJob: a fragmented-MP4 fragment is AES-128 or SAMPLE-AES, not both")
         self.mp4 = mp4
         if mp4 is not None:  # the fragment already is fMP4: no remux, and none that implies the index
-            self.remux = False
+            self.remux = self.fragment = False
             self.index = bool(index or captions)
 
     def __repr__(self) -> str:
@@ -147,16 +160,19 @@ class _Columns:
     have, ``-1`` for no check; ``index`` (``None``: nobody) marks the fragments whose samples
     are to be indexed, ``remux`` those to be remuxed as well, ``sample`` (a subset of ``index``)
     those whose ES is SAMPLE-AES protected, with ``sample_keys[i]`` / ``sample_ivs[i]``, ``captions``
-    (a subset of ``index``) those whose caption data is to be extracted."""
+    (a subset of ``index``) those whose caption data is to be extracted, ``fragment`` (a subset of
+    ``remux``) those whose moof boxes are to be written, with ``frag_params[i]`` = (sequence number,
+    time base, time reference, anchor)."""
 
     __slots__ = ("src", "offs", "nb", "enc", "iv", "drk", "keys", "expect", "index", "remux", "sample", "sample_keys",
-                 "sample_ivs", "captions")
+                 "sample_ivs", "captions", "fragment", "frag_params")
 
     def __init__(self, src: torch.Tensor, offs: np.ndarray, nb: np.ndarray, enc: np.ndarray, iv: np.ndarray,
                  drk: Optional[np.ndarray] = None, keys: Any = None, expect: Optional[np.ndarray] = None,
                  index: Optional[np.ndarray] = None, remux: Optional[np.ndarray] = None,
                  sample: Optional[np.ndarray] = None, sample_keys: Any = None, sample_ivs: Any = None,
-                 captions: Optional[np.ndarray] = None) -> None:
+                 captions: Optional[np.ndarray] = None, fragment: Optional[np.ndarray] = None,
+                 frag_params: Optional[np.ndarray] = None) -> None:
         self.src = src      # uint8 tensor on the pipeline's device
         self.offs = offs    # int64[n]
         self.nb = nb        # int64[n]
@@ -171,6 +187,8 @@ class _Columns:
         self.sample_keys = sample_keys  # n raw 16-byte keys (None where sample is not set)
         self.sample_ivs = sample_ivs
         self.captions = captions  # bool[n], a subset of index
+        self.fragment = fragment  # bool[n], a subset of remux
+        self.frag_params = frag_params  # int64[n, 4]; rows that did not ask hold (0, 0, -1, 0)
 
 
 class MediaPipeline:
@@ -330,6 +348,12 @@ class MediaPipeline:
                         sample=_mask(n, [i for i, j in enumerate(jobs) if j.sample_key is not None]),
                         sample_keys=[j.sample_key for j in jobs], sample_ivs=[j.sample_iv for j in jobs],
                         captions=_mask(n, [i for i, j in enumerate(jobs) if j.captions]))
+        asked = [i for i, j in enumerate(jobs) if j.fragment]
+        if asked:
+            cols.fragment = _mask(n, asked)
+            cols.frag_params = np.tile(np.array([0, 0, -1, 0], dtype=np.int64), (n, 1))
+            cols.frag_params[asked] = [(jobs[i].sequence_number, jobs[i].time_base, jobs[i].time_ref,
+                                        int(bool(jobs[i].anchor))) for i in asked]
         self.timer.add("stage", time.perf_counter() - t0)
         return cols
 
@@ -449,11 +473,27 @@ class MediaPipeline:
             if c.remux is not None and c.remux[g.rows].any():
                 from ..ops import remux as _rmx
 
-                out_offs, size = _rmx.layout_out(c.nb[g.rows], ix.nal.shape[1])
+                # a group in which any row asked for its moof boxes leaves room for them in every
+                # region (so a row that did not ask sees a larger ``audio_box_offset``, nothing else)
+                # and gets one ``fragment_batch`` call behind the remux, its ``finfo`` rows on the
+                # same way to the host (docs/FRAGMENT.md)
+                fragment = c.fragment is not None and bool(c.fragment[g.rows].any())
+                headroom = gap = 0
+                if fragment:
+                    from ..ops import fragment as _frg
+
+                    headroom = _frg.frag_headroom(g.res.pes.shape[2])
+                    gap = _frg.frag_audio_gap(_rmx.DEFAULT_MAX_AFRAMES)
+                out_offs, size = _rmx.layout_out(c.nb[g.rows], ix.nal.shape[1], headroom=headroom, audio_gap=gap)
                 g.rx = rx = _rmx.remux_batch(g.res, ix, c.nb[g.rows],
                                              torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
-                                             out_offs)
+                                             out_offs, audio_gap=gap, headroom=headroom)
                 g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
+                if fragment:
+                    fp = c.frag_params[g.rows]
+                    g.fr = fr = _frg.fragment_batch(rx, ix, fp[:, 0], time_base=fp[:, 1], time_ref=fp[:, 2],
+                                                    anchor=fp[:, 3] != 0)
+                    g.finfo = _to_host(fr.finfo)
                 # ... and what the init segments are built from: one ``config_batch`` call behind the
                 # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
                 from ..ops import codecconfig as _cfg
@@ -676,7 +716,7 @@ class MediaPipeline:
                     if b.jobs[i].index:
                         results[i]["samples"] = Samples(srows[k], g.ix, k)
                     if g.rx is not None and b.jobs[i].remux:  # ... and those that asked for the remux
-                        results[i]["fmp4"] = Fmp4(g, k, srows[k])
+                        results[i]["fmp4"] = Fmp4(g, k, srows[k], g.fr is not None and b.jobs[i].fragment)
                     if g.sa is not None and b.jobs[i].sample_key is not None:  # ... and for the SAMPLE-AES decrypt
                         from types import MappingProxyType
 
@@ -872,7 +912,10 @@ class Fmp4Track(_View):
     on first access, ``None`` when the configuration cannot describe the track), ``codec`` (the RFC
     6381 string, ``None`` like ``init``), ``container`` and ``width`` / ``height`` (video) or
     ``channelCount`` / ``samplerate`` (audio).  The video track of an HEVC fragment (``config`` says
-    ``unsupported_video`` and ``hevc`` has no disqualifying bit) takes the four from ``hevc``."""
+    ``unsupported_video`` and ``hevc`` has no disqualifying bit) takes the four from ``hevc``.
+    For a job that asked for its moof boxes (``TransmuxJob.fragment``) also ``moof_view`` (a device
+    view of the track's ``moof``, which ends where ``mdat`` starts), ``fragment`` (one device view
+    over both) and ``tfdt`` (the box's decode time, in the track's units)."""
 
     __slots__ = ("_f", "_video", "_moofs", "_init")
     _KEYS = ("mdat", "samples", "nb", "base", "duration", "timescale", "moof", "init", "codec", "container")
@@ -958,13 +1001,23 @@ class Fmp4Track(_View):
             return _fmp4.AAC_FRAME_SAMPLES * self["nb"]
         if name == "moof":
             return self.moof
+        if name in ("fragment", "moof_view", "tfdt") and f._fragment:
+            if name == "tfdt":
+                return f._finfo("video_tfdt" if self._video else "audio_tfdt")
+            moof = f._finfo("video_moof_bytes" if self._video else "audio_moof_bytes")
+            end = int(rx.out_offs[f._k]) + (0 if self._video else f._rinfo("audio_box_offset"))
+            if name == "moof_view":
+                return rx.out.narrow(0, end - moof, moof)
+            return rx.out.narrow(0, end - moof, moof + 8 + f._rinfo("video_payload_bytes" if self._video
+                                                                     else "audio_payload_bytes"))
         if name in ("init", "codec", "container") or name in (("width", "height") if self._video
                                                               else ("channelCount", "samplerate")):
             return self._config_key(name)
         raise KeyError(name)
 
     def keys(self):
-        return list(self._KEYS) + (["width", "height"] if self._video else ["channelCount", "samplerate"])
+        return list(self._KEYS) + (["width", "height"] if self._video else ["channelCount", "samplerate"]) \
+            + (["fragment", "moof_view", "tfdt"] if self._f._fragment else [])
 
     def __repr__(self) -> str:
         return f"Fmp4Track({'video' if self._video else 'audio'}, nb={self['nb']})"
@@ -975,15 +1028,17 @@ class Fmp4(_View):
     (:class:`Fmp4Track`), the ``rinfo`` fields by name (:data:`ops.remux.RINFO`) and ``config``: the
     fragment's codec configuration, a read-only mapping of the ``cinfo`` fields by name
     (:data:`ops.codecconfig.CINFO`) plus ``sps`` / ``pps`` as bytes, and ``hevc``: the same of the
-    ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``."""
+    ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``.  For a job that
+    asked for its moof boxes also ``time_base``: the 90 kHz base its ``tfdt`` values are relative to."""
 
-    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc")
+    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc", "_fragment")
 
-    def __init__(self, group, k: int, sinfo_row) -> None:
+    def __init__(self, group, k: int, sinfo_row, fragment: bool = False) -> None:
         from ..ops.esindex import SINFO
 
         self._g = group  # the fragment's _Group: its Remuxed and the three host tables
         self._k = k
+        self._fragment = fragment  # the job asked for its moof boxes: ``time_base``, and three more keys per track
         self._rate = sinfo_row[SINFO["audio_sample_rate"]]
         self._tracks: Dict[str, Fmp4Track] = {}
         self._config: Any = None
@@ -993,6 +1048,11 @@ class Fmp4(_View):
         from ..ops.remux import RINFO
 
         return int(_np(self._g.rinfo)[self._k, RINFO[name]])
+
+    def _finfo(self, name: str) -> int:
+        from ..ops.fragment import FINFO
+
+        return int(_np(self._g.finfo)[self._k, FINFO[name]])
 
     def __getitem__(self, name: str):
         from ..ops.remux import RINFO
@@ -1004,6 +1064,8 @@ class Fmp4(_View):
             return t
         if name in RINFO:
             return self._rinfo(name)
+        if name == "time_base" and self._fragment:
+            return self._finfo("time_base")
         if name == "config":
             if self._config is None:
                 from types import MappingProxyType
@@ -1027,7 +1089,7 @@ class Fmp4(_View):
     def keys(self):
         from ..ops.remux import RINFO
 
-        return ["video", "audio", *RINFO, "config", "hevc"]
+        return ["video", "audio", *RINFO, "config", "hevc"] + (["time_base"] if self._fragment else [])
 
     def __repr__(self) -> str:
         return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config', 'hevc')} })"
@@ -1119,6 +1181,8 @@ class _Group:
     rinfo: Any = None  # ... its three tables on the host
     vsamples: Any = None
     asamples: Any = None
+    fr: Any = None  # Fragments, when a job of the group asked for its moof boxes, with ...
+    finfo: Any = None  # ... its finfo rows on the host
     cfg: Any = None  # CodecConfig, behind the remux, with ...
     cinfo: Any = None  # ... its two tensors on the host
     ps: Any = None

@@ -1,6 +1,7 @@
 """Per-kernel microbenchmark on one bench round's batch: 64 x ~3 MB AES-128 TS segments
 (the 1080p 6 Mb/s config).  Times AES-CBC decrypt, TS demux (psi+scan+gather), the sample
-index over the demuxed ES, the remux to fMP4 samples, the codec configuration for the init segments
+index over the demuxed ES, the remux to fMP4 samples, the moof boxes in front of them (next to the
+host packing they replace), the codec configuration for the init segments
 (H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
 on a video ES the tool writes itself, the fragmented-MP4 demux on segments the tool writes itself (one
 ``moof`` and thirty), the cbcs decrypt of such segments protected by the tool (the demux row's segment and
@@ -13,14 +14,16 @@ Checks results against the host oracles once.
 import argparse
 import json
 import struct
+import time
 
 import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, hevcconfig, mp4demux,
-                                       remux, sampleaes, segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, fragment, hevcconfig,
+                                       mp4demux, remux, sampleaes, segment, tsdemux)
 from hlsjs_p2p_wrapper_amd.ops._native import runtime
+from hlsjs_p2p_wrapper_amd.player import fmp4
 
 
 def timed(fn, iters):
@@ -363,6 +366,40 @@ def main():
     a0 = int(hr.rinfo[0, remux.RINFO["audio_box_offset"]])
     for lo, hi in ((0, vend), (a0, used)):  # both boxes; the bytes between and behind them belong to nobody
         assert torch.equal(boxes[int(oo[0]) + lo:int(oo[0]) + hi].cpu(), hr.out[lo:hi]), "remux mismatch"
+    # the moof boxes of the remuxed batch, written in front of its mdat boxes (one workgroup per
+    # segment), next to the host work the call replaces: fmp4.video_moof + fmp4.audio_moof per segment
+    # over the same rows, already on the host (the pipeline has them in pinned memory by then)
+    head, gap = fragment.frag_headroom(r.pes.shape[2]), fragment.frag_audio_gap(remux.DEFAULT_MAX_AFRAMES)
+    fo, fsize = remux.layout_out(caps, ix.nal.shape[1], headroom=head, audio_gap=gap)
+    fboxes = torch.empty(fsize, dtype=torch.uint8, device=dev)
+    frx = remux.remux_batch(r, ix, caps, fboxes, fo, audio_gap=gap, headroom=head)
+    res["remux_gap_us"] = timed(lambda: remux.remux_batch(r, ix, caps, fboxes, fo, audio_gap=gap, headroom=head),
+                                args.iters)
+    seqs = np.arange(args.segs, dtype=np.int64)
+    fr = fragment.fragment_batch(frx, ix, seqs)
+    res["fragment_us"] = timed(lambda: fragment.fragment_batch(frx, ix, seqs), args.iters)
+    rinfo, vs, asamp = (t.cpu().numpy() for t in (frx.rinfo, frx.vsamples, frx.asamples))
+    rates = ix.sinfo.cpu().numpy()[:, esindex.SINFO["audio_sample_rate"]]
+    R = remux.RINFO
+
+    def host_moofs():
+        out = []
+        for i in range(args.segs):
+            rows = asamp[i]
+            out.append((fmp4.video_moof(int(seqs[i]), int(rinfo[i, R["video_base_dts"]]),
+                                        vs[i, :rinfo[i, R["n_vsamples"]]]),
+                        fmp4.audio_moof(int(seqs[i]), int(rinfo[i, R["audio_base_pts"]]), int(rates[i]),
+                                        rows[rows[:, 0] >= 0])))
+        return out
+
+    t0 = time.perf_counter()
+    for _ in range(args.iters):
+        moofs = host_moofs()
+    res["host_moof_us"] = round((time.perf_counter() - t0) / args.iters * 1e6, 1)
+    for i in (0, args.segs - 1):
+        s = fr.segment(i)
+        assert s["video"][:s["video_moof_bytes"]] == moofs[i][0], "fragment mismatch (video)"
+        assert s["audio"][:s["audio_moof_bytes"]] == moofs[i][1], "fragment mismatch (audio)"
     # the codec configuration of the indexed ES for the init segments (one workgroup per segment)
     cfg = codecconfig.config_batch(r, ix, caps)
     res["codecconfig_us"] = timed(lambda: codecconfig.config_batch(r, ix, caps), args.iters)
@@ -450,6 +487,7 @@ def main():
     res["copy_us"] = timed(lambda: segment.copy_segments(src, cp, offs, offs, lens), args.iters)
     assert torch.equal(cp[offs[5]:offs[5] + lens[5]], src[offs[5]:offs[5] + lens[5]]), "copy mismatch"
     res["torch_copy_us"] = timed(lambda: cp.copy_(src), args.iters)
+    res["remux_gap_us"], res["fragment_us"] = round(res["remux_gap_us"], 1), round(res["fragment_us"], 1)
     for k in ("aes", "demux", "esindex", "remux", "codecconfig", "hevcconfig", "hevcconfig_search", "sampleaes", "crc",
               "copy", "torch_copy"):
         res[f"{k}_GBps"] = round(total / (res[f"{k}_us"] * 1e-6) / 1e9, 1)
