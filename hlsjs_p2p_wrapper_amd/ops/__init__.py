@@ -1,7 +1,9 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``, ``fragment``,
-``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``, ``cenc``): import the
+``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``, ``cenc``, ``packedaudio``):
+import the
 submodule you need.  The entry points of the sample index, of the remux, of the two codec configurations, of the
-SAMPLE-AES decrypt, of the caption extraction, of the fragmented-MP4 demux and of the cbcs and cenc decrypts are
+SAMPLE-AES decrypt, of the caption extraction, of the fragmented-MP4 demux, of the cbcs and cenc decrypts and of
+the packed-audio demux are
 also reachable from the package
 (``ops.index_batch``,
 ``ops.EsIndex``, ``ops.remux_batch``,
@@ -9,7 +11,8 @@ also reachable from the package
 ``ops.config_batch``, ``ops.CodecConfig``, ``ops.hevc_config_batch``,
 ``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``, ``ops.caption_batch``,
 ``ops.Captions``, ``ops.mp4_demux_batch``, ``ops.Mp4Demux``, ``ops.Mp4Track``, ``ops.cbcs_decrypt_batch``,
-``ops.Cbcs``, ``ops.Mp4Protection``, ``ops.cenc_decrypt_batch``, ``ops.Cenc``), resolved on first use."""
+``ops.Cbcs``, ``ops.Mp4Protection``, ``ops.cenc_decrypt_batch``, ``ops.Cenc``,
+``ops.packed_audio_batch``, ``ops.PackedAudio``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
@@ -21,8 +24,9 @@ _CAPTIONS = ("caption_batch", "Captions")
 _MP4DEMUX = ("mp4_demux_batch", "Mp4Demux", "Mp4Track")
 _CBCS = ("cbcs_decrypt_batch", "Cbcs", "Mp4Protection")
 _CENC = ("cenc_decrypt_batch", "Cenc")
+_PACKEDAUDIO = ("packed_audio_batch", "PackedAudio")
 __all__ = list(_ESINDEX + _REMUX + _FRAGMENT + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS
-               + _CENC)
+               + _CENC + _PACKEDAUDIO)
 
 
 def __getattr__(name):
@@ -66,4 +70,8 @@ def __getattr__(name):
         from . import cenc
 
         return getattr(cenc, name)
+    if name in _PACKEDAUDIO:
+        from . import packedaudio
+
+        return getattr(packedaudio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

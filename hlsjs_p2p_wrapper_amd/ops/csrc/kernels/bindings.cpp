@@ -342,6 +342,35 @@ void mp4_demux(Tensor buf, Tensor off, Tensor len, Tensor cap, Tensor tracks, in
   hip_ok(D::launch_mp4_demux(a), "mp4_demux launch");
 }
 
+// Demux of packed-audio segments (packed_audio.hip): segment i is buf[off[i], off[i] + clamp(len[i], 0,
+// cap[i])) (the Python wrapper has checked off + cap against buf); seven output tables, info / pes in
+// ts_demux's layout and nal (one row) / au / aframes / sinfo in es_index's.  staged = false walks the
+// frame chain in global memory: the variant tools/kernel_bench.py measures the LDS walk against.
+void packed_audio(Tensor buf, Tensor off, Tensor len, Tensor cap, int64_t max_pes, Tensor info, Tensor pes, Tensor nal,
+                  Tensor au, Tensor aframes, Tensor sinfo, Tensor painfo, bool staged) {
+  const int64_t B = off.numel();
+  TORCH_CHECK(es_::packed_max_pes_ok(max_pes), "packed_audio: max_pes must be 1 to ", es_::kPackedMaxPesLimit);
+  const D::PackedAudioArgs a{
+      .buf = check<uint8_t>(buf, "buf"), .buf_numel = buf.numel(),
+      .off = check<int64_t>(off, "off"),
+      .len = check<int64_t>(len, "len", B),
+      .cap = check<int64_t>(cap, "cap", B),
+      .nseg = static_cast<int>(B),
+      .max_pes = max_pes,
+      .t = {check<int64_t>(info, "info", B * ts::kInfoWords),
+            check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+            {check<int32_t>(nal, "nal", hlsp2p::table_words(B, es_::kPackedNalRows, es_::kNalWords)),
+             check<int32_t>(au, "au", hlsp2p::table_words(B, max_pes, es_::kAuWords)),
+             check<int32_t>(aframes, "aframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+             check<int64_t>(sinfo, "sinfo", B * es_::kSinfoWords)},
+            check<int64_t>(painfo, "painfo", B * es_::kPainfoWords)},
+      .staged = staged,
+      .stream = stream()};
+  same_device(buf, {off, len, cap, info, pes, nal, au, aframes, sinfo, painfo});
+  aligned16({{buf, "buf"}, {nal, "nal"}, {au, "au"}, {aframes, "aframes"}});
+  hip_ok(D::launch_packed_audio(a), "packed_audio launch");
+}
+
 // cbcs decryption of a demuxed fMP4 batch into a copy (cbcs.hip): src and the five demux tables are
 // only read; dst already holds a copy of every enabled segment at dst_off[i] (the Python wrapper
 // has checked both offset sets against their tensors); per segment two protection rows, two
@@ -562,6 +591,9 @@ TORCH_LIBRARY(hlsp2p, m) {
         "int max_moof, int max_run, int max_emsg, Tensor(a!) minfo, Tensor(b!) msamples, Tensor(c!) runs, "
         "Tensor(d!) emsg, Tensor(e!) info, Tensor(f!) pes, Tensor(g!) nal, Tensor(h!) au, Tensor(i!) aframes, "
         "Tensor(j!) sinfo) -> ()");
+  m.def("packed_audio(Tensor buf, Tensor off, Tensor len, Tensor cap, int max_pes, Tensor(a!) info, Tensor(b!) pes, "
+        "Tensor(c!) nal, Tensor(d!) au, Tensor(e!) aframes, Tensor(f!) sinfo, Tensor(g!) painfo, "
+        "bool staged=True) -> ()");
   m.def("cbcs_decrypt(Tensor src, Tensor src_off, Tensor cap, Tensor(a!) dst, Tensor dst_off, Tensor info, Tensor pes, "
         "Tensor minfo, Tensor msamples, Tensor runs, int max_pes, int max_run, Tensor prot, Tensor const_iv, Tensor iv, "
         "Tensor round_keys, Tensor enable, Tensor td, Tensor isb, int max_range, int max_blocks, Tensor(b!) scratch, "
@@ -586,6 +618,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
   m.impl("cc_extract", &cc_extract);
   m.impl("mp4_demux", &mp4_demux);
+  m.impl("packed_audio", &packed_audio);
   m.impl("cbcs_decrypt", &cbcs_decrypt);
   m.impl("cenc_decrypt", &cenc_decrypt);
   m.impl("segment_copy", &segment_copy);
@@ -634,6 +667,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cc_scratch_words", [](int64_t nseg, int64_t max_nal) { return es_::cc_scratch(nseg, max_nal).end; },
         py::arg("nseg"), py::arg("max_nal"));
   m.def("mp4_demux", &mp4_demux);
+  m.def("packed_audio", &packed_audio, py::arg("buf"), py::arg("off"), py::arg("len"), py::arg("cap"), py::arg("max_pes"),
+        py::arg("info"), py::arg("pes"), py::arg("nal"), py::arg("au"), py::arg("aframes"), py::arg("sinfo"),
+        py::arg("painfo"), py::arg("staged") = true);
+  m.def("packed_audio_tile_bytes", &D::packed_audio_tile_bytes);
   m.attr("CRC_GROUP_BYTES") = crc::kGroupBytes;
   m.attr("CRC_TILE_GROUPS") = crc::kTileGroups;
   m.def("cbcs_decrypt", &cbcs_decrypt);

@@ -198,6 +198,21 @@ struct Mp4DemuxArgs {
 };
 hipError_t launch_mp4_demux(const Mp4DemuxArgs& a);
 
+// packed_audio.hip: ID3v2 tags in front of raw ADTS frames (docs/PACKEDAUDIO.md).  One workgroup per
+// segment; info / pes as launch_ts_demux writes them, t.ix as launch_es_index does with one nal row.
+struct PackedAudioArgs {
+  const uint8_t* buf;  // segment i is buf[off[i], off[i] + clamp(len[i], 0, cap[i])), only read; off 16-byte aligned
+  int64_t buf_numel;
+  const int64_t *off, *len, *cap;
+  int nseg;
+  int64_t max_pes;     // es::packed_max_pes_ok
+  es::PackedTables t;  // au, aframes and nal 16-byte aligned
+  bool staged = true;  // false: the frame chain is walked in global memory (the variant that was measured against)
+  hipStream_t stream;
+};
+int packed_audio_tile_bytes();
+hipError_t launch_packed_audio(const PackedAudioArgs& a);
+
 struct CbcsArgs {
   const uint8_t* src;  // the demuxed segments, only read: segment i is src[src_off[i], + clamp(info[i].video_bytes, 0, cap[i]))
   int64_t src_numel;

@@ -30,6 +30,7 @@
 #include "hevc.hpp"
 #include "locator.hpp"
 #include "mp4.hpp"
+#include "packedaudio.hpp"
 #include "planner.hpp"
 #include "remux.hpp"
 #include "sampleaes.hpp"
@@ -763,6 +764,53 @@ PYBIND11_MODULE(_runtime, m) {
                             {"time_is_delta", mp4::kEmTimeIsDelta}, {"duration", mp4::kEmDuration}, {"id", mp4::kEmId},
                             {"data_offset", mp4::kEmDataOffset}, {"data_length", mp4::kEmDataLength},
                             {"is_id3", mp4::kEmIsId3}});
+
+  // Batched CPU packed-audio demux with the device kernel's layout (docs/PACKEDAUDIO.md): segment b
+  // is buf[off[b], off[b] + len[b]).
+  //   info / pes as demux_batch writes them; nal (one row) / au / aframes / sinfo as index_batch does
+  //   painfo: int64[B, ES_PAINFO_WORDS]
+  m.def("packed_audio_batch", [](Arr<uint8_t> buf, Arr<int64_t> off, Arr<int64_t> len, int64_t max_pes, py::array info,
+                                 py::array pes, py::array nal, py::array au, py::array aframes, py::array sinfo,
+                                 py::array painfo) {
+    const int64_t B = off.size();
+    if (!es::packed_max_pes_ok(max_pes)) throw std::invalid_argument("packed_audio_batch: max_pes must be 1 to 4096");
+    const es::PackedTables t{mut_ptr<int64_t>(info, "info"), mut_ptr<int64_t>(pes, "pes"),
+                             {mut_ptr<int32_t>(nal, "nal"), mut_ptr<int32_t>(au, "au"),
+                              mut_ptr<int32_t>(aframes, "aframes"), mut_ptr<int64_t>(sinfo, "sinfo")},
+                             mut_ptr<int64_t>(painfo, "painfo")};
+    if (len.size() != B || info.size() < B * ts::kInfoWords || pes.size() < ts::pes_words(B, max_pes) ||
+        nal.size() < table_words(B, es::kPackedNalRows, es::kNalWords) ||
+        au.size() < table_words(B, max_pes, es::kAuWords) || aframes.size() < table_words(B, max_pes, es::kApesWords) ||
+        sinfo.size() < B * es::kSinfoWords || painfo.size() < B * es::kPainfoWords)
+      throw std::invalid_argument("packed_audio_batch: an argument is too small");
+    const int64_t *o = off.data(), *l = len.data();
+    int64_t total = 0;
+    for (int64_t b = 0; b < B; ++b) {
+      if (o[b] < 0 || l[b] < 0 || l[b] >= (int64_t(1) << 31) || o[b] + l[b] > buf.size())
+        throw std::invalid_argument("packed_audio_batch: segment out of bounds");
+      total += l[b];
+    }
+    const uint8_t* base = buf.data();
+    py::gil_scoped_release nogil;
+    parallel_for(B, [&](int64_t b) {
+      es::packed_segment(base + o[b], l[b], max_pes, es::packed_tables_at(t, max_pes, b));
+    }, total);
+  });
+  m.attr("ES_PAINFO_WORDS") = es::kPainfoWords;
+  m.attr("ES_PACKED_FRAMES_PER_PES") = es::kPackedFramesPerPes;
+  m.attr("ES_PACKED_MAX_TAGS") = es::kPackedMaxTags;
+  m.attr("ES_PACKED_MAX_ID3_FRAMES") = es::kPackedMaxId3Frames;
+  m.attr("ES_PACKED_NAL_ROWS") = es::kPackedNalRows;
+  m.attr("ES_PACKED_TILE") = es::kPackedTile;
+  m.attr("ES_PACKED_MAX_PES_LIMIT") = es::kPackedMaxPesLimit;
+  m.attr("ES_PACKED_FATAL") = static_cast<int64_t>(es::kPaFatalMask);
+  name_dict(m, "ES_PAINFO", {{"status", es::kPaStatus}, {"id3_bytes", es::kPaId3Bytes}, {"n_tags", es::kPaNumTags},
+                             {"timestamp", es::kPaTimestamp}, {"n_frames", es::kPaNumFrames},
+                             {"stop_offset", es::kPaStopOffset}, {"sample_rate", es::kPaSampleRate},
+                             {"channels", es::kPaChannels}});
+  name_dict(m, "ES_PASTATUS", {{"no_timestamp", es::kPaNoTimestamp}, {"bad_id3", es::kPaBadId3},
+                               {"no_frame", es::kPaNoFrame}, {"trailing_bytes", es::kPaTrailingBytes},
+                               {"pes_overflow", es::kPaPesOverflow}, {"bad_rate", es::kPaBadRate}});
 
   // Batched CPU cbcs decryption with the device kernels' result (docs/CBCS.md): segment b is
   // src[src_off[b], + len[b]), only read, and dst[dst_off[b], + len[b]) already holds its copy; a

@@ -1,9 +1,10 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
 // runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp,
-// runtime/cenc.cpp, runtime/fragment.cpp) and by the gfx950
+// runtime/cenc.cpp, runtime/fragment.cpp, runtime/packedaudio.cpp) and by the gfx950
 // kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/fragment.hip, kernels/codec_config.hip,
-// kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip).  Plain inline
+// kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip,
+// kernels/packed_audio.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -1259,4 +1260,157 @@ HLSP2P_RULE void ctr_block(const uint32_t iv[4], int64_t j, uint32_t out[4]) {
   out[3] = ctr_bswap(static_cast<uint32_t>(low));
 }
 }  // namespace mp4
+
+// ---------------------------------------------------------------- packed audio (docs/PACKEDAUDIO.md)
+// One or more ID3v2 tags in front of raw ADTS frames.  A reader `rd` is the one of namespace mp4:
+// rd.u8(p) and rd.be32(p) of the segment, asked only for bytes of [0, n).
+namespace es {
+// 'com.apple.streaming.transportStreamTimestamp', four characters per word; a NUL and the 8-byte stamp follow
+constexpr int kPackedOwnerWords = 11;
+constexpr int kPackedPrivBytes = 4 * kPackedOwnerWords + 1 + 8;
+HLSP2P_RULE uint32_t packed_owner_word(int w) {
+  using mp4::fourcc;
+  switch (w) {
+    case 0: return fourcc('c', 'o', 'm', '.'); case 1: return fourcc('a', 'p', 'p', 'l');
+    case 2: return fourcc('e', '.', 's', 't'); case 3: return fourcc('r', 'e', 'a', 'm');
+    case 4: return fourcc('i', 'n', 'g', '.'); case 5: return fourcc('t', 'r', 'a', 'n');
+    case 6: return fourcc('s', 'p', 'o', 'r'); case 7: return fourcc('t', 'S', 't', 'r');
+    case 8: return fourcc('e', 'a', 'm', 'T'); case 9: return fourcc('i', 'm', 'e', 's');
+    case 10: return fourcc('t', 'a', 'm', 'p'); default: return 0;
+  }
+}
+HLSP2P_RULE bool syncsafe_ok(uint32_t v) { return (v & 0x80808080u) == 0; }
+HLSP2P_RULE int64_t syncsafe28(uint32_t v) {
+  return (int64_t((v >> 24) & 0x7f) << 21) | (int64_t((v >> 16) & 0x7f) << 14) | (int64_t((v >> 8) & 0x7f) << 7) |
+         int64_t(v & 0x7f);
+}
+
+// The ID3v2 tag header at t of [.., n).  !ok: no tag there.
+struct Id3Tag {
+  bool ok;
+  int version, flags;
+  int64_t size, total;  // the frames' bytes, and the whole tag with header and footer
+};
+template <class R>
+HLSP2P_RULE Id3Tag id3_tag_at(R& rd, int64_t t, int64_t n) {
+  Id3Tag g = {false, 0, 0, 0, 0};
+  if (t + 10 > n) return g;
+  const uint32_t head = mp4::be32(rd, t);
+  if ((head >> 8) != 0x494433u) return g;  // 'ID3'
+  g.version = static_cast<int>(head & 0xff);
+  if (g.version == 0xff || rd.u8(t + 4) == 0xff) return g;
+  g.flags = rd.u8(t + 5);
+  const uint32_t s = mp4::be32(rd, t + 6);
+  if (!syncsafe_ok(s)) return g;
+  g.size = syncsafe28(s);
+  g.total = 10 + g.size + ((g.flags & 0x10) ? 10 : 0);
+  g.ok = true;
+  return g;
+}
+// The 33-bit stamp of the first PRIV frame of the tag at t that carries one, -1: none.
+template <class R>
+HLSP2P_RULE int64_t id3_timestamp(R& rd, int64_t t, const Id3Tag& g) {
+  if ((g.version != 3 && g.version != 4) || (g.flags & 0xC0)) return -1;
+  int64_t f = t + 10;
+  const int64_t end = f + g.size;
+  for (int i = 0; i < kPackedMaxId3Frames && f + 10 <= end && rd.u8(f) != 0; ++i) {
+    const uint32_t raw = mp4::be32(rd, f + 4);
+    if (g.version == 4 && !syncsafe_ok(raw)) break;
+    const int64_t fsize = g.version == 4 ? syncsafe28(raw) : int64_t(raw);
+    if (fsize > end - (f + 10)) break;
+    if (fsize == kPackedPrivBytes && mp4::be32(rd, f) == mp4::fourcc('P', 'R', 'I', 'V')) {
+      const int64_t body = f + 10;
+      bool match = rd.u8(body + 4 * kPackedOwnerWords) == 0;
+      for (int w = 0; w < kPackedOwnerWords; ++w) match = match && mp4::be32(rd, body + 4 * w) == packed_owner_word(w);
+      if (match) {
+        const int64_t v = body + 4 * kPackedOwnerWords + 1;
+        return (int64_t(mp4::be32(rd, v) & 1u) << 32) | int64_t(mp4::be32(rd, v + 4));
+      }
+    }
+    f += 10 + fsize;
+  }
+  return -1;
+}
+// The leading tags: T is where the audio starts, or the tag that passes the end (kPaBadId3).
+struct PackedTags { int64_t status, T, n_tags, ts; };
+template <class R>
+HLSP2P_RULE PackedTags packed_tags(R& rd, int64_t n) {
+  PackedTags r = {0, 0, 0, -1};
+  for (int i = 0; i < kPackedMaxTags; ++i) {
+    const Id3Tag g = id3_tag_at(rd, r.T, n);
+    if (!g.ok) break;
+    if (r.T + g.total > n) {
+      r.status |= kPaBadId3;
+      break;
+    }
+    if (r.ts < 0) r.ts = id3_timestamp(rd, r.T, g);
+    r.T += g.total;
+    ++r.n_tags;
+  }
+  if (r.ts < 0) r.status |= kPaNoTimestamp;
+  return r;
+}
+
+// What the tags and the frame walk leave of a segment of n bytes; the three info rows are made of it.
+struct PackedSummary { int64_t status, T, n_tags, ts, n_frames, stop, rate, chans, n; };
+HLSP2P_RULE int64_t packed_groups(int64_t n_frames) { return (n_frames + kPackedFramesPerPes - 1) / kPackedFramesPerPes; }
+// the stamp of group k: not wrapped at 2^33
+HLSP2P_RULE int64_t packed_stamp(int64_t ts, int64_t k, int64_t rate) {
+  return rate > 0 ? ts + (k * kPackedFramesPerPes * kAacFrameSamples * 90000 + rate / 2) / rate : ts;
+}
+// rate_index / channel byte pair of the first frame: A[q + 2], A[q + 3]
+HLSP2P_RULE int adts_channels(int b2, int b3) { return ((b2 & 1) << 2) | (b3 >> 6); }
+HLSP2P_RULE PackedSummary packed_summary(const PackedTags& g, int64_t n_frames, int64_t stop, int64_t rate, int64_t chans,
+                                         int64_t n, int64_t max_pes) {
+  PackedSummary s = {g.status, g.T, g.n_tags, g.ts, n_frames, stop, rate, chans, n};
+  if (!(g.status & kPaBadId3)) {
+    if (n_frames == 0) s.status |= kPaNoFrame;
+    else if (stop != n) s.status |= kPaTrailingBytes;
+    if (n_frames > 0 && rate == 0) s.status |= kPaBadRate;
+  }
+  if (packed_groups(n_frames) > max_pes) s.status |= kPaPesOverflow;
+  return s;
+}
+HLSP2P_RULE int64_t packed_info_word(int i, const PackedSummary& s, int64_t max_pes) {
+  const int64_t groups = packed_groups(s.n_frames), rec = groups < max_pes ? groups : max_pes;
+  switch (i) {
+    case ts::kStatus: return groups > max_pes ? int64_t(ts::kPesOverflow) : 0;
+    case ts::kPmtPid: case ts::kVideoPid: case ts::kAudioPid: case ts::kId3Pid: return -1;
+    case ts::kAudioBytes: return s.n - s.T;
+    case ts::kId3Bytes: return s.T;
+    case ts::kNumAudioPes: return groups;
+    case ts::kNumId3Pes: return s.T > 0;
+    case ts::kAudioType: return ts::kAdtsAac;
+    case ts::kPayloadBytes: return s.n;
+    case ts::kFirstPts: case ts::kLastPts: return -1;
+    case ts::kFirstPts + 1: return rec > 0 ? packed_stamp(s.ts, 0, s.rate) : -1;
+    case ts::kLastPts + 1: return rec > 0 ? packed_stamp(s.ts, rec - 1, s.rate) : -1;
+    case ts::kFirstPts + 2: case ts::kLastPts + 2: return s.T > 0 ? s.ts : -1;
+    case ts::kAudioEsOffset: return s.T;
+    default: return 0;  // no packets, no video, the id3 ES at 0
+  }
+}
+HLSP2P_RULE int64_t packed_sinfo_word(int i, const PackedSummary& s) {
+  switch (i) {
+    case kStatus: return (s.status & kPaTrailingBytes) ? int64_t(kAdtsError) : 0;
+    case kFirstKeyframeAu: return -1;
+    case kNumAdtsFrames: return s.n_frames;
+    case kAudioSampleRate: return s.rate;
+    case kAudioChannels: return s.chans;
+    default: return 0;
+  }
+}
+HLSP2P_RULE int64_t packed_painfo_word(int i, const PackedSummary& s) {
+  switch (i) {
+    case kPaStatus: return s.status;
+    case kPaId3Bytes: return s.T;
+    case kPaNumTags: return s.n_tags;
+    case kPaTimestamp: return s.ts;
+    case kPaNumFrames: return s.n_frames;
+    case kPaStopOffset: return s.stop;
+    case kPaSampleRate: return s.rate;
+    default: return s.chans;
+  }
+}
+}  // namespace es
 }  // namespace hlsp2p

@@ -303,6 +303,39 @@ struct CcScratch { int64_t flag, hit, end; };
 constexpr CcScratch cc_scratch(int64_t nseg, int64_t max_nal) {
   return {0, (nseg * max_nal + 3) / 4 * 4, (nseg * max_nal + 3) / 4 * 4 + nseg * max_nal * (kCcSlotBytes / 4)};
 }
+
+// ---- packed audio: ID3v2 tags in front of raw ADTS frames (docs/PACKEDAUDIO.md).  info / pes have
+// the layouts of ts:: above, nal / au / aframes / sinfo those of the index; nal has one row.
+constexpr int kPackedFramesPerPes = 4;  // G: ADTS frames per audio PES row
+constexpr int kPackedMaxTags = 8;       // leading tags that are looked at
+constexpr int kPackedMaxId3Frames = 32; // frames read inside one tag
+constexpr int kPackedNalRows = 1;       // max_nal of the views: there is no video
+constexpr int kPackedTile = 32768;      // bytes of a segment staged in LDS per round of the frame walk
+constexpr int64_t kPackedMaxPesLimit = 4096;  // max_pes: 1 .. this (the walk keeps max_pes + 1 offsets in LDS)
+constexpr bool packed_max_pes_ok(int64_t v) { return v >= 1 && v <= kPackedMaxPesLimit; }
+constexpr int kAacFrameSamples = 1024;
+constexpr int kPainfoWords = 8;
+// painfo[] row (int64), identical on host and device
+enum Painfo : int {
+  kPaStatus = 0,
+  kPaId3Bytes = 1,    // T: where the audio starts
+  kPaNumTags = 2,     // whole leading tags
+  kPaTimestamp = 3,   // 33 bits, -1: none
+  kPaNumFrames = 4,   // true total
+  kPaStopOffset = 5,  // where the frame walk ended
+  kPaSampleRate = 6, kPaChannels = 7,
+};
+enum PackedStatus : int64_t {
+  kPaNoTimestamp = 1, kPaBadId3 = 2, kPaNoFrame = 4, kPaTrailingBytes = 8, kPaPesOverflow = 16, kPaBadRate = 32,
+};
+// the bits that make a segment unusable for a player
+constexpr int64_t kPaFatalMask = kPaNoTimestamp | kPaBadId3 | kPaNoFrame | kPaBadRate;
+// One segment's seven output tables, or a batch's.
+struct PackedTables {
+  int64_t *info, *pes;
+  IndexTables<int32_t, int64_t> ix;
+  int64_t* painfo;
+};
 }  // namespace es
 
 // ---------------------------------------------------------------- fragmented MP4 demux (docs/FMP4DEMUX.md)

@@ -109,6 +109,11 @@ def _default_config() -> Dict[str, Any]:
         # device (docs/CAPTIONS.md; implies the index) and emit it on FRAG_PARSING_USERDATA; hls.js's
         # name, off by default here like every device feature
         "enableCEA708Captions": False,
+        # packed audio (docs/PACKEDAUDIO.md): a fragment of ID3v2 tags in front of raw ADTS frames,
+        # demuxed on the transmux device with the events of an MPEG-TS fragment.  "auto": a fragment
+        # without #EXT-X-MAP whose URL path ends in ".aac" (query dropped, any letter case);
+        # True: every fragment without a map; False: none (such a fragment fails in the TS demux)
+        "packedAudio": "auto",
     }
 
 

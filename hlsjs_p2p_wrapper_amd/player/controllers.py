@@ -794,9 +794,14 @@ class StreamController:
         ticket = getattr(payload, "swarm_verify", None)
         if method == "SAMPLE-AES-CTR":  # no such thing on MPEG-TS: the fragment goes through as it is
             sample_key = sample_iv = None
-        job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
-                          bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
-                          sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions")))
+        try:
+            job = TransmuxJob(payload, key, iv, lambda r: self._on_parsed(frag, stats, r), frag, ticket,
+                              bool(self.hls.config.get("indexSamples")), bool(self.hls.config.get("remuxFmp4")),
+                              sample_key, sample_iv, bool(self.hls.config.get("enableCEA708Captions")),
+                              packed_audio=self._is_packed_audio(frag))
+        except ValueError as e:  # SAMPLE-AES on packed audio
+            self._on_parsed(frag, stats, {"error": e, "status": -1})
+            return
         if self.hls.config.get("fmp4Fragments"):
             # the moof boxes on the device, on the playlist's timeline: a fragment whose discontinuity
             # counter has no initPTS yet anchors its first stamp to its own playlist start (so do all
@@ -810,6 +815,15 @@ class StreamController:
             job.anchor = base is None
             job.time_base = 0 if base is None else base
         pipeline_for(dev, self.loop).submit(job)
+
+    def _is_packed_audio(self, frag: Fragment) -> bool:
+        """``packedAudio`` for a fragment without ``#EXT-X-MAP`` (docs/PACKEDAUDIO.md)."""
+        mode = self.hls.config.get("packedAudio")
+        if mode == "auto":
+            url = frag.url
+            q = url.find("?")  # once per fragment, MPEG-TS ones included: no copy of the whole URL
+            return (url[-4:] if q < 0 else url[max(q - 4, 0):q]).lower() == ".aac"
+        return bool(mode)
 
     # ------------------------------------------------------------------ fragmented MP4 (docs/FMP4DEMUX.md)
     def _load_init_segment(self, init_segment: Any, waiter: Any) -> None:

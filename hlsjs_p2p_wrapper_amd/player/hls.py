@@ -35,7 +35,10 @@ class _DefaultConfigDescriptor:
 
 class Hls:
     """hls.js-compatible media engine: playlist / key / fragment loaders, level and ABR
-    controllers, transmux to the media element; events through ``on`` / ``trigger``."""
+    controllers, transmux to the media element; events through ``on`` / ``trigger``.  Fragments are
+    MPEG-TS, fragmented MP4 behind ``#EXT-X-MAP``, or packed audio (ID3v2 tags in front of raw ADTS
+    AAC frames; config key ``packedAudio``: ``"auto"``, the default, takes a fragment without a map
+    whose URL path ends in ``.aac``, ``True`` every fragment without a map, ``False`` none)."""
     Events = Events
     ErrorTypes = ErrorTypes
     ErrorDetails = ErrorDetails

@@ -52,17 +52,22 @@ class TransmuxJob:
     asks for the ``cbcs`` decrypt (``docs/CBCS.md``) or the ``cenc`` decrypt (``docs/CENC.md``): it is
     accepted when the init segment has a track protected under one of the two schemes, which decides
     the decrypt that runs (``scheme``; the key of ``sample_iv`` serves a track without an IV of its
-    own), and the result's ``data`` and views are then those of the decrypted copy."""
+    own), and the result's ``data`` and views are then those of the decrypted copy.  ``packed_audio``:
+    the payload is a packed-audio segment, ID3v2 tags in front of raw ADTS frames
+    (``docs/PACKEDAUDIO.md``): the batch demuxes it where it lies and the result has the shape of an
+    MPEG-TS fragment's, with ``container`` ``"aac"`` and ``packed_audio``; not with ``mp4`` or
+    ``sample_key``."""
 
     __slots__ = ("payload", "key", "iv", "callback", "frag", "verify", "index", "remux", "sample_key", "sample_iv",
-                 "captions", "mp4", "scheme", "fragment", "sequence_number", "time_base", "time_ref", "anchor")
+                 "captions", "mp4", "scheme", "fragment", "sequence_number", "time_base", "time_ref", "anchor",
+                 "packed_audio", "aside")
 
     def __init__(self, payload: Any, key: Optional[bytes], iv: Optional[bytes],
                  callback: Callable[[Dict[str, Any]], None], frag: Any = None, verify: Any = None,
                  index: bool = False, remux: bool = False, sample_key: Optional[bytes] = None,
                  sample_iv: Optional[bytes] = None, captions: bool = False, mp4: Any = None,
                  fragment: bool = False, sequence_number: int = 0, time_base: int = 0, time_ref: int = -1,
-                 anchor: bool = False) -> None:
+                 anchor: bool = False, packed_audio: bool = False) -> None:
         # ``fragment`` (implies ``remux``): the batch also writes both moof boxes of this fragment in
         # front of its mdat boxes (ops/fragment.py, docs/FRAGMENT.md) and the tracks of its ``fmp4``
         # gain ``fragment``, ``moof_view`` and ``tfdt``.  ``sequence_number`` goes into the mfhd;
@@ -71,6 +76,13 @@ class TransmuxJob:
         # that follows comes back as ``fmp4["time_base"]``
         if fragment and anchor and time_ref < 0:
             raise ValueError("TransmuxJob: an anchored fragment needs a time_ref >= 0")
+        if packed_audio and mp4 is not None:
+            raise ValueError("TransmuxJob: a fragment is packed audio or fragmented MP4, not both")
+        if packed_audio and sample_key is not None:
+            raise ValueError("TransmuxJob: SAMPLE-AES packed audio is not supported")
+        self.packed_audio = packed_audio
+        # mp4 or packed_audio: the pipeline sets the job aside in front of the MPEG-TS columns
+        self.aside = packed_audio or mp4 is not None
         remux = remux or fragment
         self.fragment = fragment
         self.sequence_number, self.time_base, self.time_ref, self.anchor = sequence_number, time_base, time_ref, anchor
@@ -199,7 +211,7 @@ class MediaPipeline:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.loop = loop or get_event_loop()
         self._jobs: List[TransmuxJob] = []
-        self._any_mp4 = False  # a submitted job carries an Mp4Init: launch() sets those aside
+        self._any_aside = False  # a submitted job is fragmented MP4 or packed audio: launch() sets those aside
         self._scheduled = False
         self.segments = 0
         self.bytes_in = 0
@@ -212,8 +224,8 @@ class MediaPipeline:
 
     def submit(self, job: TransmuxJob) -> None:
         self._jobs.append(job)
-        if job.mp4 is not None:
-            self._any_mp4 = True
+        if job.aside:
+            self._any_aside = True
         if self.auto_flush and not self._scheduled:
             self._scheduled = True
             self.loop.call_soon(self.flush)
@@ -228,27 +240,34 @@ class MediaPipeline:
         jobs, self._jobs = self._jobs, []
         if not jobs:
             return None
-        mp4 = None
-        if self._any_mp4:  # fragmented-MP4 jobs take their own path, in front of the columns
-            self._any_mp4 = False
-            mp4 = self._launch_mp4([j for j in jobs if j.mp4 is not None])
-            jobs = [j for j in jobs if j.mp4 is None]
+        mp4 = packed = None
+        if self._any_aside:  # fragmented-MP4 and packed-audio jobs take their own paths, in front of the columns
+            self._any_aside = False
+            mj = [j for j in jobs if j.mp4 is not None]
+            pj = [j for j in jobs if j.packed_audio]
+            mp4 = self._launch_mp4(mj) if mj else None
+            packed = self._launch_packed(pj) if pj else None
+            jobs = [j for j in jobs if not j.aside]
             if not jobs:
-                return _Batch([], groups=[], n=0, mp4=mp4)
+                return _Batch([], groups=[], n=0, mp4=mp4, packed=packed)
         try:
             b = self._launch_core(self._job_columns(jobs))
         except Exception as e:  # deliver the failure to every job of the batch
-            return _Batch(jobs, groups=[], error=e, n=len(jobs), mp4=mp4)
+            return _Batch(jobs, groups=[], error=e, n=len(jobs), mp4=mp4, packed=packed)
         b.jobs = jobs
         b.mp4 = mp4
+        b.packed = packed
         return b
 
     def complete(self, batch: Optional["_Batch"]) -> None:
         """Wait for a launched batch and run the per-fragment callbacks."""
         if batch is None:
             return
-        if batch.mp4 is not None:
-            self._complete_mp4(batch.mp4)
+        if batch.mp4 is not None or batch.packed is not None:
+            if batch.mp4 is not None:
+                self._complete_mp4(batch.mp4)
+            if batch.packed is not None:
+                self._complete_packed(batch.packed)
             if not batch.jobs:
                 return
         if batch.error is not None:
@@ -468,50 +487,58 @@ class MediaPipeline:
 
                 g.cc = cc = _cc.caption_batch(g.res, ix, c.nb[g.rows], enable=c.captions[g.rows].tolist())
                 g.ccinfo = _to_host(cc.ccinfo)
-            # ... and the remux of a group in which any row asked: one ``remux_batch`` call behind
-            # the index, its three tables on the same way to the host
+            # ... and the remux of a group in which any row asked (:meth:`_launch_remux`)
             if c.remux is not None and c.remux[g.rows].any():
-                from ..ops import remux as _rmx
-
-                # a group in which any row asked for its moof boxes leaves room for them in every
-                # region (so a row that did not ask sees a larger ``audio_box_offset``, nothing else)
-                # and gets one ``fragment_batch`` call behind the remux, its ``finfo`` rows on the
-                # same way to the host (docs/FRAGMENT.md)
                 fragment = c.fragment is not None and bool(c.fragment[g.rows].any())
-                headroom = gap = 0
-                if fragment:
-                    from ..ops import fragment as _frg
-
-                    headroom = _frg.frag_headroom(g.res.pes.shape[2])
-                    gap = _frg.frag_audio_gap(_rmx.DEFAULT_MAX_AFRAMES)
-                out_offs, size = _rmx.layout_out(c.nb[g.rows], ix.nal.shape[1], headroom=headroom, audio_gap=gap)
-                g.rx = rx = _rmx.remux_batch(g.res, ix, c.nb[g.rows],
-                                             torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
-                                             out_offs, audio_gap=gap, headroom=headroom)
-                g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
-                if fragment:
-                    fp = c.frag_params[g.rows]
-                    g.fr = fr = _frg.fragment_batch(rx, ix, fp[:, 0], time_base=fp[:, 1], time_ref=fp[:, 2],
-                                                    anchor=fp[:, 3] != 0)
-                    g.finfo = _to_host(fr.finfo)
-                # ... and what the init segments are built from: one ``config_batch`` call behind the
-                # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
-                from ..ops import codecconfig as _cfg
-
-                g.cfg = cfg = _cfg.config_batch(g.res, ix, c.nb[g.rows])
-                g.cinfo, g.ps = _to_host(cfg.cinfo), _to_host(cfg.ps)
-                # ... and one ``hevc_config_batch`` call behind it for the HEVC segments among them:
-                # the codec is only known on the device, so the launch is unconditional and the
-                # workgroup of any other segment exits at once
-                from ..ops import hevcconfig as _hcfg
-
-                g.hcfg = hcfg = _hcfg.hevc_config_batch(g.res, ix, c.nb[g.rows])
-                g.hvinfo, g.hps = _to_host(hcfg.hinfo), _to_host(hcfg.hps)
+                self._launch_remux(g, c.nb[g.rows], c.frag_params[g.rows] if fragment else None)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
         return _Batch(None, groups=groups, event=ev, keep=keep, tag=tag, n=n, start=ev0, verify=verify or None,
                       expect_mask=mask)
+
+    def _launch_remux(self, g: "_Group", caps: np.ndarray, frag_params: Optional[np.ndarray]) -> None:
+        """The remux of an indexed group in which a row asked for it: one ``remux_batch`` call behind
+        the index, its three tables on their way to the host; ``frag_params`` (the group's rows of
+        (sequence number, time base, time reference, anchor), ``None``: no row asked for its moof
+        boxes) adds one ``fragment_batch`` call behind it; then the two configuration calls."""
+        from ..ops import remux as _rmx
+
+        ix = g.ix
+        # a group in which any row asked for its moof boxes leaves room for them in every
+        # region (so a row that did not ask sees a larger ``audio_box_offset``, nothing else)
+        # and gets one ``fragment_batch`` call behind the remux, its ``finfo`` rows on the
+        # same way to the host (docs/FRAGMENT.md)
+        fragment = frag_params is not None
+        headroom = gap = 0
+        if fragment:
+            from ..ops import fragment as _frg
+
+            headroom = _frg.frag_headroom(g.res.pes.shape[2])
+            gap = _frg.frag_audio_gap(_rmx.DEFAULT_MAX_AFRAMES)
+        out_offs, size = _rmx.layout_out(caps, ix.nal.shape[1], headroom=headroom, audio_gap=gap)
+        g.rx = rx = _rmx.remux_batch(g.res, ix, caps,
+                                     torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
+                                     out_offs, audio_gap=gap, headroom=headroom)
+        g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
+        if fragment:
+            fp = frag_params
+            g.fr = fr = _frg.fragment_batch(rx, ix, fp[:, 0], time_base=fp[:, 1], time_ref=fp[:, 2],
+                                            anchor=fp[:, 3] != 0)
+            g.finfo = _to_host(fr.finfo)
+        # ... and what the init segments are built from: one ``config_batch`` call behind the
+        # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
+        from ..ops import codecconfig as _cfg
+
+        g.cfg = cfg = _cfg.config_batch(g.res, ix, caps)
+        g.cinfo, g.ps = _to_host(cfg.cinfo), _to_host(cfg.ps)
+        # ... and one ``hevc_config_batch`` call behind it for the HEVC segments among them:
+        # the codec is only known on the device, so the launch is unconditional and the
+        # workgroup of any other segment exits at once
+        from ..ops import hevcconfig as _hcfg
+
+        g.hcfg = hcfg = _hcfg.hevc_config_batch(g.res, ix, caps)
+        g.hvinfo, g.hps = _to_host(hcfg.hinfo), _to_host(hcfg.hps)
 
     def _host_groups(self, c: _Columns, rows: np.ndarray) -> List["_Group"]:
         """The host backend: ``ops.aes.cbc_decrypt_batch`` over the encrypted rows, then
@@ -639,6 +666,94 @@ class MediaPipeline:
                 if g.cbinfo is not None:
                     view = cbcs_view if g.scheme == "cbcs" else cenc_view
                     r[g.scheme] = MappingProxyType(view(_np(g.cbinfo)[k]))
+                results[i] = r
+        for j, r in zip(b.jobs, results):
+            j.callback(r)
+
+    # ------------------------------------------------------------------ packed audio (docs/PACKEDAUDIO.md)
+    def _launch_packed(self, jobs: List[TransmuxJob]) -> "_PackedBatch":
+        """Enqueue the packed-audio jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
+        rows, one ``packed_audio_batch`` per group (the encrypted rows in the decrypt's buffer, the
+        clear ones where they lie), and for a group in which a job asked for it the remux, fragment and
+        configuration calls of :meth:`_launch_remux` over its views; ``info``, ``sinfo``, ``painfo``
+        and the remux tables are on their way to pinned host memory in front of the event."""
+        from ..ops import packedaudio as _pa
+
+        try:
+            dev = self.device
+            tensors = [_as_tensor(j.payload) for j in jobs]
+            sizes = [t.numel() for t in tensors]
+            src, src_offs = self._stage(tensors, sizes)
+            offs, nb = np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
+            enc = np.array([j.key is not None for j in jobs], dtype=bool)
+            ok = ~(enc & ((nb <= 0) | (nb % 16 != 0)))
+            self.segments += len(jobs)
+            self.bytes_in += int(nb.sum())
+            work = []
+            e, cl = np.flatnonzero(enc & ok), np.flatnonzero(~enc)
+            if len(e):
+                caps = nb[e]
+                dec_offs, size = _layout(caps)
+                dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+                il = e.tolist()
+                out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
+                                                 [bytes(jobs[i].iv) for i in il], dec, dec_offs)
+                work.append((e, dec, dec_offs, out_len, caps))
+            if len(cl):
+                work.append((cl, src, offs[cl], nb[cl], nb[cl]))
+            groups = []
+            for idx, buf, o, lens, caps in work:
+                il = idx.tolist()
+                pa = _pa.packed_audio_batch(buf, o, lens, caps=caps)
+                hlens = _to_host(lens) if isinstance(lens, torch.Tensor) else lens
+                g = _Group(idx, pa.as_demux(), _to_host(pa.info), hlens, ix=pa.as_index(), sinfo=_to_host(pa.sinfo),
+                           painfo=_to_host(pa.painfo))
+                if any(jobs[i].remux for i in il):
+                    fp = None
+                    if any(jobs[i].fragment for i in il):
+                        fp = np.array([(j.sequence_number, j.time_base, j.time_ref, j.anchor) if j.fragment
+                                       else (0, 0, -1, 0) for j in (jobs[i] for i in il)], dtype=np.int64)
+                    self._launch_remux(g, caps, fp)
+                groups.append(g)
+            ev = self._event() if dev.type == "cuda" and groups else None
+            return _PackedBatch(jobs, groups, ev, None, np.flatnonzero(~ok))
+        except Exception as e:  # deliver the failure to every packed-audio job of the batch
+            return _PackedBatch(jobs, [], None, e, np.zeros(0, dtype=np.int64))
+
+    def _complete_packed(self, b: "_PackedBatch") -> None:
+        """Wait for the packed-audio jobs of a batch and run their callbacks: results of the MPEG-TS
+        shape, with ``container`` and ``packed_audio``."""
+        from ..ops.packedaudio import FATAL, PAINFO, PASTATUS
+
+        if b.error is not None:
+            for j in b.jobs:
+                j.callback({"error": b.error, "status": -1, "container": "aac"})
+            return
+        if b.event is not None:
+            b.event.synchronize()
+            self._free_events.append(b.event)
+        results: List[Any] = [None] * len(b.jobs)
+        for i in b.rejected.tolist():
+            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1,
+                          "container": "aac"}
+        for g in b.groups:
+            res = g.res
+            rl, srows, prows = _np(g.hinfo).tolist(), _np(g.sinfo).tolist(), _np(g.painfo).tolist()
+            hlens = _np(g.hlens)
+            for k, (i, base) in enumerate(zip(g.rows.tolist(), res.es_offs.tolist())):
+                job, row, plain, pa = b.jobs[i], rl[k], int(hlens[k]), prows[k]
+                r = _Result(status=row[0], info=InfoRow(row), plain_bytes=plain, demux=res, index=k, container="aac",
+                            packed_audio=MappingProxyType({name: pa[slot] for name, slot in PAINFO.items()}))
+                r._es = (res.es, base, row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
+                if plain < 0:
+                    r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
+                elif pa[PAINFO["status"]] & FATAL:
+                    names = [name for name, bit in PASTATUS.items() if pa[PAINFO["status"]] & FATAL & bit]
+                    r["error"] = ValueError("packed audio: " + ", ".join(names))
+                if job.index:
+                    r["samples"] = Samples(srows[k], g.ix, k)
+                if g.rx is not None and job.remux:
+                    r["fmp4"] = Fmp4(g, k, srows[k], g.fr is not None and job.fragment)
                 results[i] = r
         for j, r in zip(b.jobs, results):
             j.callback(r)
@@ -1189,6 +1304,16 @@ class _Group:
     hcfg: Any = None  # HevcConfig, behind the codec configuration, with ...
     hvinfo: Any = None  # ... its two tensors on the host
     hps: Any = None
+    painfo: Any = None  # the painfo rows of a packed-audio group on the host
+
+
+@dataclass(eq=False)
+class _PackedBatch:
+    jobs: List[TransmuxJob]
+    groups: List[_Group]  # res / ix are the views of the group's PackedAudio
+    event: Any
+    error: Optional[BaseException]
+    rejected: Any  # jobs whose encrypted payload is not whole AES blocks
 
 
 @dataclass(eq=False)
@@ -1204,6 +1329,7 @@ class _Batch:
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
     mp4: Any = None  # _Mp4Batch: the batch's fragmented-MP4 jobs, which took their own path
+    packed: Any = None  # _PackedBatch: the batch's packed-audio jobs, which took theirs
 
     # the groups as the benchmark's output dump reads them: derived, nothing is stored twice
     @property

@@ -5,11 +5,13 @@ host packing they replace), the codec configuration for the init segments
 (H.264 and HEVC), the SAMPLE-AES decrypt of the same ES protected by the tool, the caption extraction
 on a video ES the tool writes itself, the fragmented-MP4 demux on segments the tool writes itself (one
 ``moof`` and thirty), the cbcs decrypt of such segments protected by the tool (the demux row's segment and
-one of about 3 MB), the cenc decrypt of the same two segments protected under cenc, and the MFMA CRC
+one of about 3 MB), the cenc decrypt of the same two segments protected under cenc, the packed-audio demux
+on segments the tool writes itself (the walk through LDS tiles, the one through global memory and the
+batched copy of the same bytes), and the MFMA CRC
 with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
-    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20]
+    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20] [--only packedaudio]
 """
 import argparse
 import json
@@ -21,8 +23,8 @@ import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
 from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, fragment, hevcconfig,
-                                       mp4demux, remux, sampleaes, segment, tsdemux)
-from hlsjs_p2p_wrapper_amd.ops._native import runtime
+                                       mp4demux, packedaudio, remux, sampleaes, segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops._native import device, runtime
 from hlsjs_p2p_wrapper_amd.player import fmp4
 
 
@@ -192,6 +194,54 @@ def mp4_row(moofs, segs, iters, dev):
     return round(timed(lambda: mp4demux.mp4_demux_batch(d, offs, lens, tracks), iters), 1)
 
 
+def packed_segment(seed, n_frames=470, stamp=900000):
+    """A packed-audio segment (``docs/PACKEDAUDIO.md``) of about 160 KB: one ID3v2.4 tag whose PRIV frame
+    holds the transport stream timestamp, then ``n_frames`` ADTS frames (48 kHz stereo AAC-LC, 7-byte
+    headers) of 310 to 370 bytes, about ten seconds at 128 kb/s."""
+    rng = np.random.default_rng(seed)
+    body = b"com.apple.streaming.transportStreamTimestamp\0" + struct.pack(">Q", stamp + seed)
+    out = [b"ID3\x04\0\0" + bytes([0, 0, 0, 10 + len(body)]) + b"PRIV" + bytes([0, 0, 0, len(body)]) + b"\0\0" + body]
+    for n in rng.integers(310, 371, n_frames).tolist():
+        out.append(bytes([0xFF, 0xF1, 0x4C, 0x80 | (n >> 11), (n >> 3) & 0xFF, ((n & 7) << 5) | 0x1F, 0xFC])
+                   + rng.integers(0, 256, n - 7, dtype=np.uint8).tobytes())
+    return b"".join(out)
+
+
+def packed_row(segs, iters, dev):
+    """``packed_audio_batch`` on ``segs`` segments of :func:`packed_segment`: us per call of the op, of the
+    kernel's two frame walks through the raw binding (LDS tiles, global memory) and of ``copy_segments``
+    over the same bytes, after checking the totals and the first and the last segment of both walks
+    against the host implementation."""
+    data = [np.frombuffer(packed_segment(i), np.uint8) for i in range(segs)]
+    lens = [len(x) for x in data]
+    stride = (max(lens) + 255) // 256 * 256
+    buf = np.zeros(stride * segs + 256, np.uint8)
+    offs = [stride * i for i in range(segs)]
+    for o, x in zip(offs, data):
+        buf[o:o + len(x)] = x
+    d = torch.from_numpy(buf).to(dev)
+    names = ("info", "pes", "nal", "au", "aframes", "sinfo", "painfo")
+    got = packedaudio.packed_audio_batch(d, offs, lens)
+    host = packedaudio.packed_audio_batch(torch.from_numpy(buf), offs, lens)
+    t = {k: getattr(got, k) for k in names}
+    o_d, n_d = (torch.tensor(v, dtype=torch.int64, device=dev) for v in (offs, lens))
+    raw = lambda staged: device().packed_audio(d, o_d, n_d, n_d, got.pes.shape[2], *t.values(), staged=staged)  # noqa: E731
+    for staged in (True, False):
+        for v in t.values():
+            v.fill_(-7)
+        raw(staged)
+        for i in (0, segs - 1):
+            assert all(torch.equal(t[k][i].cpu(), getattr(host, k)[i]) for k in names), "packedaudio mismatch"
+    pa = host.painfo.numpy()
+    assert not pa[:, 0].any() and (pa[:, 4] == 470).all() and (pa[:, 6] == 48000).all(), "packedaudio totals"
+    cp = torch.empty_like(d)
+    return {"packedaudio_us": round(timed(lambda: packedaudio.packed_audio_batch(d, offs, lens), iters), 1),
+            "packedaudio_kernel_us": round(timed(lambda: raw(True), iters), 1),
+            "packedaudio_direct_us": round(timed(lambda: raw(False), iters), 1),
+            "packedaudio_copy_us": round(timed(lambda: segment.copy_segments(d, cp, offs, offs, lens), iters), 1),
+            "packedaudio_bytes": int(sum(lens))}
+
+
 CBCS_KEY, CBCS_IV = bytes(range(0x40, 0x50)), (bytes(range(0x70, 0x80)), bytes(range(0x90, 0xA0)))
 
 
@@ -319,8 +369,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segs", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--only", choices=["packedaudio"], default=None, help="run that row alone (for a profiler)")
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.only == "packedaudio":
+        print(json.dumps(packed_row(args.segs, args.iters, dev)))
+        return
     origin = SyntheticHlsOrigin("http://cdn.kb/", renditions=PRESET_1080P_6M, num_segments=args.segs,
                                 encrypted=True, pool_size=args.segs, pin_memory=True, seed=3)
     pool = origin.pools[0]
@@ -479,6 +533,10 @@ def main():
     # segments protected under cenc: every NAL unit behind its header byte and the audio whole
     res["cenc_us"], res["cenc_bytes"] = cenc_row(200, args.segs, args.iters, dev)
     res["cenc_large_us"], res["cenc_large_bytes"] = cenc_row(23000, args.segs, args.iters, dev)
+    # the packed-audio demux (tags, the serial frame chain, rows) on 64 segments of the tool's own: about
+    # 470 ADTS frames behind one ID3 tag each; beside it the kernel through the raw binding with the chain
+    # walked in LDS tiles and in global memory, and the batched copy of the same bytes
+    res.update(packed_row(args.segs, args.iters, dev))
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
