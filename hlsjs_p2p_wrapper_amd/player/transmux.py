@@ -16,6 +16,12 @@ kernels on CPU).  ``launch()`` (jobs submitted one by one) and ``launch_columns(
 rank's arrays) are adapters over it, and ``_rows`` gathers a completed batch's result rows
 for ``complete()``, ``complete_arrays()`` and ``complete_columns()`` alike.
 
+Fragmented-MP4 and packed-audio jobs are set aside in front of the columns and take one path of
+their own, ``_launch_aside`` / ``_complete_aside``, told apart by :class:`_Mp4` and
+:class:`_Packed`.  What the containers share is written once: ``_accepted`` (the reject rule),
+``_cbc_work`` (the AES-128 decrypt and the demux work list), ``_group_steps`` (what follows a
+group's demux), ``_ts_result`` / ``_attach`` (the MPEG-TS shaped result and what hangs off it).
+
 The batching point is per (thread, device): the peer threads of an in-process swarm each
 get their own pipeline.
 """
@@ -38,6 +44,10 @@ from ..ops._native import device as _native_device
 from ..utils.trace import PhaseTimer
 
 ALIGN = 256
+# the errors of a fragment's result (``ValueError``)
+ERR_BLOCKS = "encrypted payload is not a multiple of 16 bytes"
+ERR_PADDING = "decryption failed (bad PKCS#7 padding)"
+ERR_CRC = "received segment failed its CRC check"
 
 
 class TransmuxJob:
@@ -154,14 +164,62 @@ def _np(x) -> np.ndarray:
     return x.numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
-def _to_host(t: torch.Tensor):
+def _to_host(t):
     """A small device tensor on its way into pinned host memory (async, on the current
-    stream: readable after the batch's event); a CPU tensor as numpy."""
+    stream: readable after the batch's event); a CPU tensor as numpy, a numpy array as it is."""
+    if not isinstance(t, torch.Tensor):
+        return t
     if t.device.type == "cpu":
         return t.numpy()
     h = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
     h.copy_(t, non_blocking=True)
     return h
+
+
+def _accepted(enc: np.ndarray, nb: np.ndarray) -> np.ndarray:
+    """bool[n], the reject rule: an encrypted row must be a positive number of whole AES blocks."""
+    return ~(enc & ((nb <= 0) | (nb % 16 != 0)))
+
+
+def _enc_iv(jobs: List[TransmuxJob]) -> Tuple[List[int], np.ndarray, np.ndarray]:
+    """The AES-128 jobs among ``jobs``: their positions, ``enc`` bool[n] and ``iv`` uint8[n, 16]."""
+    n = len(jobs)
+    e = [i for i, j in enumerate(jobs) if j.key is not None]
+    enc = np.zeros(n, dtype=bool)
+    iv = np.zeros((n, 16), dtype=np.uint8)
+    if e:
+        enc[e] = True
+        iv[e] = np.frombuffer(b"".join(bytes(jobs[i].iv) for i in e), dtype=np.uint8).reshape(-1, 16)
+    return e, enc, iv
+
+
+def _frag_params(jobs: List[TransmuxJob]) -> Tuple[Optional[np.ndarray], Optional[np.ndarray]]:
+    """``(fragment bool[n], frag_params int64[n, 4])`` of ``jobs`` (``_Columns``), ``(None, None)``
+    when no job asked for its moof boxes."""
+    asked = [i for i, j in enumerate(jobs) if j.fragment]
+    if not asked:
+        return None, None
+    params = np.tile(np.array([0, 0, -1, 0], dtype=np.int64), (len(jobs), 1))
+    params[asked] = [(jobs[i].sequence_number, jobs[i].time_base, jobs[i].time_ref, int(bool(jobs[i].anchor)))
+                     for i in asked]
+    return _mask(len(jobs), asked), params
+
+
+def _by_scheme(work: List[Tuple[Any, ...]], jobs: List[TransmuxJob]) -> List[Tuple[Any, ...]]:
+    """The work tuples of :meth:`MediaPipeline._cbc_work` with the rows of each grouped by the
+    decrypt they asked for: none, ``cbcs``, ``cenc`` (an AES-128 row asks for none)."""
+    out = []
+    for rows, buf, offs, lens, caps in work:
+        scheme = np.array([(None, "cbcs", "cenc").index(jobs[i].scheme) for i in rows.tolist()])
+        for s in np.unique(scheme).tolist():
+            m = scheme == s
+            out.append((rows, buf, offs, lens, caps) if m.all() else (rows[m], buf, offs[m], lens[m], caps[m]))
+    return out
+
+
+def _failed(error: BaseException, container: Optional[str] = None) -> Dict[str, Any]:
+    """The result of a fragment that got no row; ``container``: of a job that was set aside."""
+    return {"error": error, "status": -1, **({} if container is None else {"container": container})}
 
 
 class _Columns:
@@ -240,34 +298,29 @@ class MediaPipeline:
         jobs, self._jobs = self._jobs, []
         if not jobs:
             return None
-        mp4 = packed = None
-        if self._any_aside:  # fragmented-MP4 and packed-audio jobs take their own paths, in front of the columns
+        aside: Any = ()
+        if self._any_aside:  # fragmented-MP4 and packed-audio jobs take their own path, in front of the columns
             self._any_aside = False
-            mj = [j for j in jobs if j.mp4 is not None]
-            pj = [j for j in jobs if j.packed_audio]
-            mp4 = self._launch_mp4(mj) if mj else None
-            packed = self._launch_packed(pj) if pj else None
+            parts = [(_Mp4, [j for j in jobs if j.mp4 is not None]), (_Packed, [j for j in jobs if j.packed_audio])]
+            aside = [self._launch_aside(kind, kj) for kind, kj in parts if kj]
             jobs = [j for j in jobs if not j.aside]
             if not jobs:
-                return _Batch([], groups=[], n=0, mp4=mp4, packed=packed)
+                return _Batch([], groups=[], n=0, aside=aside)
         try:
             b = self._launch_core(self._job_columns(jobs))
         except Exception as e:  # deliver the failure to every job of the batch
-            return _Batch(jobs, groups=[], error=e, n=len(jobs), mp4=mp4, packed=packed)
+            return _Batch(jobs, groups=[], error=e, n=len(jobs), aside=aside)
         b.jobs = jobs
-        b.mp4 = mp4
-        b.packed = packed
+        b.aside = aside
         return b
 
     def complete(self, batch: Optional["_Batch"]) -> None:
         """Wait for a launched batch and run the per-fragment callbacks."""
         if batch is None:
             return
-        if batch.mp4 is not None or batch.packed is not None:
-            if batch.mp4 is not None:
-                self._complete_mp4(batch.mp4)
-            if batch.packed is not None:
-                self._complete_packed(batch.packed)
+        if batch.aside:
+            for part in batch.aside:
+                self._complete_aside(part)
             if not batch.jobs:
                 return
         if batch.error is not None:
@@ -280,8 +333,7 @@ class MediaPipeline:
             for i in np.flatnonzero(batch.expect_mask).tolist():
                 batch.jobs[i].verify.report(bool(ok[i]))
                 if not ok[i]:
-                    results[i] = {"error": ValueError("received segment failed its CRC check"), "status": -1,
-                                  "verify_failed": True}
+                    results[i] = dict(_failed(ValueError(ERR_CRC)), verify_failed=True)
         t = time.perf_counter()
         for j, r in zip(batch.jobs, results):
             j.callback(r)
@@ -333,22 +385,22 @@ class MediaPipeline:
             buf[o:o + t.numel()].copy_(t, non_blocking=True)
         return buf, offs
 
+    def _stage_jobs(self, jobs: List[TransmuxJob]) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+        """The payloads of ``jobs`` in one source buffer (:meth:`_stage`): ``(src, offs, nb)``."""
+        tensors = [_as_tensor(j.payload) for j in jobs]
+        sizes = [t.numel() for t in tensors]
+        src, src_offs = self._stage(tensors, sizes)
+        return src, np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
+
     def _job_columns(self, jobs: List[TransmuxJob]) -> _Columns:
         """The submitted jobs as columns: payloads staged into one source buffer; one key per
         stream (the usual case) is expanded once."""
         t0 = time.perf_counter()
         cuda = self.device.type == "cuda"
-        tensors = [_as_tensor(j.payload) for j in jobs]
-        sizes = [t.numel() for t in tensors]
-        src, src_offs = self._stage(tensors, sizes)
+        src, offs, nb = self._stage_jobs(jobs)
         n = len(jobs)
-        e = [i for i, j in enumerate(jobs) if j.key is not None]
-        enc = np.zeros(n, dtype=bool)
-        iv = np.zeros((n, 16), dtype=np.uint8)
+        e, enc, iv = _enc_iv(jobs)
         drk = np.zeros((n, 44), dtype=np.uint32) if cuda else None
-        if e:
-            enc[e] = True
-            iv[e] = np.frombuffer(b"".join(bytes(jobs[i].iv) for i in e), dtype=np.uint8).reshape(-1, 16)
         if e and cuda:  # (the host decrypt expands the raw keys itself)
             k0 = jobs[e[0]].key
             if all(jobs[i].key is k0 or jobs[i].key == k0 for i in e):
@@ -360,19 +412,14 @@ class MediaPipeline:
         if v:
             expect = np.full(n, -1, dtype=np.int64)
             expect[v] = [jobs[i].verify.expect & 0xFFFFFFFF for i in v]
-        cols = _Columns(src, np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64), enc, iv, drk=drk,
+        cols = _Columns(src, offs, nb, enc, iv, drk=drk,
                         keys=None if cuda else [j.key for j in jobs], expect=expect,
                         index=_mask(n, [i for i, j in enumerate(jobs) if j.index]),
                         remux=_mask(n, [i for i, j in enumerate(jobs) if j.remux]),
                         sample=_mask(n, [i for i, j in enumerate(jobs) if j.sample_key is not None]),
                         sample_keys=[j.sample_key for j in jobs], sample_ivs=[j.sample_iv for j in jobs],
                         captions=_mask(n, [i for i, j in enumerate(jobs) if j.captions]))
-        asked = [i for i, j in enumerate(jobs) if j.fragment]
-        if asked:
-            cols.fragment = _mask(n, asked)
-            cols.frag_params = np.tile(np.array([0, 0, -1, 0], dtype=np.int64), (n, 1))
-            cols.frag_params[asked] = [(jobs[i].sequence_number, jobs[i].time_base, jobs[i].time_ref,
-                                        int(bool(jobs[i].anchor))) for i in asked]
+        cols.fragment, cols.frag_params = _frag_params(jobs)
         self.timer.add("stage", time.perf_counter() - t0)
         return cols
 
@@ -425,7 +472,7 @@ class MediaPipeline:
         self.segments += n
         self.bytes_in += int(c.nb.sum())
         self.batches += 1
-        ok = ~(c.enc & ((c.nb <= 0) | (c.nb % 16 != 0)))
+        ok = _accepted(c.enc, c.nb)
         rows = np.flatnonzero(ok)
         verify: List[Any] = []
         mask = ex = None
@@ -459,43 +506,44 @@ class MediaPipeline:
         else:
             groups = self._host_groups(c, rows)
         for g in groups:
-            # the sample index of a group in which any row asked for it: one ``index_batch`` call
-            # after the group's demux on the same stream, its ``sinfo`` rows on their way to the
-            # host before the batch's event
-            if c.index is None or not c.index[g.rows].any():
-                continue
-            from ..ops import esindex as _esx
-
-            g.ix = ix = _esx.index_batch(g.res, c.nb[g.rows])
-            g.sinfo = _to_host(ix.sinfo)
-            # ... and the SAMPLE-AES decrypt of a group in which any row asked: one
-            # ``sample_decrypt_batch`` call behind the index and in front of the remux and the two
-            # configuration calls, which then read the decrypted ES; rows that did not ask are not
-            # enabled and stay as they are
-            if c.sample is not None and c.sample[g.rows].any():
-                from ..ops import sampleaes as _sa
-
-                il = g.rows.tolist()
-                g.sa = sa = _sa.sample_decrypt_batch(g.res, ix, c.nb[g.rows], [c.sample_keys[i] for i in il],
-                                                     [c.sample_ivs[i] for i in il], c.sample[g.rows].tolist())
-                g.sainfo = _to_host(sa.sainfo)
-            # ... and the caption data of a group in which any row asked: one ``caption_batch`` call
-            # behind the SAMPLE-AES step and in front of the remux, its ``ccinfo`` rows on the same
-            # way to the host; rows that did not ask are not enabled
-            if c.captions is not None and c.captions[g.rows].any():
-                from ..ops import captions as _cc
-
-                g.cc = cc = _cc.caption_batch(g.res, ix, c.nb[g.rows], enable=c.captions[g.rows].tolist())
-                g.ccinfo = _to_host(cc.ccinfo)
-            # ... and the remux of a group in which any row asked (:meth:`_launch_remux`)
-            if c.remux is not None and c.remux[g.rows].any():
-                fragment = c.fragment is not None and bool(c.fragment[g.rows].any())
-                self._launch_remux(g, c.nb[g.rows], c.frag_params[g.rows] if fragment else None)
+            self._group_steps(g, c)
         # completing the batch is the stage's only sync: one event after everything enqueued
         ev = self._event() if cuda and (groups or verify) else None
         self.timer.add("launch", time.perf_counter() - t1)
         return _Batch(None, groups=groups, event=ev, keep=keep, tag=tag, n=n, start=ev0, verify=verify or None,
                       expect_mask=mask)
+
+    def _group_steps(self, g: "_Group", c: _Columns) -> None:
+        """The steps behind a group's demux, each one call on the same stream when a row of the group
+        asked for it in ``c``, its small tables on their way to the host before the batch's event."""
+        rows = g.rows
+        if g.ix is None:
+            # the sample index (a container whose demux brings its own has it already): one
+            # ``index_batch`` call; ``sample``, ``captions`` and ``remux`` are subsets of ``index``
+            if not _any(c.index, rows):
+                return
+            from ..ops import esindex as _esx
+
+            g.ix = _esx.index_batch(g.res, c.nb[rows])
+            g.sinfo = _to_host(g.ix.sinfo)
+        ix, caps = g.ix, c.nb[rows]
+        # ... the SAMPLE-AES decrypt, in front of the captions, the remux and the two configuration
+        # calls, which then read the decrypted ES; rows that did not ask are not enabled
+        if _any(c.sample, rows):
+            from ..ops import sampleaes as _sa
+
+            il = rows.tolist()
+            g.sa = sa = _sa.sample_decrypt_batch(g.res, ix, caps, [c.sample_keys[i] for i in il],
+                                                 [c.sample_ivs[i] for i in il], c.sample[rows].tolist())
+            g.sainfo = _to_host(sa.sainfo)
+        # ... the caption data (rows that did not ask are not enabled)
+        if _any(c.captions, rows):
+            from ..ops import captions as _cc
+
+            g.cc = cc = _cc.caption_batch(g.res, ix, caps, enable=c.captions[rows].tolist())
+            g.ccinfo = _to_host(cc.ccinfo)
+        if _any(c.remux, rows):  # ... and the remux, with the moof boxes where a row asked for them
+            self._launch_remux(g, caps, c.frag_params[rows] if _any(c.fragment, rows) else None)
 
     def _launch_remux(self, g: "_Group", caps: np.ndarray, frag_params: Optional[np.ndarray]) -> None:
         """The remux of an indexed group in which a row asked for it: one ``remux_batch`` call behind
@@ -540,220 +588,78 @@ class MediaPipeline:
         g.hcfg = hcfg = _hcfg.hevc_config_batch(g.res, ix, caps)
         g.hvinfo, g.hps = _to_host(hcfg.hinfo), _to_host(hcfg.hps)
 
-    def _host_groups(self, c: _Columns, rows: np.ndarray) -> List["_Group"]:
-        """The host backend: ``ops.aes.cbc_decrypt_batch`` over the encrypted rows, then
-        ``ops.tsdemux.demux_batch`` per group, like the native call's groups."""
-        dev = self.device
+    def _cbc_work(self, c: _Columns, rows: np.ndarray) -> List[Tuple[Any, ...]]:
+        """The demux work list of the accepted ``rows`` of ``c``, ``(rows, buf, offs, lens, caps)``
+        each: the encrypted rows behind ONE ``ops.aes.cbc_decrypt_batch`` call (raw keys ``c.keys``)
+        into a freshly laid-out buffer, then the clear rows where they lie."""
         work = []
         e, cl = rows[c.enc[rows]], rows[~c.enc[rows]]
         if len(e):
             caps = c.nb[e]
             dec_offs, size = _layout(caps)
-            dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+            dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=self.device)
             out_len = _aes.cbc_decrypt_batch(c.src, c.offs[e], caps, [bytes(c.keys[i]) for i in e.tolist()], c.iv[e],
                                              dec, dec_offs)
             work.append((e, dec, dec_offs, out_len, caps))
         if len(cl):
             work.append((cl, c.src, c.offs[cl], c.nb[cl], c.nb[cl]))
+        return work
+
+    def _host_groups(self, c: _Columns, rows: np.ndarray) -> List["_Group"]:
+        """The host backend: :meth:`_cbc_work`, then ``ops.tsdemux.demux_batch`` per group, like the
+        native call's groups."""
         groups = []
-        for idx, buf, offs, lens, caps in work:
+        for idx, buf, offs, lens, caps in self._cbc_work(c, rows):
             es_offs, size = _layout(caps)
-            es = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
+            es = torch.empty(size + ALIGN, dtype=torch.uint8, device=self.device)
             res = _ts.demux_batch(buf, offs, lens, es, es_offs, caps=caps)
-            hlens = _to_host(lens) if isinstance(lens, torch.Tensor) else lens
-            groups.append(_Group(idx, res, _to_host(res.info), hlens))
+            groups.append(_Group(idx, res, hlens=_to_host(lens), hinfo=_to_host(res.info)))
         return groups
 
-    # ------------------------------------------------------------------ fragmented MP4 (docs/FMP4DEMUX.md)
-    def _launch_mp4(self, jobs: List[TransmuxJob]) -> "_Mp4Batch":
-        """Enqueue the fragmented-MP4 jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
-        rows, one ``mp4_demux_batch`` per group (the encrypted rows in the decrypt's buffer, the clear
-        ones where they lie, the ``cbcs`` and the ``cenc`` ones where they lie as a group each), one
-        ``cbcs_decrypt_batch`` / ``cenc_decrypt_batch`` behind the demux of such a group, whose views
-        then are those of the decrypted copy, and one ``caption_batch`` over a group's views when a job of it asked;
-        ``minfo``, ``info``, ``sinfo``, the ``emsg`` table and the ``cinfo`` / ``ccinfo`` rows are on
-        their way to pinned host memory in front of the event."""
-        from ..ops import mp4demux as _mp4
-
+    # ------------------------------------------------------------------ the jobs set aside
+    def _launch_aside(self, kind: Any, jobs: List[TransmuxJob]) -> "_Aside":
+        """Enqueue the jobs of one container that is not MPEG-TS (``kind``: :class:`_Mp4` or
+        :class:`_Packed`): staging, :meth:`_cbc_work`, ``kind.demux`` per work tuple, then the steps
+        of :meth:`_group_steps` that the container takes; every small table is on its way to pinned
+        host memory in front of the event.  A failure is delivered to these jobs alone.  (A receive
+        ticket, ``verify``, is not looked at here: the node's own sweep checks it later.)"""
         try:
-            dev = self.device
-            tensors = [_as_tensor(j.payload) for j in jobs]
-            sizes = [t.numel() for t in tensors]
-            src, src_offs = self._stage(tensors, sizes)
-            offs, nb = np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
-            enc = np.array([j.key is not None for j in jobs], dtype=bool)
-            ok = ~(enc & ((nb <= 0) | (nb % 16 != 0)))
-            self.segments += len(jobs)
+            src, offs, nb = self._stage_jobs(jobs)
+            n = len(jobs)
+            self.segments += n
             self.bytes_in += int(nb.sum())
-            work = []
-            e, cl = np.flatnonzero(enc & ok), np.flatnonzero(~enc)
-            if len(e):
-                caps = nb[e]
-                dec_offs, size = _layout(caps)
-                dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
-                il = e.tolist()
-                out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
-                                                 [bytes(jobs[i].iv) for i in il], dec, dec_offs)
-                work.append((e, dec, dec_offs, out_len, caps))
-            scheme = np.array([{"cbcs": 1, "cenc": 2}.get(j.scheme, 0) for j in jobs], dtype=np.int64)
-            for rows in (cl[scheme[cl] == 0], cl[scheme[cl] == 1], cl[scheme[cl] == 2]):
-                if len(rows):
-                    work.append((rows, src, offs[rows], nb[rows], nb[rows]))
+            _, enc, iv = _enc_iv(jobs)
+            c = _Columns(src, offs, nb, enc, iv, keys=[j.key for j in jobs])
+            if kind.captions:
+                c.captions = _mask(n, [i for i, j in enumerate(jobs) if j.captions])
+            if kind.remux:
+                c.remux = _mask(n, [i for i, j in enumerate(jobs) if j.remux])
+                c.fragment, c.frag_params = _frag_params(jobs)
+            ok = _accepted(enc, nb)
             groups = []
-            for idx, buf, o, lens, caps in work:
-                il = idx.tolist()
-                md = _mp4.mp4_demux_batch(buf, o, lens, [jobs[i].mp4 for i in il], caps=caps)
-                cb = None
-                if scheme[il[0]]:  # out of place: buf may be the arena that peers are served from
-                    if scheme[il[0]] == 1:
-                        from ..ops.cbcs import cbcs_decrypt_batch as decrypt
-                    else:
-                        from ..ops.cenc import cenc_decrypt_batch as decrypt
-                    cb = decrypt(md, [jobs[i].mp4 for i in il], [jobs[i].sample_key for i in il],
-                                 [jobs[i].sample_iv for i in il])
-                    md = cb.md
-                g = _Mp4Group(idx, md, _to_host(md.minfo), _to_host(md.info), _to_host(md.sinfo), _to_host(md.emsg),
-                              _to_host(lens) if isinstance(lens, torch.Tensor) else lens)
-                if cb is not None:
-                    g.cbinfo = _to_host(cb.cinfo)
-                    g.scheme = "cbcs" if scheme[il[0]] == 1 else "cenc"
-                asked = [bool(jobs[i].captions) for i in il]
-                if any(asked):
-                    from ..ops import captions as _cc
-
-                    g.cc = _cc.caption_batch(md.as_demux(), md.as_index(), caps, enable=asked)
-                    g.ccinfo = _to_host(g.cc.ccinfo)
+            for work in _by_scheme(self._cbc_work(c, np.flatnonzero(ok)), jobs):
+                g = kind.demux(jobs, *work)
+                self._group_steps(g, c)
                 groups.append(g)
-            ev = self._event() if dev.type == "cuda" and groups else None
-            return _Mp4Batch(jobs, groups, ev, None, np.flatnonzero(~ok))
-        except Exception as e:  # deliver the failure to every fragmented-MP4 job of the batch
-            return _Mp4Batch(jobs, [], None, e, np.zeros(0, dtype=np.int64))
+            ev = self._event() if self.device.type == "cuda" and groups else None
+            return _Aside(kind, jobs, groups, ev, None, np.flatnonzero(~ok))
+        except Exception as e:  # deliver the failure to every job of this container in the batch
+            return _Aside(kind, jobs, [], None, e, np.zeros(0, dtype=np.int64))
 
-    def _complete_mp4(self, b: "_Mp4Batch") -> None:
-        """Wait for the fragmented-MP4 jobs of a batch and run their callbacks."""
-        from ..ops.cbcs import segment_view as cbcs_view
-        from ..ops.cenc import segment_view as cenc_view
-        from ..ops.mp4demux import EMSG, MINFO
-
+    def _complete_aside(self, b: "_Aside") -> None:
+        """Wait for the jobs of a batch that were set aside as one container and run their callbacks."""
+        name = b.kind.name
         if b.error is not None:
             for j in b.jobs:
-                j.callback({"error": b.error, "status": -1, "container": "mp4"})
+                j.callback(_failed(b.error, name))
             return
-        if b.event is not None:
-            b.event.synchronize()
-            self._free_events.append(b.event)
+        self._wait(b)
         results: List[Any] = [None] * len(b.jobs)
         for i in b.rejected.tolist():
-            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1,
-                          "container": "mp4"}
+            results[i] = _failed(ValueError(ERR_BLOCKS), name)
         for g in b.groups:
-            md = g.md
-            minfo, info, sinfo, emsg, hlens = (_np(x) for x in (g.minfo, g.info, g.sinfo, g.emsg, g.hlens))
-            for k, i in enumerate(g.rows.tolist()):
-                job, row, plain = b.jobs[i], minfo[k].tolist(), int(hlens[k])
-                r = {"status": row[MINFO["status"]], "info": {n: row[s] for n, s in MINFO.items()},
-                     "plain_bytes": plain, "container": "mp4", "init": job.mp4, "mp4": md, "index": k,
-                     "video": Mp4TrackView(md, k, 0, row, info[k], job.mp4),
-                     "audio": Mp4TrackView(md, k, 1, row, info[k], job.mp4),
-                     "data": md.buf.narrow(0, int(md.offs[k]), max(plain, 0)),
-                     "emsg": [{n: int(er[s]) for n, s in EMSG.items()} for er in emsg[k] if er[EMSG["offset"]] >= 0]}
-                if plain < 0:
-                    r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
-                if job.index:
-                    r["samples"] = Samples(sinfo[k].tolist(), md.as_index(), k)
-                if g.cc is not None and job.captions:
-                    r["captions"] = CaptionData(g, k)
-                if g.cbinfo is not None:
-                    view = cbcs_view if g.scheme == "cbcs" else cenc_view
-                    r[g.scheme] = MappingProxyType(view(_np(g.cbinfo)[k]))
-                results[i] = r
-        for j, r in zip(b.jobs, results):
-            j.callback(r)
-
-    # ------------------------------------------------------------------ packed audio (docs/PACKEDAUDIO.md)
-    def _launch_packed(self, jobs: List[TransmuxJob]) -> "_PackedBatch":
-        """Enqueue the packed-audio jobs of a batch: staging, ``cbc_decrypt_batch`` for the AES-128
-        rows, one ``packed_audio_batch`` per group (the encrypted rows in the decrypt's buffer, the
-        clear ones where they lie), and for a group in which a job asked for it the remux, fragment and
-        configuration calls of :meth:`_launch_remux` over its views; ``info``, ``sinfo``, ``painfo``
-        and the remux tables are on their way to pinned host memory in front of the event."""
-        from ..ops import packedaudio as _pa
-
-        try:
-            dev = self.device
-            tensors = [_as_tensor(j.payload) for j in jobs]
-            sizes = [t.numel() for t in tensors]
-            src, src_offs = self._stage(tensors, sizes)
-            offs, nb = np.asarray(src_offs, dtype=np.int64), np.asarray(sizes, dtype=np.int64)
-            enc = np.array([j.key is not None for j in jobs], dtype=bool)
-            ok = ~(enc & ((nb <= 0) | (nb % 16 != 0)))
-            self.segments += len(jobs)
-            self.bytes_in += int(nb.sum())
-            work = []
-            e, cl = np.flatnonzero(enc & ok), np.flatnonzero(~enc)
-            if len(e):
-                caps = nb[e]
-                dec_offs, size = _layout(caps)
-                dec = torch.empty(size + ALIGN, dtype=torch.uint8, device=dev)
-                il = e.tolist()
-                out_len = _aes.cbc_decrypt_batch(src, offs[e], caps, [bytes(jobs[i].key) for i in il],
-                                                 [bytes(jobs[i].iv) for i in il], dec, dec_offs)
-                work.append((e, dec, dec_offs, out_len, caps))
-            if len(cl):
-                work.append((cl, src, offs[cl], nb[cl], nb[cl]))
-            groups = []
-            for idx, buf, o, lens, caps in work:
-                il = idx.tolist()
-                pa = _pa.packed_audio_batch(buf, o, lens, caps=caps)
-                hlens = _to_host(lens) if isinstance(lens, torch.Tensor) else lens
-                g = _Group(idx, pa.as_demux(), _to_host(pa.info), hlens, ix=pa.as_index(), sinfo=_to_host(pa.sinfo),
-                           painfo=_to_host(pa.painfo))
-                if any(jobs[i].remux for i in il):
-                    fp = None
-                    if any(jobs[i].fragment for i in il):
-                        fp = np.array([(j.sequence_number, j.time_base, j.time_ref, j.anchor) if j.fragment
-                                       else (0, 0, -1, 0) for j in (jobs[i] for i in il)], dtype=np.int64)
-                    self._launch_remux(g, caps, fp)
-                groups.append(g)
-            ev = self._event() if dev.type == "cuda" and groups else None
-            return _PackedBatch(jobs, groups, ev, None, np.flatnonzero(~ok))
-        except Exception as e:  # deliver the failure to every packed-audio job of the batch
-            return _PackedBatch(jobs, [], None, e, np.zeros(0, dtype=np.int64))
-
-    def _complete_packed(self, b: "_PackedBatch") -> None:
-        """Wait for the packed-audio jobs of a batch and run their callbacks: results of the MPEG-TS
-        shape, with ``container`` and ``packed_audio``."""
-        from ..ops.packedaudio import FATAL, PAINFO, PASTATUS
-
-        if b.error is not None:
-            for j in b.jobs:
-                j.callback({"error": b.error, "status": -1, "container": "aac"})
-            return
-        if b.event is not None:
-            b.event.synchronize()
-            self._free_events.append(b.event)
-        results: List[Any] = [None] * len(b.jobs)
-        for i in b.rejected.tolist():
-            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1,
-                          "container": "aac"}
-        for g in b.groups:
-            res = g.res
-            rl, srows, prows = _np(g.hinfo).tolist(), _np(g.sinfo).tolist(), _np(g.painfo).tolist()
-            hlens = _np(g.hlens)
-            for k, (i, base) in enumerate(zip(g.rows.tolist(), res.es_offs.tolist())):
-                job, row, plain, pa = b.jobs[i], rl[k], int(hlens[k]), prows[k]
-                r = _Result(status=row[0], info=InfoRow(row), plain_bytes=plain, demux=res, index=k, container="aac",
-                            packed_audio=MappingProxyType({name: pa[slot] for name, slot in PAINFO.items()}))
-                r._es = (res.es, base, row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
-                if plain < 0:
-                    r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
-                elif pa[PAINFO["status"]] & FATAL:
-                    names = [name for name, bit in PASTATUS.items() if pa[PAINFO["status"]] & FATAL & bit]
-                    r["error"] = ValueError("packed audio: " + ", ".join(names))
-                if job.index:
-                    r["samples"] = Samples(srows[k], g.ix, k)
-                if g.rx is not None and job.remux:
-                    r["fmp4"] = Fmp4(g, k, srows[k], g.fr is not None and job.fragment)
+            for i, r in zip(g.rows.tolist(), b.kind.rows(g, b.jobs)):
+                r["container"] = name
                 results[i] = r
         for j, r in zip(b.jobs, results):
             j.callback(r)
@@ -811,37 +717,142 @@ class MediaPipeline:
         rl, pl = rows.tolist(), plain.tolist()
         results: List[Any] = [None] * b.n
         for i in np.flatnonzero(~has).tolist():  # rejected before launch
-            results[i] = {"error": ValueError("encrypted payload is not a multiple of 16 bytes"), "status": -1}
+            results[i] = _failed(ValueError(ERR_BLOCKS))
         for g in b.groups:
             res = g.res
             es = res.es
             il = g.rows.tolist()
             for k, (i, base) in enumerate(zip(il, res.es_offs.tolist())):
-                row = rl[i]
-                # ES views (per class, at the row's offsets from base) are built on first access: the
-                # buffer path only needs their byte counts, which the info row holds
-                r = _Result(status=row[0], info=InfoRow(row), plain_bytes=pl[i], demux=res, index=k)
-                r._es = (es, base, row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
-                if pl[i] < 0:
-                    r["error"] = ValueError("decryption failed (bad PKCS#7 padding)")
-                results[i] = r
-            if g.ix is not None:  # the jobs of this group that asked for the sample index
+                results[i] = _ts_result(res, es, k, rl[i], base, pl[i])
+            if g.ix is not None:  # a job of this group asked for the sample index
                 srows = _np(g.sinfo).tolist()
                 for k, i in enumerate(il):
-                    if b.jobs[i].index:
-                        results[i]["samples"] = Samples(srows[k], g.ix, k)
-                    if g.rx is not None and b.jobs[i].remux:  # ... and those that asked for the remux
-                        results[i]["fmp4"] = Fmp4(g, k, srows[k], g.fr is not None and b.jobs[i].fragment)
-                    if g.sa is not None and b.jobs[i].sample_key is not None:  # ... and for the SAMPLE-AES decrypt
-                        from types import MappingProxyType
-
-                        from ..ops.sampleaes import segment_view
-
-                        results[i]["sample_aes"] = MappingProxyType(segment_view(_np(g.sainfo)[k]))
-                    if g.cc is not None and b.jobs[i].captions:  # ... and for the caption data
-                        results[i]["captions"] = CaptionData(g, k)
+                    _attach(results[i], g, k, b.jobs[i], srows[k])
         self.timer.add("results", time.perf_counter() - t4)
         return results
+
+
+def _ts_result(res, es, k, row, base, plain) -> "_Result":
+    """The MPEG-TS shaped result of row ``k`` of the demux ``res`` (``es`` its ES buffer): ``row`` its
+    info row, ``base`` its ES offset, ``plain`` its plaintext length (negative: the decrypt found bad
+    padding).  The ES views (per class, at the row's offsets from ``base``) are built on first
+    access: the buffer path only needs their byte counts, which the info row holds.  (Called per
+    row of every batch: no annotations for the compiled module to check.)"""
+    r = _Result(status=row[0], info=InfoRow(row), plain_bytes=plain, demux=res, index=k)
+    r._es = (es, base, row[_VB], row[_AB], row[_IB], row[_AO], row[_IO])
+    if plain < 0:
+        r["error"] = ValueError(ERR_PADDING)
+    return r
+
+
+def _attach(r: Any, g: "_Group", k: int, job: TransmuxJob, srow: List[int]) -> None:
+    """What hangs off the result of row ``k`` of the indexed group ``g``: the sample index, the remux,
+    the SAMPLE-AES decrypt and the caption data, each where the group ran it and ``job`` asked."""
+    if job.index:
+        r["samples"] = Samples(srow, g.ix, k)
+    if g.rx is not None and job.remux:
+        r["fmp4"] = Fmp4(g, k, srow, g.fr is not None and job.fragment)
+    if g.sa is not None and job.sample_key is not None:
+        from ..ops.sampleaes import segment_view
+
+        r["sample_aes"] = MappingProxyType(segment_view(_np(g.sainfo)[k]))
+    if g.cc is not None and job.captions:
+        r["captions"] = CaptionData(g, k)
+
+
+class _Mp4:
+    """What tells a container that is set aside apart (:meth:`MediaPipeline._launch_aside`): ``name``
+    (the results' ``container``), the steps of ``_group_steps`` that its groups take (``captions``;
+    ``remux`` with fragment and configuration), ``demux`` (a work tuple into a :class:`_Group` that
+    brings its own index) and ``rows`` (the results of a finished group, in its order).
+
+    Fragmented MP4 (docs/FMP4DEMUX.md): one ``mp4_demux_batch`` per group and, behind the demux of a
+    ``cbcs`` or ``cenc`` group, one ``cbcs_decrypt_batch`` / ``cenc_decrypt_batch`` (docs/CBCS.md,
+    docs/CENC.md), whose views then are those of the decrypted copy."""
+
+    name, captions, remux = "mp4", True, False
+
+    @staticmethod
+    def demux(jobs, rows, buf, offs, lens, caps):
+        from ..ops import mp4demux as _mp4
+
+        il = rows.tolist()
+        inits, scheme = [jobs[i].mp4 for i in il], jobs[il[0]].scheme
+        md = _mp4.mp4_demux_batch(buf, offs, lens, inits, caps=caps)
+        cb = None
+        if scheme:  # out of place: buf may be the arena that peers are served from
+            if scheme == "cbcs":
+                from ..ops.cbcs import cbcs_decrypt_batch as decrypt
+            else:
+                from ..ops.cenc import cenc_decrypt_batch as decrypt
+            cb = decrypt(md, inits, [jobs[i].sample_key for i in il], [jobs[i].sample_iv for i in il])
+            md = cb.md
+        g = _Group(rows, md.as_demux(), md=md, minfo=_to_host(md.minfo), hinfo=_to_host(md.info), ix=md.as_index(),
+                   sinfo=_to_host(md.sinfo), emsg=_to_host(md.emsg), hlens=_to_host(lens))
+        if cb is not None:
+            g.cbinfo, g.scheme = _to_host(cb.cinfo), scheme
+        return g
+
+    @staticmethod
+    def rows(g, jobs):
+        from ..ops.cbcs import segment_view as cbcs_view
+        from ..ops.cenc import segment_view as cenc_view
+        from ..ops.mp4demux import EMSG, MINFO
+
+        md = g.md
+        minfo, info, sinfo, emsg, hlens = (_np(x) for x in (g.minfo, g.hinfo, g.sinfo, g.emsg, g.hlens))
+        for k, i in enumerate(g.rows.tolist()):
+            job, row, plain = jobs[i], minfo[k].tolist(), int(hlens[k])
+            r = {"status": row[MINFO["status"]], "info": {n: row[s] for n, s in MINFO.items()},
+                 "plain_bytes": plain, "init": job.mp4, "mp4": md, "index": k,
+                 "video": Mp4TrackView(md, k, 0, row, info[k], job.mp4),
+                 "audio": Mp4TrackView(md, k, 1, row, info[k], job.mp4),
+                 "data": md.buf.narrow(0, int(md.offs[k]), max(plain, 0)),
+                 "emsg": [{n: int(er[s]) for n, s in EMSG.items()} for er in emsg[k] if er[EMSG["offset"]] >= 0]}
+            if plain < 0:
+                r["error"] = ValueError(ERR_PADDING)
+            _attach(r, g, k, job, sinfo[k].tolist())
+            if g.cbinfo is not None:
+                view = cbcs_view if g.scheme == "cbcs" else cenc_view
+                r[g.scheme] = MappingProxyType(view(_np(g.cbinfo)[k]))
+            yield r
+
+
+class _Packed:
+    """Packed audio (docs/PACKEDAUDIO.md): one ``packed_audio_batch`` per group, whose views stand in
+    for the demux and the index, the remux of :meth:`MediaPipeline._launch_remux` over them, and
+    results of the MPEG-TS shape with ``packed_audio``."""
+
+    name, captions, remux = "aac", False, True
+
+    @staticmethod
+    def demux(jobs, rows, buf, offs, lens, caps):
+        from ..ops import packedaudio as _pa
+
+        pa = _pa.packed_audio_batch(buf, offs, lens, caps=caps)
+        return _Group(rows, pa.as_demux(), hlens=_to_host(lens), hinfo=_to_host(pa.info), ix=pa.as_index(),
+                      sinfo=_to_host(pa.sinfo), painfo=_to_host(pa.painfo))
+
+    @staticmethod
+    def rows(g, jobs):
+        from ..ops.packedaudio import FATAL, PAINFO, PASTATUS
+
+        res = g.res
+        rl, srows, prows, hlens = _np(g.hinfo).tolist(), _np(g.sinfo).tolist(), _np(g.painfo).tolist(), _np(g.hlens)
+        for k, (i, base) in enumerate(zip(g.rows.tolist(), res.es_offs.tolist())):
+            pa = prows[k]
+            r = _ts_result(res, res.es, k, rl[k], base, int(hlens[k]))
+            r["packed_audio"] = MappingProxyType({name: pa[slot] for name, slot in PAINFO.items()})
+            if "error" not in r and pa[PAINFO["status"]] & FATAL:
+                names = [name for name, bit in PASTATUS.items() if pa[PAINFO["status"]] & FATAL & bit]
+                r["error"] = ValueError("packed audio: " + ", ".join(names))
+            _attach(r, g, k, jobs[i], srows[k])
+            yield r
+
+
+def _any(mask: Optional[np.ndarray], rows: np.ndarray) -> bool:
+    """A row of ``rows`` is set in ``mask`` (``None``: nobody asked)."""
+    return mask is not None and bool(mask[rows].any())
 
 
 def _mask(n: int, idx) -> Optional[np.ndarray]:
@@ -1183,8 +1194,6 @@ class Fmp4(_View):
             return self._finfo("time_base")
         if name == "config":
             if self._config is None:
-                from types import MappingProxyType
-
                 from ..ops.codecconfig import segment_view
 
                 g, k = self._g, self._k
@@ -1192,8 +1201,6 @@ class Fmp4(_View):
             return self._config
         if name == "hevc":
             if self._hevc is None:
-                from types import MappingProxyType
-
                 from ..ops.hevcconfig import segment_view
 
                 g, k = self._g, self._k
@@ -1254,32 +1261,6 @@ class Mp4TrackView(_View):
 
 
 @dataclass(eq=False)
-class _Mp4Group:
-    """One demux group of the fragmented-MP4 jobs of a batch (its encrypted rows, its clear ones or
-    its ``cbcs`` ones)."""
-    rows: np.ndarray  # rows of the batch's fragmented-MP4 jobs, in the group's order
-    md: Any  # the group's Mp4Demux, on the device; of a cbcs group: over the decrypted copy
-    minfo: Any  # its minfo, info, sinfo rows, emsg table and ...
-    info: Any
-    sinfo: Any
-    emsg: Any
-    hlens: Any  # ... plaintext lengths on the host (pinned: readable after the batch's event)
-    cc: Any = None  # Captions, when a job of the group asked for it, with ...
-    ccinfo: Any = None  # ... its ccinfo rows on the host
-    cbinfo: Any = None  # the cinfo rows of a cbcs or cenc group on the host
-    scheme: str = ""    # "cbcs" / "cenc" where cbinfo is set
-
-
-@dataclass(eq=False)
-class _Mp4Batch:
-    jobs: List[TransmuxJob]
-    groups: List[_Mp4Group]
-    event: Any
-    error: Optional[BaseException]
-    rejected: Any  # jobs whose encrypted payload is not whole AES blocks
-
-
-@dataclass(eq=False)
 class _Group:
     """One demux group of a batch (its encrypted rows, or its clear ones) and what was run on it."""
     rows: np.ndarray  # rows of the batch, in the group's order
@@ -1305,15 +1286,23 @@ class _Group:
     hvinfo: Any = None  # ... its two tensors on the host
     hps: Any = None
     painfo: Any = None  # the painfo rows of a packed-audio group on the host
+    md: Any = None  # the Mp4Demux of a fragmented-MP4 group (of a cbcs or cenc group: over the decrypted copy) ...
+    minfo: Any = None  # ... with its minfo rows and emsg table on the host; res / ix are its views
+    emsg: Any = None
+    cbinfo: Any = None  # the cinfo rows of a cbcs or cenc group on the host
+    scheme: str = ""    # "cbcs" / "cenc" where cbinfo is set
 
 
 @dataclass(eq=False)
-class _PackedBatch:
+class _Aside:
+    """The jobs of a batch that were set aside as one container, and their launch."""
+    kind: Any  # _Mp4 / _Packed
     jobs: List[TransmuxJob]
-    groups: List[_Group]  # res / ix are the views of the group's PackedAudio
+    groups: List[_Group]
     event: Any
     error: Optional[BaseException]
     rejected: Any  # jobs whose encrypted payload is not whole AES blocks
+    start: Any = None  # (no timing event: a batch's device time is its MPEG-TS core's)
 
 
 @dataclass(eq=False)
@@ -1328,8 +1317,7 @@ class _Batch:
     start: Any = None  # timing event recorded before the batch's first launch
     verify: Any = None  # [(fragment indices, ok flags (pinned uint8 / bool))] of expect-CRC checks
     expect_mask: Any = None  # bool[n]: fragments that asked for a CRC check (unchecked ones fail)
-    mp4: Any = None  # _Mp4Batch: the batch's fragmented-MP4 jobs, which took their own path
-    packed: Any = None  # _PackedBatch: the batch's packed-audio jobs, which took theirs
+    aside: Any = ()  # [_Aside]: the batch's fragmented-MP4 jobs, then its packed-audio jobs, which took their own path
 
     # the groups as the benchmark's output dump reads them: derived, nothing is stored twice
     @property
