@@ -201,7 +201,8 @@ void remux(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t tot
 // fparams row per segment (the Python wrapper has checked the regions against out and against each
 // other; the kernel leaves a row alone that does not lie inside out) and `out` as remux left it.
 void fragment_moof(Tensor rinfo, Tensor vsamples, Tensor asamples, Tensor sinfo, Tensor fparams, int64_t max_pes,
-                   int64_t max_aframes, int64_t headroom, int64_t audio_gap, Tensor out, Tensor finfo) {
+                   int64_t max_aframes, int64_t headroom, int64_t audio_gap, Tensor out, Tensor finfo,
+                   c10::optional<Tensor> mpainfo) {
   const int64_t B = fparams.numel() / es_::kFparamWords;
   TORCH_CHECK(max_pes > 0 && max_aframes > 0 && max_pes <= 0x7fffffff / 16 && max_aframes <= 0x7fffffff / 16,
               "fragment_moof: max_pes / max_aframes out of range");
@@ -218,10 +219,46 @@ void fragment_moof(Tensor rinfo, Tensor vsamples, Tensor asamples, Tensor sinfo,
       .max_pes = max_pes, .max_aframes = max_aframes, .headroom = headroom, .audio_gap = audio_gap,
       .out = check<uint8_t>(out, "out"), .out_numel = out.numel(),
       .finfo = check<int64_t>(finfo, "finfo", B * es_::kFinfoWords),
+      .mpainfo = mpainfo.has_value() ? check<int64_t>(*mpainfo, "mpainfo", B * es_::kMpainfoWords) : nullptr,
       .nseg = static_cast<int>(B), .stream = stream()};
   same_device(out, {rinfo, vsamples, asamples, sinfo, fparams, finfo});
+  if (mpainfo.has_value()) same_device(out, {*mpainfo});
   aligned16({{out, "out"}});
   hip_ok(D::launch_fragment_moof(a), "fragment_moof launch");
+}
+
+// MPEG audio of a demuxed and remuxed batch (mpeg_audio.hip): ts_demux's outputs, per segment the
+// bytes of its output region (what remux was sized with; the Python wrapper has checked the regions
+// against out), remux's asamples, rinfo and out, which are rewritten for a segment with an MPEG
+// audio config; tile_prefix counts ceil(region / mpeg_audio_tile_bytes()).
+void mpeg_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
+                int64_t max_pes, Tensor region, int64_t max_aframes, Tensor scratch, Tensor mframes, Tensor mpainfo,
+                Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff / 4 && max_aframes > 0 && total_tiles >= 0,
+              "mpeg_audio: max_pes / max_aframes / total_tiles out of range");
+  const D::MpegAudioArgs a{
+      .b = {.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
+            .es_off = check<int64_t>(es_off, "es_off"),
+            .cap = check<int64_t>(cap, "cap", B),
+            .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
+            .nseg = static_cast<int>(B), .total_tiles = total_tiles,
+            .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+            .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+            .max_pes = max_pes, .max_nal = 0, .ix = {nullptr, nullptr, nullptr, nullptr}, .stream = stream()},
+      .region = check<int64_t>(region, "region", B),
+      .max_aframes = max_aframes,
+      .scratch = check<int32_t>(scratch, "scratch", es_::mpa_scratch(B, max_pes).end),
+      .t = {check<int32_t>(mframes, "mframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+            check<int64_t>(mpainfo, "mpainfo", B * es_::kMpainfoWords),
+            check<int32_t>(asamples, "asamples", hlsp2p::table_words(B, max_aframes, es_::kAsampleWords)),
+            check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
+      .out = check<uint8_t>(out, "out"),
+      .out_off = check<int64_t>(out_off, "out_off", B)};
+  same_device(es, {es_off, cap, tile_prefix, info, pes, region, scratch, mframes, mpainfo, asamples, rinfo, out, out_off});
+  aligned16({{es, "es"}, {out, "out"}});
+  TORCH_CHECK(es.data_ptr() != out.data_ptr(), "mpeg_audio cannot run in place");
+  hip_ok(D::launch_mpeg_audio(a), "mpeg_audio launch");
 }
 
 // Codec configuration of a demuxed and indexed batch (codec_config.hip): the inputs of es_index
@@ -576,7 +613,10 @@ TORCH_LIBRARY(hlsp2p, m) {
         "Tensor(a!) scratch, Tensor(b!) vsamples, Tensor(c!) asamples, Tensor(d!) rinfo, Tensor(e!) out, "
         "Tensor out_off, int audio_gap=0) -> ()");
   m.def("fragment_moof(Tensor rinfo, Tensor vsamples, Tensor asamples, Tensor sinfo, Tensor fparams, int max_pes, "
-        "int max_aframes, int headroom, int audio_gap, Tensor(a!) out, Tensor(b!) finfo) -> ()");
+        "int max_aframes, int headroom, int audio_gap, Tensor(a!) out, Tensor(b!) finfo, Tensor? mpainfo=None) -> ()");
+  m.def("mpeg_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
+        "int max_pes, Tensor region, int max_aframes, Tensor(a!) scratch, Tensor(b!) mframes, Tensor(c!) mpainfo, "
+        "Tensor(d!) asamples, Tensor(e!) rinfo, Tensor(f!) out, Tensor out_off) -> ()");
   m.def("codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
   m.def("hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
@@ -613,6 +653,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("es_index", &es_index);
   m.impl("remux", &remux);
   m.impl("fragment_moof", &fragment_moof);
+  m.impl("mpeg_audio", &mpeg_audio);
   m.impl("codec_config", &codec_config);
   m.impl("hevc_config", &hevc_config);
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
@@ -658,7 +699,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("remux_scratch_words", [](int64_t nseg, int64_t max_nal, int64_t max_aframes) {
     return es_::remux_scratch(nseg, max_nal, max_aframes).end;
   }, py::arg("nseg"), py::arg("max_nal"), py::arg("max_aframes"));
-  m.def("fragment_moof", &fragment_moof);
+  m.def("fragment_moof", &fragment_moof, py::arg("rinfo"), py::arg("vsamples"), py::arg("asamples"), py::arg("sinfo"),
+        py::arg("fparams"), py::arg("max_pes"), py::arg("max_aframes"), py::arg("headroom"), py::arg("audio_gap"),
+        py::arg("out"), py::arg("finfo"), py::arg("mpainfo") = py::none());
+  m.def("mpeg_audio", &mpeg_audio);
+  m.def("mpeg_audio_tile_bytes", &D::mpeg_audio_tile_bytes);
+  m.def("mpa_scratch_words", [](int64_t nseg, int64_t max_pes) { return es_::mpa_scratch(nseg, max_pes).end; },
+        py::arg("nseg"), py::arg("max_pes"));
   m.def("codec_config", &codec_config);
   m.def("hevc_config", &hevc_config);
   m.def("sample_aes_decrypt", &sample_aes_decrypt);

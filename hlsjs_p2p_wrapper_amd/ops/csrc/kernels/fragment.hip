@@ -1,7 +1,8 @@
 // The moof boxes of remuxed segments (docs/FRAGMENT.md) — CDNA4 / gfx950.
 //
 // Input: what remux.hip leaves in HBM (rinfo, vsamples, asamples), the index's sinfo row for the
-// audio sample rate, and one fparams row per segment from the host (where the segment's region
+// audio sample rate (or, with a mpainfo row that has a config, that row's rate and frame:
+// docs/MPEGAUDIO.md), and one fparams row per segment from the host (where the segment's region
 // lies, the mfhd sequence number, the time base, the reference time, the anchor flag).  Output per
 // segment, identical to the host implementation runtime/fragment.cpp fragment_segment:
 //   out:   the video moof, right-aligned so that it ends where the video mdat starts (out_off),
@@ -41,7 +42,8 @@ __device__ __forceinline__ uint32_t fr_be32(int32_t x) { return fr_be32(static_c
 __global__ __launch_bounds__(kFrThreads) void fragment_moof_kernel(
     const int64_t* __restrict__ rinfo, const int32_t* __restrict__ vs_all, const int32_t* __restrict__ as_all,
     const int64_t* __restrict__ sinfo, const int64_t* __restrict__ fparams, int64_t max_pes, int64_t max_aframes,
-    int64_t headroom, int64_t audio_gap, uint8_t* __restrict__ out, int64_t out_numel, int64_t* __restrict__ finfo) {
+    int64_t headroom, int64_t audio_gap, uint8_t* __restrict__ out, int64_t out_numel, int64_t* __restrict__ finfo,
+    const int64_t* __restrict__ mpainfo) {
   __shared__ int s_cnt[kFrWaves];
   const int seg = blockIdx.x;
   const int tid = threadIdx.x;
@@ -68,8 +70,9 @@ __global__ __launch_bounds__(kFrThreads) void fragment_moof_kernel(
 #pragma unroll
   for (int w = 0; w < kFrWaves; ++w) n += s_cnt[w];
 
-  const es::FragTimes ft = es::frag_times(m, ri[es::kVideoBaseDts], ri[es::kAudioBasePts],
-                                          sinfo[static_cast<int64_t>(seg) * es::kSinfoWords + es::kAudioSampleRate],
+  const es::FragAudio fa = es::frag_audio(sinfo[static_cast<int64_t>(seg) * es::kSinfoWords + es::kAudioSampleRate],
+                                          mpainfo ? mpainfo + static_cast<int64_t>(seg) * es::kMpainfoWords : nullptr);
+  const es::FragTimes ft = es::frag_times(m, ri[es::kVideoBaseDts], ri[es::kAudioBasePts], fa.rate,
                                           fp[es::kFpTimeBase], fp[es::kFpTimeRef], fp[es::kFpAnchor] != 0);
   const uint32_t seq = static_cast<uint32_t>(fp[es::kFpSequence]);
   const int64_t vbytes = es::moof_video_bytes(m), abytes = es::moof_audio_bytes(n);
@@ -101,7 +104,7 @@ __global__ __launch_bounds__(kFrThreads) void fragment_moof_kernel(
   } else if (tid >= kFrAudioLane0 && tid < kFrAudioLane0 + es::kMoofAudioHead / 4) {
     const int i = tid - kFrAudioLane0;
     *reinterpret_cast<uint32_t*>(aend - abytes + 4 * i) =
-        fr_be32(es::moof_audio_word(i, static_cast<uint32_t>(n), seq, static_cast<uint64_t>(ft.audio_tfdt)));
+        fr_be32(es::moof_audio_word(i, static_cast<uint32_t>(n), seq, static_cast<uint64_t>(ft.audio_tfdt), fa.duration));
   } else if (tid == 2 * kFrAudioLane0) {
     int64_t* fi = finfo + static_cast<int64_t>(seg) * es::kFinfoWords;
     fi[es::kFStatus] = ft.status;
@@ -118,7 +121,8 @@ __global__ __launch_bounds__(kFrThreads) void fragment_moof_kernel(
 hipError_t launch_fragment_moof(const FragmentArgs& a) {
   if (a.nseg <= 0) return hipSuccess;
   hipLaunchKernelGGL(fragment_moof_kernel, dim3(a.nseg), dim3(kFrThreads), 0, a.stream, a.rinfo, a.vsamples, a.asamples,
-                     a.sinfo, a.fparams, a.max_pes, a.max_aframes, a.headroom, a.audio_gap, a.out, a.out_numel, a.finfo);
+                     a.sinfo, a.fparams, a.max_pes, a.max_aframes, a.headroom, a.audio_gap, a.out, a.out_numel, a.finfo,
+                     a.mpainfo);
   return hipGetLastError();
 }
 

@@ -127,6 +127,20 @@ struct RemuxArgs {
 int remux_tile_bytes();
 hipError_t launch_remux(const RemuxArgs& a);
 
+// mpeg_audio.hip: the MPEG audio frames of every segment of a remuxed batch (docs/MPEGAUDIO.md),
+// behind launch_remux on the same out, asamples and rinfo.
+struct MpegAudioArgs {
+  EsBatch b;              // tiles of `region`; ix is not used (all null), max_nal 0
+  const int64_t* region;  // [nseg] bytes of each output region, the audio gap included: what launch_remux was given
+  int64_t max_aframes;
+  int32_t* scratch;  // es::mpa_scratch(nseg, max_pes)
+  es::MpaTables t;   // asamples and rinfo are launch_remux's
+  uint8_t* out;
+  const int64_t* out_off;
+};
+int mpeg_audio_tile_bytes();
+hipError_t launch_mpeg_audio(const MpegAudioArgs& a);
+
 // fragment.hip: the two moof boxes of every segment of a remuxed batch (docs/FRAGMENT.md), written
 // into the room launch_remux's caller left: headroom bytes in front of each region, audio_gap in
 // front of each audio box.  One workgroup per segment; a segment whose fparams row does not lie
@@ -143,6 +157,7 @@ struct FragmentArgs {
   uint8_t* out;       // 16-byte aligned
   int64_t out_numel;
   int64_t* finfo;  // nseg x es::kFinfoWords
+  const int64_t* mpainfo = nullptr;  // nseg x es::kMpainfoWords, launch_mpeg_audio's: frame and rate of an MPEG audio track
   int nseg;
   hipStream_t stream;
 };

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <map>
+#include <optional>
 #include <sstream>
 #include <stdexcept>
 #include <thread>
@@ -30,6 +31,7 @@
 #include "hevc.hpp"
 #include "locator.hpp"
 #include "mp4.hpp"
+#include "mpegaudio.hpp"
 #include "packedaudio.hpp"
 #include "planner.hpp"
 #include "remux.hpp"
@@ -488,7 +490,8 @@ PYBIND11_MODULE(_runtime, m) {
   //   fparams: int64[B, ES_FPARAM_WORDS]; finfo: int64[B, ES_FINFO_WORDS]
   m.def("fragment_batch", [](Arr<int64_t> rinfo, Arr<int32_t> vsamples, Arr<int32_t> asamples, Arr<int64_t> sinfo,
                              Arr<int64_t> fparams, int64_t max_pes, int64_t max_aframes, int64_t headroom,
-                             int64_t audio_gap, py::array out, py::array finfo) {
+                             int64_t audio_gap, py::array out, py::array finfo,
+                             std::optional<Arr<int64_t>> mpainfo) {
     const int64_t B = fparams.size() / es::kFparamWords;
     if (max_pes <= 0 || max_aframes <= 0 || max_pes > 0x7fffffff / 16 || max_aframes > 0x7fffffff / 16)
       throw std::invalid_argument("fragment_batch: max_pes and max_aframes must be positive");
@@ -499,7 +502,7 @@ PYBIND11_MODULE(_runtime, m) {
     if (fparams.size() != B * es::kFparamWords || rinfo.size() < B * es::kRinfoWords ||
         vsamples.size() < table_words(B, max_pes, es::kVsampleWords) ||
         asamples.size() < table_words(B, max_aframes, es::kAsampleWords) || sinfo.size() < B * es::kSinfoWords ||
-        finfo.size() < B * es::kFinfoWords)
+        finfo.size() < B * es::kFinfoWords || (mpainfo && mpainfo->size() < B * es::kMpainfoWords))
       throw std::invalid_argument("fragment_batch: an argument is too small");
     uint8_t* op = mut_ptr<uint8_t>(out, "out");
     int64_t* fi = mut_ptr<int64_t>(finfo, "finfo");
@@ -514,9 +517,12 @@ PYBIND11_MODULE(_runtime, m) {
       es::fragment_segment(rinfo.data() + b * es::kRinfoWords, vsamples.data() + table_words(b, max_pes, es::kVsampleWords),
                            asamples.data() + table_words(b, max_aframes, es::kAsampleWords),
                            sinfo.data()[b * es::kSinfoWords + es::kAudioSampleRate], row, max_pes, max_aframes, audio_gap,
-                           op + row[es::kFpOutOff], fi + b * es::kFinfoWords);
+                           op + row[es::kFpOutOff], fi + b * es::kFinfoWords,
+                           mpainfo ? mpainfo->data() + b * es::kMpainfoWords : nullptr);
     }
-  });
+  }, py::arg("rinfo"), py::arg("vsamples"), py::arg("asamples"), py::arg("sinfo"), py::arg("fparams"), py::arg("max_pes"),
+     py::arg("max_aframes"), py::arg("headroom"), py::arg("audio_gap"), py::arg("out"), py::arg("finfo"),
+     py::arg("mpainfo") = py::none());
   m.def("moof_video_bytes", py::vectorize(&es::moof_video_bytes), py::arg("m"));
   m.def("moof_audio_bytes", py::vectorize(&es::moof_audio_bytes), py::arg("n"));
   m.def("frag_headroom", &es::frag_headroom, py::arg("max_pes"));
@@ -796,6 +802,55 @@ PYBIND11_MODULE(_runtime, m) {
       es::packed_segment(base + o[b], l[b], max_pes, es::packed_tables_at(t, max_pes, b));
     }, total);
   });
+  // Batched CPU MPEG audio behind remux_batch with the device kernels' layout (docs/MPEGAUDIO.md):
+  // the demuxed batch, per segment the bytes of its output region (the audio gap included), and the
+  // remux's asamples, rinfo and out, which are rewritten for a segment with an MPEG audio config.
+  //   mframes: int32[B, max_pes, ES_APES_WORDS]; mpainfo: int64[B, ES_MPAINFO_WORDS]
+  m.def("mpeg_audio_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
+                               int64_t max_pes, Arr<int64_t> region, int64_t max_aframes, py::array mframes,
+                               py::array mpainfo, py::array asamples, py::array rinfo, py::array out,
+                               Arr<int64_t> out_off) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_aframes <= 0) throw std::invalid_argument("mpeg_audio_batch: max_pes and max_aframes must be positive");
+    if (cap.size() != B || region.size() != B || out_off.size() != B || info.size() < B * ts::kInfoWords ||
+        pes.size() < ts::pes_words(B, max_pes) || mframes.size() < table_words(B, max_pes, es::kApesWords) ||
+        mpainfo.size() < B * es::kMpainfoWords || asamples.size() < table_words(B, max_aframes, es::kAsampleWords) ||
+        rinfo.size() < B * es::kRinfoWords)
+      throw std::invalid_argument("mpeg_audio_batch: an argument is too small");
+    const es::MpaTables t{mut_ptr<int32_t>(mframes, "mframes"), mut_ptr<int64_t>(mpainfo, "mpainfo"),
+                          mut_ptr<int32_t>(asamples, "asamples"), mut_ptr<int64_t>(rinfo, "rinfo")};
+    uint8_t* op = mut_ptr<uint8_t>(out, "out");
+    const int64_t *eo = es_off.data(), *cp = cap.data(), *rg = region.data(), *oo = out_off.data();
+    for (int64_t b = 0; b < B; ++b) {
+      if (eo[b] < 0 || cp[b] < 0 || eo[b] + cp[b] > es.size()) throw std::invalid_argument("mpeg_audio_batch: ES out of bounds");
+      if (oo[b] < 0 || rg[b] < 16 || oo[b] > out.size() || rg[b] > out.size() - oo[b])
+        throw std::invalid_argument("mpeg_audio_batch: output region out of bounds");
+    }
+    const uint8_t* ep = es.data();
+    const int64_t *ip = info.data(), *pp = pes.data();
+    py::gil_scoped_release nogil;
+    for (int64_t b = 0; b < B; ++b) {
+      const es::Segment s = es::segment_at(ep, eo, cp, ip, pp, max_pes, 0, b);
+      es::mpeg_audio_segment(s, rg[b], max_aframes,
+                             {t.mframes + table_words(b, max_pes, es::kApesWords), t.mpainfo + b * es::kMpainfoWords,
+                              t.asamples + table_words(b, max_aframes, es::kAsampleWords), t.rinfo + b * es::kRinfoWords},
+                             op + oo[b]);
+    }
+  });
+  m.def("mpa_frame", [](Arr<uint8_t> bytes, int64_t q, int64_t end) {
+    if (q < 0 || end > bytes.size()) throw std::invalid_argument("mpa_frame: range outside the bytes");
+    const es::MpaFrame f = es::mpa_frame_at(bytes.data(), q, end);
+    return py::make_tuple(f.len, f.counts, f.key, f.samples, f.rate, f.channels, f.version, f.layer, f.bitrate);
+  }, py::arg("bytes"), py::arg("q"), py::arg("end"));
+  m.def("mpa_scratch_words", [](int64_t nseg, int64_t max_pes) { return es::mpa_scratch(nseg, max_pes).end; },
+        py::arg("nseg"), py::arg("max_pes"));
+  m.attr("ES_MPAINFO_WORDS") = es::kMpainfoWords;
+  name_dict(m, "ES_MPAINFO", {{"status", es::kMpStatus}, {"n_frames", es::kMpNumFrames}, {"sample_rate", es::kMpSampleRate},
+                              {"channels", es::kMpChannels}, {"version", es::kMpVersion}, {"layer", es::kMpLayer},
+                              {"frame_samples", es::kMpFrameSamples}, {"bitrate", es::kMpBitrate}});
+  name_dict(m, "ES_MPASTATUS", {{"not_mpeg_audio", es::kMpaNotMpegAudio}, {"no_audio_config", es::kMpaNoAudioConfig},
+                                {"mpa_error", es::kMpaError}, {"format_change", es::kMpaFormatChange},
+                                {"aframe_overflow", es::kMpaAframeOverflow}});
   m.attr("ES_PAINFO_WORDS") = es::kPainfoWords;
   m.attr("ES_PACKED_FRAMES_PER_PES") = es::kPackedFramesPerPes;
   m.attr("ES_PACKED_MAX_TAGS") = es::kPackedMaxTags;

@@ -17,12 +17,13 @@ void put_be32(uint8_t* p, uint32_t v) {
 
 void fragment_segment(const int64_t* rinfo, const int32_t* vsamples, const int32_t* asamples, int64_t rate,
                       const int64_t* fparam, int64_t max_pes, int64_t max_aframes, int64_t audio_gap, uint8_t* out,
-                      int64_t* finfo) {
+                      int64_t* finfo, const int64_t* mpainfo) {
   const int64_t m = clamp(rinfo[kNumVsamples], 0, max_pes);
   const int64_t A0 = frag_audio_box(rinfo[kAudioBoxOffset], fparam[kFpRegion], audio_gap);
   int64_t n = 0;  // the recorded frames: rows with offset >= 0
   for (int64_t f = 0; f < max_aframes; ++f) n += asamples[kAsampleWords * f + kAsOffset] >= 0;
-  const FragTimes ft = frag_times(m, rinfo[kVideoBaseDts], rinfo[kAudioBasePts], rate, fparam[kFpTimeBase],
+  const FragAudio fa = frag_audio(rate, mpainfo);
+  const FragTimes ft = frag_times(m, rinfo[kVideoBaseDts], rinfo[kAudioBasePts], fa.rate, fparam[kFpTimeBase],
                                   fparam[kFpTimeRef], fparam[kFpAnchor] != 0);
   const uint32_t seq = static_cast<uint32_t>(fparam[kFpSequence]);
   const int64_t vbytes = moof_video_bytes(m), abytes = moof_audio_bytes(n);
@@ -43,7 +44,7 @@ void fragment_segment(const int64_t* rinfo, const int32_t* vsamples, const int32
   // ---- the audio moof ends where the audio mdat starts: the sizes of the first n rows
   uint8_t* a0 = out + A0 - abytes;
   for (int i = 0; i < kMoofAudioHead / 4; ++i)
-    put_be32(a0 + 4 * i, moof_audio_word(i, static_cast<uint32_t>(n), seq, static_cast<uint64_t>(ft.audio_tfdt)));
+    put_be32(a0 + 4 * i, moof_audio_word(i, static_cast<uint32_t>(n), seq, static_cast<uint64_t>(ft.audio_tfdt), fa.duration));
   for (int64_t f = 0; f < n; ++f)
     put_be32(a0 + kMoofAudioHead + kMoofAudioEntry * f, static_cast<uint32_t>(asamples[kAsampleWords * f + kAsSize]));
 

@@ -25,9 +25,11 @@ namespace es {
 //              it and fparam[kFpRegion] bytes from it on are writable.  Only the two moof boxes
 //              are written: the video one ends at out, the audio one at out + A0.
 //   finfo:     int64[kFinfoWords]
+//   mpainfo:   the segment's row of mpeg_audio_segment, or null: with a config its rate and frame
+//              replace `rate` and the AAC frame (docs/MPEGAUDIO.md)
 void fragment_segment(const int64_t* rinfo, const int32_t* vsamples, const int32_t* asamples, int64_t rate,
                       const int64_t* fparam, int64_t max_pes, int64_t max_aframes, int64_t audio_gap, uint8_t* out,
-                      int64_t* finfo);
+                      int64_t* finfo, const int64_t* mpainfo = nullptr);
 
 }  // namespace es
 }  // namespace hlsp2p

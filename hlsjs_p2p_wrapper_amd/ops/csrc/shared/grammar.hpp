@@ -1,10 +1,10 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
 // runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp,
-// runtime/cenc.cpp, runtime/fragment.cpp, runtime/packedaudio.cpp) and by the gfx950
+// runtime/cenc.cpp, runtime/fragment.cpp, runtime/packedaudio.cpp, runtime/mpegaudio.cpp) and by the gfx950
 // kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/fragment.hip, kernels/codec_config.hip,
 // kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip,
-// kernels/packed_audio.hip).  Plain inline
+// kernels/packed_audio.hip, kernels/mpeg_audio.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -305,6 +305,114 @@ HLSP2P_RULE AdtsConfig adts_config_at(const uint8_t* A, int64_t q) {
   return {((A[q + 2] >> 6) & 3) + 1, (A[q + 2] >> 2) & 15, ((A[q + 2] & 1) << 2) | (A[q + 3] >> 6)};
 }
 HLSP2P_RULE bool adts_config_usable(const AdtsConfig& c) { return c.rate_index < 13 && c.channel_config != 0; }
+
+// ---- MPEG audio frames (docs/MPEGAUDIO.md)
+HLSP2P_RULE bool is_mpeg_audio(int64_t atype) { return atype == ts::kMpeg1Audio || atype == ts::kMpeg2Audio; }
+// kbit/s of bitrate index bi = 1..14; v1: MPEG-1, else MPEG-2 / 2.5; layer 1..3
+HLSP2P_RULE int mpa_kbps(bool v1, int layer, int bi) {
+  if (v1 && layer == 1) return 32 * bi;
+  if (v1 && layer == 2) {
+    switch (bi) {
+      case 1: return 32; case 2: return 48; case 3: return 56; case 4: return 64; case 5: return 80;
+      case 6: return 96; case 7: return 112; case 8: return 128; case 9: return 160; case 10: return 192;
+      case 11: return 224; case 12: return 256; case 13: return 320; default: return 384;
+    }
+  }
+  if (v1) {
+    switch (bi) {
+      case 1: return 32; case 2: return 40; case 3: return 48; case 4: return 56; case 5: return 64;
+      case 6: return 80; case 7: return 96; case 8: return 112; case 9: return 128; case 10: return 160;
+      case 11: return 192; case 12: return 224; case 13: return 256; default: return 320;
+    }
+  }
+  if (layer == 1) {
+    switch (bi) {
+      case 1: return 32; case 2: return 48; case 3: return 56; case 4: return 64; case 5: return 80;
+      case 6: return 96; case 7: return 112; case 8: return 128; case 9: return 144; case 10: return 160;
+      case 11: return 176; case 12: return 192; case 13: return 224; default: return 256;
+    }
+  }
+  switch (bi) {
+    case 1: return 8; case 2: return 16; case 3: return 24; case 4: return 32; case 5: return 40;
+    case 6: return 48; case 7: return 56; case 8: return 64; case 9: return 80; case 10: return 96;
+    case 11: return 112; case 12: return 128; case 13: return 144; default: return 160;
+  }
+}
+
+struct MpaFrame {
+  int32_t len;      // whole frame, header included; 0: no header at q
+  bool counts;      // the frame ends inside [.., end)
+  int32_t key;      // (V, L, ri, mono) packed: what every frame of a segment has in common
+  int32_t samples, rate, channels, version, layer, bitrate;  // version 1, 2 or 25; bitrate in bit/s
+};
+// The header in bytes b1 b2 b3 behind a first byte FF, whatever lies behind it.
+HLSP2P_RULE MpaFrame mpa_header(int b1, int b2, int b3) {
+  MpaFrame f = {0, false, 0, 0, 0, 0, 0, 0, 0};
+  const int V = (b1 >> 3) & 3, L = (b1 >> 1) & 3, bi = b2 >> 4, ri = (b2 >> 2) & 3, pad = (b2 >> 1) & 1;
+  if ((b1 & 0xE0) != 0xE0 || V == 1 || L == 0 || bi == 0 || bi == 15 || ri == 3) return f;
+  const bool v1 = V == 3;
+  const int mono = (b3 >> 6) == 3;
+  f.layer = 4 - L;
+  f.version = v1 ? 1 : V == 2 ? 2 : 25;
+  f.rate = (ri == 0 ? 44100 : ri == 1 ? 48000 : 32000) >> (v1 ? 0 : V == 2 ? 1 : 2);
+  f.bitrate = 1000 * mpa_kbps(v1, f.layer, bi);
+  f.channels = mono ? 1 : 2;
+  f.key = (V << 5) | (L << 3) | (ri << 1) | mono;
+  if (f.layer == 1) {
+    f.len = (12 * f.bitrate / f.rate + pad) * 4;
+    f.samples = 384;
+  } else if (f.layer == 2 || v1) {
+    f.len = 144 * f.bitrate / f.rate + pad;
+    f.samples = 1152;
+  } else {
+    f.len = 72 * f.bitrate / f.rate + pad;
+    f.samples = 576;
+  }
+  return f;
+}
+// The frame at q of [.., end): len == 0 without a header there (q + 4 <= end, FF and the field rules).
+HLSP2P_RULE MpaFrame mpa_frame_at(const uint8_t* A, int64_t q, int64_t end) {
+  if (q + 4 > end || A[q] != 0xFF) return {0, false, 0, 0, 0, 0, 0, 0, 0};
+  MpaFrame f = mpa_header(A[q + 1], A[q + 2], A[q + 3]);
+  f.counts = f.len > 0 && q + f.len <= end;
+  return f;
+}
+// bytes [start, end) of the audio ES that audio PES k < a.n_pes covers: up to the next PES, inside the ES
+HLSP2P_RULE ByteRange mpa_pes_range(const int64_t* ap, int64_t k, const AudioSpan& a) {
+  const int64_t start = clamp(pes_at(ap, k, ts::kPesEsOffset), 0, a.len);
+  return {start, k + 1 < a.n_pes ? clamp(pes_at(ap, k + 1, ts::kPesEsOffset), start, a.len) : a.len};
+}
+// The audio box offset the MPEG audio op trusts: rinfo's, with the box header inside the region
+HLSP2P_RULE int64_t mpa_audio_box(int64_t a0, int64_t region) { return clamp(a0, 0, region > 8 ? region - 8 : 0); }
+
+struct MpaWalk {
+  int32_t frames, used;  // whole frames with the segment's key, and their bytes
+  bool error;            // the walk stopped in front of the PES's end
+  bool format_change;    // the PES starts with a header of another key: nothing of it counts
+};
+// The frames of one audio PES, bytes [start, end) of the audio ES: back to back, each with `key`.
+// fa(q, end) is mpa_frame_at on the caller's bytes; on_frame(j, q, len) sees every counted frame.
+template <class FA, class F>
+HLSP2P_RULE MpaWalk mpa_walk(FA&& fa, int64_t start, int64_t end, int32_t key, F&& on_frame) {
+  MpaWalk r = {0, 0, false, false};
+  int64_t q = start;
+  while (q != end) {
+    const MpaFrame f = fa(q, end);
+    if (r.frames == 0 && f.len > 0 && f.key != key) {
+      r.format_change = true;
+      return r;
+    }
+    if (!f.counts || f.key != key) {
+      r.error = true;
+      break;
+    }
+    on_frame(r.frames, q, f.len);
+    ++r.frames;
+    q += f.len;
+  }
+  r.used = static_cast<int32_t>(q - start);
+  return r;
+}
 
 // Byte j >= 2 of a NAL unit is an emulation-prevention byte iff it is 03 behind two raw zeros
 // (p2 = b[j - 2], p1 = b[j - 1], b = b[j]).  Equal to the sequential rule: a dropped byte is never zero.
@@ -628,6 +736,15 @@ HLSP2P_RULE FragTimes frag_times(int64_t m, int64_t vdts, int64_t apts, int64_t 
   return f;
 }
 
+// What the audio traf takes from the segment: the index's sample rate and the AAC frame, or, with a
+// mpainfo row (docs/MPEGAUDIO.md) that has a config (frame_samples > 0), that row's rate and frame
+struct FragAudio { int64_t rate; uint32_t duration; };
+HLSP2P_RULE FragAudio frag_audio(int64_t sinfo_rate, const int64_t* mpainfo_row) {
+  if (mpainfo_row && mpainfo_row[kMpFrameSamples] > 0)
+    return {mpainfo_row[kMpSampleRate], static_cast<uint32_t>(mpainfo_row[kMpFrameSamples])};
+  return {sinfo_rate, static_cast<uint32_t>(kAacFrameSamples)};
+}
+
 // The audio box offset a fragment trusts: rinfo's, brought to a multiple of 16 that leaves the
 // gap in front of it and the box header behind it inside the region (>= audio_gap + 32 bytes)
 HLSP2P_RULE int64_t frag_audio_box(int64_t a0, int64_t region, int64_t audio_gap) {
@@ -663,7 +780,8 @@ HLSP2P_RULE uint32_t moof_video_word(int i, uint32_t m, uint32_t seq, uint64_t t
     default: return 0;
   }
 }
-HLSP2P_RULE uint32_t moof_audio_word(int i, uint32_t n, uint32_t seq, uint64_t tfdt) {
+// duration: the samples of one frame, the tfhd default (1,024 for AAC; docs/MPEGAUDIO.md for MPEG audio)
+HLSP2P_RULE uint32_t moof_audio_word(int i, uint32_t n, uint32_t seq, uint64_t tfdt, uint32_t duration = kAacFrameSamples) {
   const uint32_t size = kMoofAudioHead + kMoofAudioEntry * n;
   switch (i) {
     case 0: return size;
@@ -677,7 +795,7 @@ HLSP2P_RULE uint32_t moof_audio_word(int i, uint32_t n, uint32_t seq, uint64_t t
     case 9: return 0x74666864u;
     case 10: return 0x00020028u;  // default-base-is-moof, default duration, default flags
     case 11: return 2;            // track
-    case 12: return 1024;         // samples of an AAC frame
+    case 12: return duration;     // samples of a frame
     case 13: return 0x02000000u;  // every frame is a sync sample
     case 14: return 20;
     case 15: return 0x74666474u;

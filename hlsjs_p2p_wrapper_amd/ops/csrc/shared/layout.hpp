@@ -336,6 +336,38 @@ struct PackedTables {
   IndexTables<int32_t, int64_t> ix;
   int64_t* painfo;
 };
+
+// ---- MPEG audio (MPEG-1/2/2.5 Layer I-III) tracks of TS segments, behind the remux (docs/MPEGAUDIO.md)
+constexpr int kMpainfoWords = 8;
+// mpainfo[] row (int64), identical on host and device; with kMpaNotMpegAudio or kMpaNoAudioConfig every other slot is 0
+enum Mpainfo : int {
+  kMpStatus = 0,
+  kMpNumFrames = 1,  // true total, also when the table overflowed
+  kMpSampleRate = 2, kMpChannels = 3,
+  kMpVersion = 4,    // 1, 2 or 25
+  kMpLayer = 5,      // 1, 2 or 3
+  kMpFrameSamples = 6,
+  kMpBitrate = 7,    // of the first frame, bit/s
+};
+enum MpaStatus : int64_t {
+  kMpaNotMpegAudio = 1, kMpaNoAudioConfig = 2, kMpaError = 4, kMpaFormatChange = 8, kMpaAframeOverflow = 16,
+};
+// mframes[] row (int32) [segment][max_pes]: ApesRow (whole frames, and their bytes), -1 rows beyond the audio PES
+// One segment's outputs, or a batch's: two tables of its own, and the remux's asamples and rinfo.
+struct MpaTables {
+  int32_t* mframes;
+  int64_t* mpainfo;
+  int32_t* asamples;
+  int64_t* rinfo;
+};
+// scratch (int32), element offsets inside one segment's slice of `stride` elements:
+// [hdr: 8 | pstart: max_pes + 1 | psrc: max_pes]
+// hdr = (walked PES); pstart are the payload offsets of each PES's first frame with the total
+// behind the last row, psrc the PES's first byte in the segment's ES
+struct MpaScratch { int64_t pstart, psrc, stride, end; };
+constexpr MpaScratch mpa_scratch(int64_t nseg, int64_t max_pes) {
+  return {8, 9 + max_pes, 9 + 2 * max_pes, nseg * (9 + 2 * max_pes)};
+}
 }  // namespace es
 
 // ---------------------------------------------------------------- fragmented MP4 demux (docs/FMP4DEMUX.md)

@@ -103,13 +103,16 @@ def _per_segment(name: str, value, B: int, default: int, dtype=np.int64) -> np.n
 
 
 def fragment_batch(rx: Remuxed, ix: EsIndex, sequence_numbers: Sequence[int], time_base=None, time_ref=None,
-                   anchor=None) -> Fragments:
+                   anchor=None, mpeg_audio=None) -> Fragments:
     """Write both ``moof`` boxes of every segment of a remuxed batch on the device its tensors
     live on.  ``rx`` was made with ``headroom >= frag_headroom(max_pes)`` and ``audio_gap >=
     frag_audio_gap(max_aframes)``; ``ix`` is the batch's index (its ``sinfo`` holds the audio
     sample rate).  Per segment: ``sequence_numbers`` (``mfhd``, modulo 2^32), ``time_base``
     (default 0), ``time_ref`` (default -1: no unwrap) and ``anchor`` (default off; where set the
-    segment's first stamp lands on ``time_ref``, which must then be >= 0)."""
+    segment's first stamp lands on ``time_ref``, which must then be >= 0).  ``mpeg_audio`` is the
+    batch's :class:`~.mpegaudio.MpegAudio` (or its ``mpainfo`` tensor): a segment whose row has a
+    config takes its audio ``tfhd`` default duration and its ``tfdt`` rate from there instead of
+    1,024 and ``sinfo`` (``docs/MPEGAUDIO.md``)."""
     rt = _rt()
     B, max_pes, max_aframes = int(rx.rinfo.shape[0]), int(rx.vsamples.shape[1]), int(rx.asamples.shape[1])
     dev = rx.out.device
@@ -149,15 +152,21 @@ def fragment_batch(rx: Remuxed, ix: EsIndex, sequence_numbers: Sequence[int], ti
     fp[:, FPARAM["anchor"]] = _per_segment("anchor", anchor, B, 0, dtype=bool)
     if np.any((fp[:, FPARAM["anchor"]] != 0) & (fp[:, FPARAM["time_ref"]] < 0)):
         raise ValueError("fragment_batch: an anchored segment needs a time_ref >= 0")
+    mpainfo = getattr(mpeg_audio, "mpainfo", mpeg_audio)
+    if mpainfo is not None and (not isinstance(mpainfo, torch.Tensor) or mpainfo.dtype != torch.int64
+                                or tuple(mpainfo.shape) != (B, rt.ES_MPAINFO_WORDS) or mpainfo.device != dev
+                                or not mpainfo.is_contiguous()):
+        raise ValueError("fragment_batch: mpeg_audio does not belong to this batch")
     fr = Fragments(torch.empty((B, FINFO_WORDS), dtype=torch.int64, device=dev), rx)
     if dev.type == "cpu":
         rt.fragment_batch(rx.rinfo.numpy(), rx.vsamples.numpy(), rx.asamples.numpy(), ix.sinfo.numpy(), fp, max_pes,
-                          max_aframes, headroom, gap, rx.out.numpy(), fr.finfo.numpy())
+                          max_aframes, headroom, gap, rx.out.numpy(), fr.finfo.numpy(),
+                          None if mpainfo is None else mpainfo.numpy())
         return fr
     if np.any(oo % OUT_ALIGN):
         raise ValueError(f"fragment_batch: output offsets must be {OUT_ALIGN}-byte aligned on device")
     if B:
         d = pack_to_device({"fp": fp.reshape(-1)}, dev)
         _dev().fragment_moof(rx.rinfo, rx.vsamples, rx.asamples, ix.sinfo, d["fp"], max_pes, max_aframes, headroom, gap,
-                             rx.out, fr.finfo)
+                             rx.out, fr.finfo, mpainfo)
     return fr

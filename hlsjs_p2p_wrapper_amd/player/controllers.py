@@ -1026,6 +1026,9 @@ class StreamController:
             if cfg["status"] & 16:  # unsupported_video: an HEVC fragment's parameter sets are in ``hevc``
                 hevc = fmp4["hevc"]
                 sig = (hevc["vps"], hevc["sps"], hevc["pps"]) + sig[2:]
+            mpa = fmp4.get("mpeg_audio")  # an MPEG audio track (ops/mpegaudio.py) has its config there
+            if mpa is not None and not mpa["status"] & 3:  # neither not_mpeg_audio nor no_audio_config
+                sig = sig + (mpa["version"], mpa["layer"], mpa["sample_rate"], mpa["channels"])
             announce = announce or sig != self._init_announced
         if announce:
             self._init_levels.add(frag.level)

@@ -179,6 +179,35 @@ def audio_init(cfg):
     return _init(AUDIO_TRACK, rate, b"soun", b"SoundHandler", 0x0100, 0, 0, smhd, mp4a, trex)
 
 
+MPEG_AUDIO_DISQUALIFIED = 1 | 2  # mpainfo: not_mpeg_audio, no_audio_config
+
+
+def mpeg_audio_codec(m):
+    """The RFC 6381 codec string of an MPEG audio track from its ``mpainfo`` fields
+    (``ops.mpegaudio``, ``docs/MPEGAUDIO.md``): ``mp4a.6b`` (object type 0x6B, MPEG-1 audio) or
+    ``mp4a.69`` (0x69, MPEG-2 audio, which MPEG-2.5 rides on).  ``None`` without a config."""
+    if m["status"] & MPEG_AUDIO_DISQUALIFIED or m["frame_samples"] <= 0:
+        return None
+    return "mp4a.6b" if m["version"] == 1 else "mp4a.69"
+
+
+def mpeg_audio_init(m):
+    """The audio track's init segment for MPEG audio: :func:`audio_init`'s ``ftyp`` + ``moov`` with
+    one ``mp4a{ esds }`` entry whose decoder configuration carries the object type 0x6B / 0x69 and
+    no decoder-specific info, track 2 in units of the sample rate, ``trex`` default duration one
+    frame's samples.  ``None`` without a config."""
+    if mpeg_audio_codec(m) is None:
+        return None
+    rate, channels = int(m["sample_rate"]), int(m["channels"])
+    dec_config = b"\x04" + bytes([13]) + struct.pack(">BB3xII", 0x6B if m["version"] == 1 else 0x69, 0x15, 0, 0)
+    es_body = struct.pack(">HB", 1, 0) + dec_config + b"\x06\x01\x02"
+    esds = _full(b"esds", 0, 0, b"\x03" + bytes([len(es_body)]) + es_body)
+    mp4a = _box(b"mp4a", struct.pack(">6xH8xHHHHI", 1, channels, 16, 0, 0, (rate << 16) if rate < 65536 else 0) + esds)
+    smhd = _full(b"smhd", 0, 0, bytes(4))
+    trex = struct.pack(">IIIII", AUDIO_TRACK, 1, int(m["frame_samples"]), 0, AUDIO_SAMPLE_FLAGS)
+    return _init(AUDIO_TRACK, rate, b"soun", b"SoundHandler", 0x0100, 0, 0, smhd, mp4a, trex)
+
+
 def _moof(sequence_number: int, tfhd: bytes, base: int, trun_flags: int, version: int, rows: np.ndarray) -> bytes:
     """``rows``: ``>u4[n, k]``, the trun's per-sample fields in box order."""
     mfhd = _full(b"mfhd", 0, 0, struct.pack(">I", sequence_number & 0xFFFFFFFF))
@@ -212,13 +241,15 @@ def audio_base(base_pts: int, sample_rate: int) -> int:
     return (int(base_pts) * int(sample_rate) + VIDEO_TIMESCALE // 2) // VIDEO_TIMESCALE
 
 
-def audio_moof(sequence_number: int, base_pts: int, sample_rate: int, asamples) -> bytes:
+def audio_moof(sequence_number: int, base_pts: int, sample_rate: int, asamples,
+               frame_samples: int = AAC_FRAME_SAMPLES) -> bytes:
     """The audio fragment: track 2 in units of ``sample_rate``, ``tfdt`` = the rescaled
-    ``base_pts``, 1024 samples and sync flags per frame as ``tfhd`` defaults, a ``trun`` with one
-    size per ``asamples`` row ``(offset, size)``."""
+    ``base_pts``, ``frame_samples`` (1024 for AAC; an MPEG audio track passes its own) and sync
+    flags per frame as ``tfhd`` defaults, a ``trun`` with one size per ``asamples`` row
+    ``(offset, size)``."""
     a = np.asarray(asamples, dtype=np.int32).reshape(-1, 2)
     rows = np.empty((len(a), 1), dtype=">u4")
     rows[:, 0] = a[:, 1].astype(np.uint32)
     tfhd = _full(b"tfhd", 0, _TFHD_BASE_IS_MOOF | _TFHD_DEFAULT_DURATION | _TFHD_DEFAULT_FLAGS,
-                 struct.pack(">III", AUDIO_TRACK, AAC_FRAME_SAMPLES, AUDIO_SAMPLE_FLAGS))
+                 struct.pack(">III", AUDIO_TRACK, int(frame_samples), AUDIO_SAMPLE_FLAGS))
     return _moof(sequence_number, tfhd, audio_base(base_pts, sample_rate), _TRUN_DATA_OFFSET | _TRUN_SIZE, 0, rows)

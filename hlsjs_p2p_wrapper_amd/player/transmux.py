@@ -549,7 +549,11 @@ class MediaPipeline:
         """The remux of an indexed group in which a row asked for it: one ``remux_batch`` call behind
         the index, its three tables on their way to the host; ``frag_params`` (the group's rows of
         (sequence number, time base, time reference, anchor), ``None``: no row asked for its moof
-        boxes) adds one ``fragment_batch`` call behind it; then the two configuration calls."""
+        boxes) adds one ``fragment_batch`` call behind it; then the two configuration calls.  Directly
+        behind the remux stands one ``mpeg_audio_batch`` call (docs/MPEGAUDIO.md): the audio codec is
+        only known on the device, so the launch is unconditional, and a segment whose audio is not
+        MPEG audio exits at once and keeps every byte of the remux."""
+        from ..ops import mpegaudio as _mpa
         from ..ops import remux as _rmx
 
         ix = g.ix
@@ -568,11 +572,14 @@ class MediaPipeline:
         g.rx = rx = _rmx.remux_batch(g.res, ix, caps,
                                      torch.empty(size + ALIGN, dtype=torch.uint8, device=g.res.es.device),
                                      out_offs, audio_gap=gap, headroom=headroom)
+        # in front of the copies to the host: the op rewrites rinfo and asamples of its segments
+        g.ma = ma = _mpa.mpeg_audio_batch(g.res, rx, caps)
         g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
+        g.mpainfo = _to_host(ma.mpainfo)
         if fragment:
             fp = frag_params
             g.fr = fr = _frg.fragment_batch(rx, ix, fp[:, 0], time_base=fp[:, 1], time_ref=fp[:, 2],
-                                            anchor=fp[:, 3] != 0)
+                                            anchor=fp[:, 3] != 0, mpeg_audio=ma)
             g.finfo = _to_host(fr.finfo)
         # ... and what the init segments are built from: one ``config_batch`` call behind the
         # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
@@ -1059,6 +1066,15 @@ class Fmp4Track(_View):
         cfg = self._f["config"]
         if name == "container":
             return "video/mp4" if self._video else "audio/mp4"
+        mpa = None if self._video else self._f._mpa()
+        if mpa is not None:  # an MPEG audio track: the four come from its mpainfo row
+            if name == "init":
+                if self._init is self._UNBUILT:
+                    self._init = _fmp4.mpeg_audio_init(mpa)
+                return self._init
+            if name == "codec":
+                return _fmp4.mpeg_audio_codec(mpa)
+            return mpa["channels" if name == "channelCount" else "sample_rate"]
         if self._video and cfg["status"] & _UNSUPPORTED_VIDEO:
             hevc = self._f["hevc"]
             if not hevc["status"] & _fmp4.HEVC_DISQUALIFIED:
@@ -1097,7 +1113,9 @@ class Fmp4Track(_View):
             if self._video:
                 data = _fmp4.video_moof(sequence_number, f._rinfo("video_base_dts"), self._host_rows())
             else:
-                data = _fmp4.audio_moof(sequence_number, f._rinfo("audio_base_pts"), f._rate, self._host_rows())
+                mpa = f._mpa()
+                data = _fmp4.audio_moof(sequence_number, f._rinfo("audio_base_pts"), f._audio_rate(), self._host_rows(),
+                                        mpa["frame_samples"] if mpa is not None else _fmp4.AAC_FRAME_SAMPLES)
             self._moofs[sequence_number] = data
         return data
 
@@ -1116,15 +1134,16 @@ class Fmp4Track(_View):
         if name == "samples":
             return (rx.vsamples if self._video else rx.asamples)[f._k, :self["nb"]]
         if name == "timescale":
-            return _fmp4.VIDEO_TIMESCALE if self._video else f._rate
+            return _fmp4.VIDEO_TIMESCALE if self._video else f._audio_rate()
         if name == "base":
             if self._video:
                 return max(f._rinfo("video_base_dts"), 0)
-            return _fmp4.audio_base(f._rinfo("audio_base_pts"), f._rate)
+            return _fmp4.audio_base(f._rinfo("audio_base_pts"), f._audio_rate())
         if name == "duration":
             if self._video:
                 return int(self._host_rows()[:, 2].sum(dtype=np.int64))
-            return _fmp4.AAC_FRAME_SAMPLES * self["nb"]
+            mpa = f._mpa()
+            return (mpa["frame_samples"] if mpa is not None else _fmp4.AAC_FRAME_SAMPLES) * self["nb"]
         if name == "moof":
             return self.moof
         if name in ("fragment", "moof_view", "tfdt") and f._fragment:
@@ -1154,10 +1173,13 @@ class Fmp4(_View):
     (:class:`Fmp4Track`), the ``rinfo`` fields by name (:data:`ops.remux.RINFO`) and ``config``: the
     fragment's codec configuration, a read-only mapping of the ``cinfo`` fields by name
     (:data:`ops.codecconfig.CINFO`) plus ``sps`` / ``pps`` as bytes, and ``hevc``: the same of the
-    ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``.  For a job that
+    ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``, and
+    ``mpeg_audio``: the ``mpainfo`` fields by name (:data:`ops.mpegaudio.MPAINFO`); where that has a
+    config (neither ``not_mpeg_audio`` nor ``no_audio_config``) the audio track is an MPEG audio
+    track and takes its time scale, frame length, init segment and codec from there.  For a job that
     asked for its moof boxes also ``time_base``: the 90 kHz base its ``tfdt`` values are relative to."""
 
-    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc", "_fragment")
+    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc", "_fragment", "_mpeg")
 
     def __init__(self, group, k: int, sinfo_row, fragment: bool = False) -> None:
         from ..ops.esindex import SINFO
@@ -1169,6 +1191,18 @@ class Fmp4(_View):
         self._tracks: Dict[str, Fmp4Track] = {}
         self._config: Any = None
         self._hevc: Any = None
+        self._mpeg: Any = None
+
+    def _mpa(self):
+        """The ``mpeg_audio`` mapping where it has a config, else ``None``."""
+        from ..ops.mpegaudio import NO_CONFIG
+
+        m = self["mpeg_audio"]
+        return None if m["status"] & NO_CONFIG else m
+
+    def _audio_rate(self) -> int:
+        m = self._mpa()
+        return self._rate if m is None else m["sample_rate"]
 
     def _rinfo(self, name: str) -> int:
         from ..ops.remux import RINFO
@@ -1206,15 +1240,23 @@ class Fmp4(_View):
                 g, k = self._g, self._k
                 self._hevc = MappingProxyType(segment_view(_np(g.hvinfo)[k], _np(g.hps)[k]))
             return self._hevc
+        if name == "mpeg_audio":
+            if self._mpeg is None:
+                from ..ops.mpegaudio import MPAINFO
+
+                row = _np(self._g.mpainfo)[self._k]
+                self._mpeg = MappingProxyType({k: int(row[v]) for k, v in MPAINFO.items()})
+            return self._mpeg
         raise KeyError(name)
 
     def keys(self):
         from ..ops.remux import RINFO
 
-        return ["video", "audio", *RINFO, "config", "hevc"] + (["time_base"] if self._fragment else [])
+        return ["video", "audio", *RINFO, "config", "hevc", "mpeg_audio"] + (["time_base"] if self._fragment else [])
 
     def __repr__(self) -> str:
-        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in ('video', 'audio', 'config', 'hevc')} })"
+        views = ("video", "audio", "config", "hevc", "mpeg_audio")
+        return f"Fmp4({ {k: self[k] for k in self.keys() if k not in views} })"
 
 
 class Mp4TrackView(_View):
@@ -1285,6 +1327,8 @@ class _Group:
     hcfg: Any = None  # HevcConfig, behind the codec configuration, with ...
     hvinfo: Any = None  # ... its two tensors on the host
     hps: Any = None
+    ma: Any = None  # MpegAudio, directly behind the remux, with ...
+    mpainfo: Any = None  # ... its mpainfo rows on the host
     painfo: Any = None  # the painfo rows of a packed-audio group on the host
     md: Any = None  # the Mp4Demux of a fragmented-MP4 group (of a cbcs or cenc group: over the decrypted copy) ...
     minfo: Any = None  # ... with its minfo rows and emsg table on the host; res / ix are its views

@@ -7,11 +7,12 @@ on a video ES the tool writes itself, the fragmented-MP4 demux on segments the t
 ``moof`` and thirty), the cbcs decrypt of such segments protected by the tool (the demux row's segment and
 one of about 3 MB), the cenc decrypt of the same two segments protected under cenc, the packed-audio demux
 on segments the tool writes itself (the walk through LDS tiles, the one through global memory and the
-batched copy of the same bytes), and the MFMA CRC
+batched copy of the same bytes), the MPEG audio remux on the bench's video with an MP3 track the tool
+writes in place of the AAC one, and the MFMA CRC
 with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
-    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20] [--only packedaudio]
+    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20] [--only packedaudio|mpegaudio]
 """
 import argparse
 import json
@@ -23,7 +24,7 @@ import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
 from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, fragment, hevcconfig,
-                                       mp4demux, packedaudio, remux, sampleaes, segment, tsdemux)
+                                       mp4demux, mpegaudio, packedaudio, remux, sampleaes, segment, tsdemux)
 from hlsjs_p2p_wrapper_amd.ops._native import device, runtime
 from hlsjs_p2p_wrapper_amd.player import fmp4
 
@@ -245,6 +246,79 @@ def packed_row(segs, iters, dev):
 CBCS_KEY, CBCS_IV = bytes(range(0x40, 0x50)), (bytes(range(0x70, 0x80)), bytes(range(0x90, 0xA0)))
 
 
+def mp3_frames(n, seed):
+    """``n`` MPEG-1 Layer III frames of 128 kbit/s at 44,100 Hz (417 bytes, 418 with the padding bit, which
+    47 frames of 49 carry) with random bytes behind the header."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for i in range(n):
+        pad = 1 if i % 49 < 47 else 0
+        body = rng.integers(0, 255, 413 + pad, dtype=np.uint8).tobytes()
+        out.append(bytes([0xFF, 0xFB, 0x90 | (pad << 1), 0x00]) + body)
+    return out
+
+
+def mpegaudio_row(r, caps, iters, dev, per_pes=4):
+    """``mpeg_audio_batch`` (``docs/MPEGAUDIO.md``) on the demuxed batch ``r`` with every segment's AAC
+    track replaced by an MP3 track of 128 kbit/s at 44,100 Hz as long as its video, ``per_pes`` frames to
+    an audio PES: us per call of the op behind the remux, after segment 0 was checked against the host."""
+    info, pes, es = r.info.cpu().numpy().copy(), r.pes.cpu().numpy().copy(), r.es.cpu().numpy()
+    I, B, max_pes = tsdemux.INFO, len(caps), pes.shape[2]
+    parts, offs2, caps2, pos, frames_total = [], [], [], 0, 0
+    for i in range(B):
+        row = info[i]
+        vb = int(row[I["video_bytes"]])
+        span = int(row[I["video_last_pts"]] - row[I["video_first_pts"]])
+        n = min(max(1, span * 44100 // (90000 * 1152)), per_pes * max_pes)
+        frames = mp3_frames(n, 100 + i)
+        groups = [frames[j:j + per_pes] for j in range(0, n, per_pes)]
+        audio, first = b"".join(frames), int(row[I["video_first_pts"]])
+        pes[i, 1:] = -1
+        at = 0
+        for k, g in enumerate(groups):
+            stamp = first + k * per_pes * 1152 * 90000 // 44100
+            pes[i, 1, k] = (at, stamp, stamp)
+            at += sum(map(len, g))
+        row[I["audio_type"]], row[I["audio_bytes"]], row[I["n_audio_pes"]] = 0x03, len(audio), len(groups)
+        row[I["audio_es_offset"]], row[I["id3_es_offset"]] = vb, vb + len(audio)
+        row[I["id3_bytes"]], row[I["n_id3_pes"]], row[I["payload_bytes"]] = 0, 0, vb + len(audio)
+        row[I["audio_first_pts"]], row[I["audio_last_pts"]] = first, int(pes[i, 1, len(groups) - 1, 1])
+        o = int(r.es_offs[i])
+        seg = es[o:o + vb].tobytes() + audio
+        offs2.append(pos)
+        caps2.append(len(seg))
+        parts.append(seg + bytes(-len(seg) % 256))
+        pos += len(parts[-1])
+        frames_total += n
+    buf = np.frombuffer(b"".join(parts) + bytes(256), np.uint8).copy()
+    offs2 = np.asarray(offs2, np.int64)
+
+    def batch(device_, sel):
+        res = tsdemux.DemuxResult(torch.from_numpy(info[sel]).to(device_), torch.from_numpy(pes[sel]).to(device_),
+                                  torch.from_numpy(buf).to(device_), offs2[sel])
+        cp = [caps2[j] for j in sel]
+        ix = esindex.index_batch(res, cp)
+        oo, size = remux.layout_out(cp, ix.nal.shape[1])
+        rx = remux.remux_batch(res, ix, cp, torch.zeros(size, dtype=torch.uint8, device=device_), oo)
+        return res, rx, cp
+
+    res, rx, cp = batch(dev, list(range(B)))
+    ma = mpegaudio.mpeg_audio_batch(res, rx, cp)
+    hres, hrx, hcp = batch("cpu", [0])
+    hma = mpegaudio.mpeg_audio_batch(hres, hrx, hcp)
+    assert torch.equal(ma.mpainfo[0].cpu(), hma.mpainfo[0]) and torch.equal(ma.mframes[0].cpu(), hma.mframes[0]), \
+        "mpegaudio mismatch"
+    assert torch.equal(rx.rinfo[0].cpu(), hrx.rinfo[0]) and torch.equal(rx.asamples[0].cpu(), hrx.asamples[0]), \
+        "mpegaudio mismatch"
+    end = int(hrx.rinfo[0, remux.RINFO["audio_box_offset"]] + 8 + hrx.rinfo[0, remux.RINFO["audio_payload_bytes"]])
+    assert torch.equal(rx.out[int(rx.out_offs[0]):int(rx.out_offs[0]) + end].cpu(), hrx.out[:end]), "mpegaudio mismatch"
+    mp = ma.mpainfo.cpu().numpy()
+    assert not mp[:, 0].any() and int(mp[:, 1].sum()) == frames_total and (mp[:, 2] == 44100).all(), "mpegaudio totals"
+    return {"mpegaudio_us": round(timed(lambda: mpegaudio.mpeg_audio_batch(res, rx, cp), iters), 1),
+            "mpegaudio_frames": frames_total,
+            "mpegaudio_bytes": int(rx.rinfo[:, remux.RINFO["audio_payload_bytes"]].sum().item())}
+
+
 def cbcs_protect(seg, md):
     """The tool's cbcs packager: ``seg`` (a host array of one :func:`mp4_segment` with ``senc`` boxes,
     changed in place) with one 16-byte block in ten of every video NAL unit behind its header byte and
@@ -369,7 +443,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segs", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", choices=["packedaudio"], default=None, help="run that row alone (for a profiler)")
+    ap.add_argument("--only", choices=["packedaudio", "mpegaudio"], default=None,
+                    help="run that row alone (for a profiler)")
     args = ap.parse_args()
     dev = torch.device("cuda")
     if args.only == "packedaudio":
@@ -400,6 +475,9 @@ def main():
     g, c = r.segment(0), cpu.segment(0)
     assert g["video_bytes"] == c["video_bytes"] and torch.equal(g["video"]["es"].cpu(), c["video"]["es"]), \
         "demux mismatch"
+    if args.only == "mpegaudio":
+        print(json.dumps(mpegaudio_row(r, caps, args.iters, dev)))
+        return
     # the sample index over the ES the demux just wrote (count + prefix + emit + finish)
     ix = esindex.index_batch(r, caps)
     res["esindex_us"] = timed(lambda: esindex.index_batch(r, caps), args.iters)
@@ -537,6 +615,9 @@ def main():
     # 470 ADTS frames behind one ID3 tag each; beside it the kernel through the raw binding with the chain
     # walked in LDS tiles and in global memory, and the batched copy of the same bytes
     res.update(packed_row(args.segs, args.iters, dev))
+    # the MPEG audio remux behind the remux (plan + copy) on the bench's video with an MP3 track in place
+    # of the AAC one
+    res.update(mpegaudio_row(r, caps, args.iters, dev))
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
