@@ -1,10 +1,10 @@
 """Batched segment ops (``aes``, ``crc``, ``segment``, ``tsdemux``, ``esindex``, ``remux``, ``fragment``,
 ``codecconfig``, ``hevcconfig``, ``sampleaes``, ``captions``, ``mp4demux``, ``cbcs``, ``cenc``, ``packedaudio``,
-``mpegaudio``):
+``mpegaudio``, ``ac3audio``):
 import the
 submodule you need.  The entry points of the sample index, of the remux, of the two codec configurations, of the
 SAMPLE-AES decrypt, of the caption extraction, of the fragmented-MP4 demux, of the cbcs and cenc decrypts and of
-the packed-audio demux and of the MPEG audio remux are
+the packed-audio demux and of the MPEG audio and AC-3 / E-AC-3 remuxes are
 also reachable from the package
 (``ops.index_batch``,
 ``ops.EsIndex``, ``ops.remux_batch``,
@@ -13,7 +13,8 @@ also reachable from the package
 ``ops.HevcConfig``, ``ops.sample_decrypt_batch``, ``ops.SampleAes``, ``ops.caption_batch``,
 ``ops.Captions``, ``ops.mp4_demux_batch``, ``ops.Mp4Demux``, ``ops.Mp4Track``, ``ops.cbcs_decrypt_batch``,
 ``ops.Cbcs``, ``ops.Mp4Protection``, ``ops.cenc_decrypt_batch``, ``ops.Cenc``,
-``ops.packed_audio_batch``, ``ops.PackedAudio``, ``ops.mpeg_audio_batch``, ``ops.MpegAudio``), resolved on first use."""
+``ops.packed_audio_batch``, ``ops.PackedAudio``, ``ops.mpeg_audio_batch``, ``ops.MpegAudio``,
+``ops.ac3_audio_batch``, ``ops.Ac3Audio``), resolved on first use."""
 
 _ESINDEX = ("index_batch", "EsIndex")
 _REMUX = ("remux_batch", "Remuxed")
@@ -27,8 +28,9 @@ _CBCS = ("cbcs_decrypt_batch", "Cbcs", "Mp4Protection")
 _CENC = ("cenc_decrypt_batch", "Cenc")
 _PACKEDAUDIO = ("packed_audio_batch", "PackedAudio")
 _MPEGAUDIO = ("mpeg_audio_batch", "MpegAudio")
+_AC3AUDIO = ("ac3_audio_batch", "Ac3Audio")
 __all__ = list(_ESINDEX + _REMUX + _FRAGMENT + _CODECCONFIG + _HEVCCONFIG + _SAMPLEAES + _CAPTIONS + _MP4DEMUX + _CBCS
-               + _CENC + _PACKEDAUDIO + _MPEGAUDIO)
+               + _CENC + _PACKEDAUDIO + _MPEGAUDIO + _AC3AUDIO)
 
 
 def __getattr__(name):
@@ -80,4 +82,8 @@ def __getattr__(name):
         from . import mpegaudio
 
         return getattr(mpegaudio, name)
+    if name in _AC3AUDIO:
+        from . import ac3audio
+
+        return getattr(ac3audio, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

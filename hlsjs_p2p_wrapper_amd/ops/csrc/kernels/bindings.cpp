@@ -261,6 +261,46 @@ void mpeg_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_
   hip_ok(D::launch_mpeg_audio(a), "mpeg_audio launch");
 }
 
+// AC-3 / E-AC-3 audio of a demuxed and remuxed batch (ac3_audio.hip): mpeg_audio's arguments, with
+// ac3info and a new tensor in mpainfo's layout; mpa_in is mpeg_audio's mpainfo (only read) or None.
+void ac3_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int64_t total_tiles, Tensor info, Tensor pes,
+               int64_t max_pes, Tensor region, int64_t max_aframes, Tensor scratch, Tensor dframes, Tensor ac3info,
+               Tensor mpainfo, Tensor asamples, Tensor rinfo, Tensor out, Tensor out_off,
+               const c10::optional<Tensor>& mpa_in) {
+  const int64_t B = es_off.numel();
+  TORCH_CHECK(max_pes > 0 && max_pes <= 0x7fffffff / 4 && max_aframes > 0 && total_tiles >= 0,
+              "ac3_audio: max_pes / max_aframes / total_tiles out of range");
+  const D::Ac3AudioArgs a{
+      .b = {.es = check<uint8_t>(es, "es"), .es_numel = es.numel(),
+            .es_off = check<int64_t>(es_off, "es_off"),
+            .cap = check<int64_t>(cap, "cap", B),
+            .tile_prefix = check<int64_t>(tile_prefix, "tile_prefix", B + 1),
+            .nseg = static_cast<int>(B), .total_tiles = total_tiles,
+            .info = check<int64_t>(info, "info", B * ts::kInfoWords),
+            .pes = check<int64_t>(pes, "pes", ts::pes_words(B, max_pes)),
+            .max_pes = max_pes, .max_nal = 0, .ix = {nullptr, nullptr, nullptr, nullptr}, .stream = stream()},
+      .region = check<int64_t>(region, "region", B),
+      .max_aframes = max_aframes,
+      .scratch = check<int32_t>(scratch, "scratch", es_::mpa_scratch(B, max_pes).end),
+      .t = {check<int32_t>(dframes, "dframes", hlsp2p::table_words(B, max_pes, es_::kApesWords)),
+            check<int64_t>(ac3info, "ac3info", B * es_::kAc3infoWords),
+            check<int64_t>(mpainfo, "mpainfo", B * es_::kMpainfoWords),
+            mpa_in.has_value() ? check<int64_t>(*mpa_in, "mpa_in", B * es_::kMpainfoWords) : nullptr,
+            check<int32_t>(asamples, "asamples", hlsp2p::table_words(B, max_aframes, es_::kAsampleWords)),
+            check<int64_t>(rinfo, "rinfo", B * es_::kRinfoWords)},
+      .out = check<uint8_t>(out, "out"),
+      .out_off = check<int64_t>(out_off, "out_off", B)};
+  same_device(es, {es_off, cap, tile_prefix, info, pes, region, scratch, dframes, ac3info, mpainfo, asamples, rinfo, out,
+                   out_off});
+  if (mpa_in.has_value()) {
+    same_device(es, {*mpa_in});
+    TORCH_CHECK(mpa_in->data_ptr() != mpainfo.data_ptr(), "ac3_audio: mpainfo must not be mpa_in");
+  }
+  aligned16({{es, "es"}, {out, "out"}});
+  TORCH_CHECK(es.data_ptr() != out.data_ptr(), "ac3_audio cannot run in place");
+  hip_ok(D::launch_ac3_audio(a), "ac3_audio launch");
+}
+
 // Codec configuration of a demuxed and indexed batch (codec_config.hip): the inputs of es_index
 // without a tile space, its four outputs, and per segment a cinfo row and two rows of max_ps bytes.
 void codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int64_t max_pes, int64_t max_nal,
@@ -617,6 +657,10 @@ TORCH_LIBRARY(hlsp2p, m) {
   m.def("mpeg_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
         "int max_pes, Tensor region, int max_aframes, Tensor(a!) scratch, Tensor(b!) mframes, Tensor(c!) mpainfo, "
         "Tensor(d!) asamples, Tensor(e!) rinfo, Tensor(f!) out, Tensor out_off) -> ()");
+  m.def("ac3_audio(Tensor es, Tensor es_off, Tensor cap, Tensor tile_prefix, int total_tiles, Tensor info, Tensor pes, "
+        "int max_pes, Tensor region, int max_aframes, Tensor(a!) scratch, Tensor(b!) dframes, Tensor(c!) ac3info, "
+        "Tensor(d!) mpainfo, Tensor(e!) asamples, Tensor(f!) rinfo, Tensor(g!) out, Tensor out_off, "
+        "Tensor? mpa_in=None) -> ()");
   m.def("codec_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
         "Tensor nal, Tensor au, Tensor aframes, Tensor sinfo, int max_ps, Tensor(a!) cinfo, Tensor(b!) ps) -> ()");
   m.def("hevc_config(Tensor es, Tensor es_off, Tensor cap, Tensor info, Tensor pes, int max_pes, int max_nal, "
@@ -654,6 +698,7 @@ TORCH_LIBRARY_IMPL(hlsp2p, CUDA, m) {
   m.impl("remux", &remux);
   m.impl("fragment_moof", &fragment_moof);
   m.impl("mpeg_audio", &mpeg_audio);
+  m.impl("ac3_audio", &ac3_audio);
   m.impl("codec_config", &codec_config);
   m.impl("hevc_config", &hevc_config);
   m.impl("sample_aes_decrypt", &sample_aes_decrypt);
@@ -706,6 +751,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mpeg_audio_tile_bytes", &D::mpeg_audio_tile_bytes);
   m.def("mpa_scratch_words", [](int64_t nseg, int64_t max_pes) { return es_::mpa_scratch(nseg, max_pes).end; },
         py::arg("nseg"), py::arg("max_pes"));
+  m.def("ac3_audio", &ac3_audio, py::arg("es"), py::arg("es_off"), py::arg("cap"), py::arg("tile_prefix"),
+        py::arg("total_tiles"), py::arg("info"), py::arg("pes"), py::arg("max_pes"), py::arg("region"),
+        py::arg("max_aframes"), py::arg("scratch"), py::arg("dframes"), py::arg("ac3info"), py::arg("mpainfo"),
+        py::arg("asamples"), py::arg("rinfo"), py::arg("out"), py::arg("out_off"), py::arg("mpa_in") = py::none());
+  m.def("ac3_audio_tile_bytes", &D::ac3_audio_tile_bytes);
   m.def("codec_config", &codec_config);
   m.def("hevc_config", &hevc_config);
   m.def("sample_aes_decrypt", &sample_aes_decrypt);

@@ -141,6 +141,20 @@ struct MpegAudioArgs {
 int mpeg_audio_tile_bytes();
 hipError_t launch_mpeg_audio(const MpegAudioArgs& a);
 
+// ac3_audio.hip: the AC-3 / E-AC-3 syncframes of every segment of a remuxed batch (docs/AC3AUDIO.md),
+// behind launch_remux (and launch_mpeg_audio) on the same out, asamples and rinfo.
+struct Ac3AudioArgs {
+  EsBatch b;              // tiles of `region`; ix is not used (all null), max_nal 0
+  const int64_t* region;  // [nseg] bytes of each output region, the audio gap included: what launch_remux was given
+  int64_t max_aframes;
+  int32_t* scratch;  // es::mpa_scratch(nseg, max_pes), not launch_mpeg_audio's
+  es::Ac3Tables t;   // asamples and rinfo are launch_remux's; mpa_in launch_mpeg_audio's mpainfo or null
+  uint8_t* out;
+  const int64_t* out_off;
+};
+int ac3_audio_tile_bytes();
+hipError_t launch_ac3_audio(const Ac3AudioArgs& a);
+
 // fragment.hip: the two moof boxes of every segment of a remuxed batch (docs/FRAGMENT.md), written
 // into the room launch_remux's caller left: headroom bytes in front of each region, audio_gap in
 // front of each audio box.  One workgroup per segment; a segment whose fparams row does not lie

@@ -31,6 +31,7 @@
 #include "hevc.hpp"
 #include "locator.hpp"
 #include "mp4.hpp"
+#include "ac3audio.hpp"
 #include "mpegaudio.hpp"
 #include "packedaudio.hpp"
 #include "planner.hpp"
@@ -851,6 +852,64 @@ PYBIND11_MODULE(_runtime, m) {
   name_dict(m, "ES_MPASTATUS", {{"not_mpeg_audio", es::kMpaNotMpegAudio}, {"no_audio_config", es::kMpaNoAudioConfig},
                                 {"mpa_error", es::kMpaError}, {"format_change", es::kMpaFormatChange},
                                 {"aframe_overflow", es::kMpaAframeOverflow}});
+  // Batched CPU AC-3 / E-AC-3 audio behind remux_batch (and mpeg_audio_batch) with the device
+  // kernels' layout (docs/AC3AUDIO.md): mpeg_audio_batch's arguments, with ac3info and a new row in
+  // mpainfo's layout per segment; mpa_in is the MPEG audio op's mpainfo (only read) or None.
+  //   dframes: int32[B, max_pes, ES_APES_WORDS]; ac3info: int64[B, ES_AC3INFO_WORDS]; mpainfo: int64[B, ES_MPAINFO_WORDS]
+  m.def("ac3_audio_batch", [](Arr<uint8_t> es, Arr<int64_t> es_off, Arr<int64_t> cap, Arr<int64_t> info, Arr<int64_t> pes,
+                              int64_t max_pes, Arr<int64_t> region, int64_t max_aframes, py::array dframes,
+                              py::array ac3info, py::array mpainfo, py::array asamples, py::array rinfo, py::array out,
+                              Arr<int64_t> out_off, std::optional<Arr<int64_t>> mpa_in) {
+    const int64_t B = es_off.size();
+    if (max_pes <= 0 || max_aframes <= 0) throw std::invalid_argument("ac3_audio_batch: max_pes and max_aframes must be positive");
+    if (cap.size() != B || region.size() != B || out_off.size() != B || info.size() < B * ts::kInfoWords ||
+        pes.size() < ts::pes_words(B, max_pes) || dframes.size() < table_words(B, max_pes, es::kApesWords) ||
+        ac3info.size() < B * es::kAc3infoWords || mpainfo.size() < B * es::kMpainfoWords ||
+        asamples.size() < table_words(B, max_aframes, es::kAsampleWords) || rinfo.size() < B * es::kRinfoWords ||
+        (mpa_in && mpa_in->size() < B * es::kMpainfoWords))
+      throw std::invalid_argument("ac3_audio_batch: an argument is too small");
+    const es::Ac3Tables t{mut_ptr<int32_t>(dframes, "dframes"), mut_ptr<int64_t>(ac3info, "ac3info"),
+                          mut_ptr<int64_t>(mpainfo, "mpainfo"), mpa_in ? mpa_in->data() : nullptr,
+                          mut_ptr<int32_t>(asamples, "asamples"), mut_ptr<int64_t>(rinfo, "rinfo")};
+    uint8_t* op = mut_ptr<uint8_t>(out, "out");
+    const int64_t *eo = es_off.data(), *cp = cap.data(), *rg = region.data(), *oo = out_off.data();
+    for (int64_t b = 0; b < B; ++b) {
+      if (eo[b] < 0 || cp[b] < 0 || eo[b] + cp[b] > es.size()) throw std::invalid_argument("ac3_audio_batch: ES out of bounds");
+      if (oo[b] < 0 || rg[b] < 16 || oo[b] > out.size() || rg[b] > out.size() - oo[b])
+        throw std::invalid_argument("ac3_audio_batch: output region out of bounds");
+    }
+    const uint8_t* ep = es.data();
+    const int64_t *ip = info.data(), *pp = pes.data();
+    py::gil_scoped_release nogil;
+    for (int64_t b = 0; b < B; ++b) {
+      const es::Segment s = es::segment_at(ep, eo, cp, ip, pp, max_pes, 0, b);
+      es::ac3_audio_segment(s, rg[b], max_aframes,
+                            {t.dframes + table_words(b, max_pes, es::kApesWords), t.ac3info + b * es::kAc3infoWords,
+                             t.mpainfo + b * es::kMpainfoWords, t.mpa_in ? t.mpa_in + b * es::kMpainfoWords : nullptr,
+                             t.asamples + table_words(b, max_aframes, es::kAsampleWords), t.rinfo + b * es::kRinfoWords},
+                            op + oo[b]);
+    }
+  }, py::arg("es"), py::arg("es_off"), py::arg("cap"), py::arg("info"), py::arg("pes"), py::arg("max_pes"),
+     py::arg("region"), py::arg("max_aframes"), py::arg("dframes"), py::arg("ac3info"), py::arg("mpainfo"),
+     py::arg("asamples"), py::arg("rinfo"), py::arg("out"), py::arg("out_off"), py::arg("mpa_in") = py::none());
+  m.def("ac3_frame", [](Arr<uint8_t> bytes, int64_t q, int64_t end) {
+    if (q < 0 || end > bytes.size()) throw std::invalid_argument("ac3_frame: range outside the bytes");
+    const es::Ac3Frame f = es::ac3_frame_at(bytes.data(), q, end);
+    return py::make_tuple(f.len, f.counts, f.key, f.layout_ok, f.kind, f.rate, f.channels, f.bsid, f.bitrate, f.fscod,
+                          f.bsmod, f.acmod, f.lfeon, f.bit_rate_code, f.data_rate);
+  }, py::arg("bytes"), py::arg("q"), py::arg("end"));
+  m.attr("ES_AC3INFO_WORDS") = es::kAc3infoWords;
+  m.attr("ES_AC3_FRAME_SAMPLES") = es::kAc3FrameSamples;
+  name_dict(m, "ES_AC3INFO", {{"status", es::kAcStatus}, {"n_frames", es::kAcNumFrames}, {"sample_rate", es::kAcSampleRate},
+                              {"channels", es::kAcChannels}, {"kind", es::kAcKind}, {"bsid", es::kAcBsid},
+                              {"frame_samples", es::kAcFrameSamples}, {"bitrate", es::kAcBitrate}, {"fscod", es::kAcFscod},
+                              {"bsmod", es::kAcBsmod}, {"acmod", es::kAcAcmod}, {"lfeon", es::kAcLfeon},
+                              {"bit_rate_code", es::kAcBitRateCode}, {"data_rate", es::kAcDataRate},
+                              {"first_frame_bytes", es::kAcFirstFrameBytes}});
+  name_dict(m, "ES_AC3STATUS", {{"not_dolby_audio", es::kAc3NotDolbyAudio}, {"no_audio_config", es::kAc3NoAudioConfig},
+                                {"ac3_error", es::kAc3Error}, {"format_change", es::kAc3FormatChange},
+                                {"aframe_overflow", es::kAc3AframeOverflow},
+                                {"unsupported_layout", es::kAc3UnsupportedLayout}});
   m.attr("ES_PAINFO_WORDS") = es::kPainfoWords;
   m.attr("ES_PACKED_FRAMES_PER_PES") = es::kPackedFramesPerPes;
   m.attr("ES_PACKED_MAX_TAGS") = es::kPackedMaxTags;

@@ -1,10 +1,11 @@
 // The MPEG-TS / PES / NAL / SPS / ADTS byte rules that fill the rows of layout.hpp: the only
 // definition of each, called by the host runtime (runtime/ts.cpp, runtime/es.cpp, runtime/remux.cpp,
 // runtime/codec.cpp, runtime/sampleaes.cpp, runtime/captions.cpp, runtime/mp4.cpp, runtime/cbcs.cpp,
-// runtime/cenc.cpp, runtime/fragment.cpp, runtime/packedaudio.cpp, runtime/mpegaudio.cpp) and by the gfx950
+// runtime/cenc.cpp, runtime/fragment.cpp, runtime/packedaudio.cpp, runtime/mpegaudio.cpp,
+// runtime/ac3audio.cpp) and by the gfx950
 // kernels (kernels/ts_demux.hip, kernels/es_index.hip, kernels/remux.hip, kernels/fragment.hip, kernels/codec_config.hip,
 // kernels/sample_aes.hip, kernels/captions.hip, kernels/mp4_demux.hip, kernels/cbcs.hip, kernels/cenc.hip,
-// kernels/packed_audio.hip, kernels/mpeg_audio.hip).  Plain inline
+// kernels/packed_audio.hip, kernels/mpeg_audio.hip, kernels/ac3_audio.hip).  Plain inline
 // functions over <cstdint> and layout.hpp: no containers, no statics, no tables in memory.
 #pragma once
 #include <cstdint>
@@ -28,6 +29,7 @@ constexpr int kPusi = 0x40;  // payload_unit_start_indicator, in header byte 1
 enum StreamType : int {
   kMpeg1Audio = 0x03, kMpeg2Audio = 0x04, kAdtsAac = 0x0F, kId3 = 0x15, kAvc = 0x1B, kHevc = 0x24,
   kSampleAesAdts = 0xCF, kSampleAesAvc = 0xDB,  // HLS SAMPLE-AES: reported as kAdtsAac / kAvc
+  kAc3 = 0x81, kEac3 = 0x87,  // HLS AC-3 / E-AC-3: the audio class only where no AAC / MPEG audio stream took it
 };
 
 HLSP2P_RULE int packet_pid(int b1, int b2) { return ((b1 & 0x1f) << 8) | b2; }
@@ -63,7 +65,8 @@ struct Psi {
 };
 
 // PAT -> PMT PID, PMT -> the first ES PID of each class, both within the first kPsiScanPackets
-// packets; sections are read as far as they lie inside their first packet.
+// packets; sections are read as far as they lie inside their first packet.  A Dolby stream (kAc3 /
+// kEac3) is a fallback: the first one becomes the audio class behind the walk, if the class is free.
 HLSP2P_RULE Psi parse_psi(const uint8_t* data, int64_t n_packets) {
   Psi r = {0, -1, {-1, -1, -1}, 0, 0};
   const int64_t scan = n_packets < kPsiScanPackets ? n_packets : kPsiScanPackets;
@@ -90,6 +93,7 @@ HLSP2P_RULE Psi parse_psi(const uint8_t* data, int64_t n_packets) {
     const int slen = ((p[ps + 1] & 0x0f) << 8) | p[ps + 2];
     const int end = ps + 3 + slen - 4 < kPacket ? ps + 3 + slen - 4 : kPacket;
     const int pil = ((p[ps + 10] & 0x0f) << 8) | p[ps + 11];
+    int dolby_pid = -1, dolby_type = 0;
     for (int q = ps + 12 + pil; q + 5 <= end;) {
       const int type = p[q];
       const int epid = packet_pid(p[q + 1], p[q + 2]);
@@ -103,8 +107,15 @@ HLSP2P_RULE Psi parse_psi(const uint8_t* data, int64_t n_packets) {
         r.audio_type = type == kSampleAesAdts ? kAdtsAac : type;
       } else if (type == kId3 && r.pid[2] < 0) {
         r.pid[2] = epid;
+      } else if ((type == kAc3 || type == kEac3) && dolby_pid < 0) {
+        dolby_pid = epid;
+        dolby_type = type;
       }
       q += 5 + eil;
+    }
+    if (r.pid[1] < 0 && dolby_pid >= 0) {
+      r.pid[1] = dolby_pid;
+      r.audio_type = dolby_type;
     }
   }
   if (r.pmt_pid >= 0 && !pmt_found) r.status |= kNoPmt;
@@ -391,13 +402,14 @@ struct MpaWalk {
   bool format_change;    // the PES starts with a header of another key: nothing of it counts
 };
 // The frames of one audio PES, bytes [start, end) of the audio ES: back to back, each with `key`.
-// fa(q, end) is mpa_frame_at on the caller's bytes; on_frame(j, q, len) sees every counted frame.
+// fa(q, end) is the codec's frame rule (mpa_frame_at, ac3_frame_at) on the caller's bytes: any type
+// with len, counts and key; on_frame(j, q, len) sees every counted frame.
 template <class FA, class F>
 HLSP2P_RULE MpaWalk mpa_walk(FA&& fa, int64_t start, int64_t end, int32_t key, F&& on_frame) {
   MpaWalk r = {0, 0, false, false};
   int64_t q = start;
   while (q != end) {
-    const MpaFrame f = fa(q, end);
+    const auto f = fa(q, end);
     if (r.frames == 0 && f.len > 0 && f.key != key) {
       r.format_change = true;
       return r;
@@ -412,6 +424,114 @@ HLSP2P_RULE MpaWalk mpa_walk(FA&& fa, int64_t start, int64_t end, int32_t key, F
   }
   r.used = static_cast<int32_t>(q - start);
   return r;
+}
+
+// ---- AC-3 / E-AC-3 frames (docs/AC3AUDIO.md): ATSC A/52 syncinfo and bsi, Table 5.18, Annex E
+HLSP2P_RULE bool is_dolby_audio(int64_t atype) { return atype == ts::kAc3 || atype == ts::kEac3; }
+// kbit/s of bit_rate_code i = 0..18 (frmsizecod >> 1)
+HLSP2P_RULE int ac3_kbps(int i) {
+  switch (i) {
+    case 0: return 32; case 1: return 40; case 2: return 48; case 3: return 56; case 4: return 64;
+    case 5: return 80; case 6: return 96; case 7: return 112; case 8: return 128; case 9: return 160;
+    case 10: return 192; case 11: return 224; case 12: return 256; case 13: return 320; case 14: return 384;
+    case 15: return 448; case 16: return 512; case 17: return 576; default: return 640;
+  }
+}
+HLSP2P_RULE int ac3_rate(int fscod) { return fscod == 0 ? 48000 : fscod == 1 ? 44100 : 32000; }
+HLSP2P_RULE int ac3_channels(int acmod, int lfeon) {
+  switch (acmod) {
+    case 0: return 2 + lfeon; case 1: return 1 + lfeon; case 2: return 2 + lfeon; case 3: return 3 + lfeon;
+    case 4: return 3 + lfeon; case 5: return 4 + lfeon; case 6: return 4 + lfeon; default: return 5 + lfeon;
+  }
+}
+
+struct Ac3Frame {
+  int32_t len;     // whole syncframe; 0: no header at q
+  bool counts;     // a supported layout, and the frame ends inside [.., end)
+  int32_t key;     // (kind, fscod, acmod, lfeon, bsid) packed; kAc3NoKey where the layout is unsupported
+  bool layout_ok;  // false: a valid E-AC-3 header of a layout that is out of scope
+  int32_t kind;    // kAc3KindAc3 / kAc3KindEac3
+  int32_t rate, channels, bsid, bitrate, fscod, bsmod, acmod, lfeon, bit_rate_code, data_rate;
+};
+// The header in bytes b2 .. b6 behind the syncword 0B 77, whatever lies behind it.
+HLSP2P_RULE Ac3Frame ac3_header(int b2, int b3, int b4, int b5, int b6) {
+  Ac3Frame f = {0, false, kAc3NoKey, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  const int bsid = b5 >> 3;
+  if (bsid <= 8) {
+    const int fscod = b4 >> 6, code = b4 & 0x3F;
+    if (fscod == 3 || code > 37) return f;
+    const int kbps = ac3_kbps(code >> 1);
+    const int words = fscod == 0 ? 2 * kbps : fscod == 1 ? kbps * 320 / 147 + (code & 1) : 3 * kbps;
+    const int acmod = b6 >> 5;
+    const int skip = 2 * ((acmod & 1) && acmod != 1) + 2 * ((acmod & 4) != 0) + 2 * (acmod == 2);
+    f.len = 2 * words;
+    f.layout_ok = true;
+    f.kind = kAc3KindAc3;
+    f.fscod = fscod;
+    f.bsmod = b5 & 7;
+    f.acmod = acmod;
+    f.lfeon = (b6 >> (4 - skip)) & 1;
+    f.bit_rate_code = code >> 1;
+    f.bitrate = 1000 * kbps;
+  } else if (bsid >= 11 && bsid <= 16) {
+    const int strmtyp = b2 >> 6, substreamid = (b2 >> 3) & 7, frmsiz = ((b2 & 7) << 8) | b3;
+    const int fscod = b4 >> 6, numblkscod = (b4 >> 4) & 3;
+    if (2 * (frmsiz + 1) < 8) return f;
+    f.len = 2 * (frmsiz + 1);
+    f.kind = kAc3KindEac3;
+    f.layout_ok = strmtyp == 0 && substreamid == 0 && fscod != 3 && numblkscod == 3;
+    if (!f.layout_ok) return f;
+    f.fscod = fscod;
+    f.acmod = (b4 >> 1) & 7;
+    f.lfeon = b4 & 1;
+    f.bitrate = 8 * f.len * ac3_rate(fscod) / kAc3FrameSamples;
+    f.data_rate = f.bitrate / 1000;
+  } else {
+    return f;
+  }
+  f.bsid = bsid;
+  f.rate = ac3_rate(f.fscod);
+  f.channels = ac3_channels(f.acmod, f.lfeon);
+  f.key = (f.kind << 13) | (f.fscod << 11) | (f.acmod << 6) | (f.lfeon << 5) | bsid;
+  return f;
+}
+// The frame at q of [.., end): len == 0 without a header there (q + 7 <= end, 0B 77 and the bsid's rule).
+HLSP2P_RULE Ac3Frame ac3_frame_at(const uint8_t* A, int64_t q, int64_t end) {
+  if (q + 7 > end || A[q] != 0x0B || A[q + 1] != 0x77)
+    return {0, false, kAc3NoKey, false, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  Ac3Frame f = ac3_header(A[q + 2], A[q + 3], A[q + 4], A[q + 5], A[q + 6]);
+  f.counts = f.layout_ok && q + f.len <= end;
+  return f;
+}
+// The ac3info row of a segment with a config, whose audio PES 0 starts with `first`, and its row in
+// mpainfo's layout (version and layer stay 0: fragment_moof takes the rate and the frame samples).
+HLSP2P_RULE void ac3_info_row(int64_t* row, int64_t status, int64_t n_frames, const Ac3Frame& first) {
+  row[kAcStatus] = status;
+  row[kAcNumFrames] = n_frames;
+  row[kAcSampleRate] = first.rate;
+  row[kAcChannels] = first.channels;
+  row[kAcKind] = first.kind;
+  row[kAcBsid] = first.bsid;
+  row[kAcFrameSamples] = kAc3FrameSamples;
+  row[kAcBitrate] = first.bitrate;
+  row[kAcFscod] = first.fscod;
+  row[kAcBsmod] = first.bsmod;
+  row[kAcAcmod] = first.acmod;
+  row[kAcLfeon] = first.lfeon;
+  row[kAcBitRateCode] = first.bit_rate_code;
+  row[kAcDataRate] = first.data_rate;
+  row[kAcFirstFrameBytes] = first.len;
+  row[kAcSpare] = 0;
+}
+HLSP2P_RULE void ac3_mpainfo_row(int64_t* row, int64_t n_frames, const Ac3Frame& first) {
+  row[kMpStatus] = 0;
+  row[kMpNumFrames] = n_frames;
+  row[kMpSampleRate] = first.rate;
+  row[kMpChannels] = first.channels;
+  row[kMpVersion] = 0;
+  row[kMpLayer] = 0;
+  row[kMpFrameSamples] = kAc3FrameSamples;
+  row[kMpBitrate] = first.bitrate;
 }
 
 // Byte j >= 2 of a NAL unit is an emulation-prevention byte iff it is 03 behind two raw zeros

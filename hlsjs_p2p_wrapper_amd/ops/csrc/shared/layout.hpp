@@ -368,6 +368,40 @@ struct MpaScratch { int64_t pstart, psrc, stride, end; };
 constexpr MpaScratch mpa_scratch(int64_t nseg, int64_t max_pes) {
   return {8, 9 + max_pes, 9 + 2 * max_pes, nseg * (9 + 2 * max_pes)};
 }
+// ---- AC-3 / E-AC-3 tracks of TS segments, behind the remux (docs/AC3AUDIO.md).  The scratch is es::mpa_scratch.
+constexpr int kAc3FrameSamples = 1536;
+constexpr int kAc3KindAc3 = 1, kAc3KindEac3 = 2;
+constexpr int32_t kAc3NoKey = -1;  // the key of a header whose layout is unsupported: equal to no frame's key
+constexpr int kAc3infoWords = 16;
+// ac3info[] row (int64), identical on host and device; with kAc3NotDolbyAudio or kAc3NoAudioConfig every other slot is 0
+enum Ac3info : int {
+  kAcStatus = 0,
+  kAcNumFrames = 1,  // true total, also when the table overflowed
+  kAcSampleRate = 2, kAcChannels = 3,
+  kAcKind = 4,       // kAc3KindAc3 / kAc3KindEac3
+  kAcBsid = 5,
+  kAcFrameSamples = 6,
+  kAcBitrate = 7,    // of the first frame, bit/s
+  kAcFscod = 8, kAcBsmod = 9, kAcAcmod = 10, kAcLfeon = 11,
+  kAcBitRateCode = 12,  // AC-3: frmsizecod >> 1 (dac3)
+  kAcDataRate = 13,     // E-AC-3: kbit/s (dec3)
+  kAcFirstFrameBytes = 14,
+  kAcSpare = 15,
+};
+enum Ac3Status : int64_t {
+  kAc3NotDolbyAudio = 1, kAc3NoAudioConfig = 2, kAc3Error = 4, kAc3FormatChange = 8, kAc3AframeOverflow = 16,
+  kAc3UnsupportedLayout = 32,
+};
+// dframes[] row (int32) [segment][max_pes]: ApesRow, as mframes
+// One segment's outputs, or a batch's: three tables of its own, and the remux's asamples and rinfo.
+struct Ac3Tables {
+  int32_t* dframes;
+  int64_t* ac3info;
+  int64_t* mpainfo;       // a row in Mpainfo's layout for fragment_moof
+  const int64_t* mpa_in;  // the MPEG audio op's mpainfo (copied for the segments of other codecs), or null
+  int32_t* asamples;
+  int64_t* rinfo;
+};
 }  // namespace es
 
 // ---------------------------------------------------------------- fragmented MP4 demux (docs/FMP4DEMUX.md)

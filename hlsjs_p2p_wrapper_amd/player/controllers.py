@@ -1029,6 +1029,9 @@ class StreamController:
             mpa = fmp4.get("mpeg_audio")  # an MPEG audio track (ops/mpegaudio.py) has its config there
             if mpa is not None and not mpa["status"] & 3:  # neither not_mpeg_audio nor no_audio_config
                 sig = sig + (mpa["version"], mpa["layer"], mpa["sample_rate"], mpa["channels"])
+            dolby = fmp4.get("ac3_audio")  # an AC-3 / E-AC-3 track (ops/ac3audio.py) likewise
+            if dolby is not None and not dolby["status"] & 3:  # neither not_dolby_audio nor no_audio_config
+                sig = sig + (dolby["kind"], dolby["sample_rate"], dolby["acmod"], dolby["lfeon"])
             announce = announce or sig != self._init_announced
         if announce:
             self._init_levels.add(frag.level)

@@ -208,6 +208,46 @@ def mpeg_audio_init(m):
     return _init(AUDIO_TRACK, rate, b"soun", b"SoundHandler", 0x0100, 0, 0, smhd, mp4a, trex)
 
 
+AC3_AUDIO_DISQUALIFIED = 1 | 2  # ac3info: not_dolby_audio, no_audio_config
+AC3_FRAME_SAMPLES = 1536
+
+
+def ac3_audio_codec(info):
+    """The codec string of a Dolby audio track from its ``ac3info`` fields (``ops.ac3audio``,
+    ``docs/AC3AUDIO.md``): ``ac-3`` or ``ec-3``.  ``None`` without a config."""
+    if info["status"] & AC3_AUDIO_DISQUALIFIED or info["kind"] not in (1, 2):
+        return None
+    return "ac-3" if info["kind"] == 1 else "ec-3"
+
+
+def ac3_specific_box(info) -> bytes:
+    """``dac3`` (3 bytes: ``fscod:2 bsid:5 bsmod:3 acmod:3 lfeon:1 bit_rate_code:5 0:5``) or ``dec3``
+    (5 bytes, one independent substream without dependents: ``data_rate:13 0:3 | fscod:2 bsid:5 0:1
+    0:1 bsmod:3 acmod:3 lfeon:1 0:3 0:4 0:1``) of ETSI TS 102 366 Annex F."""
+    fscod, bsid, bsmod, acmod, lfeon = (int(info[k]) for k in ("fscod", "bsid", "bsmod", "acmod", "lfeon"))
+    if info["kind"] == 1:
+        bits = (fscod << 22) | (bsid << 17) | (bsmod << 14) | (acmod << 11) | (lfeon << 10) | \
+            (int(info["bit_rate_code"]) << 5)
+        return _box(b"dac3", bits.to_bytes(3, "big"))
+    head = (int(info["data_rate"]) & 0x1FFF) << 3
+    sub = (fscod << 22) | (bsid << 17) | (bsmod << 12) | (acmod << 9) | (lfeon << 8)
+    return _box(b"dec3", head.to_bytes(2, "big") + sub.to_bytes(3, "big"))
+
+
+def ac3_audio_init(info):
+    """The audio track's init segment for AC-3 / E-AC-3: ``ftyp`` + ``moov`` with one ``ac-3{ dac3 }``
+    or ``ec-3{ dec3 }`` entry, track 2 in units of the sample rate, ``trex`` default duration 1536.
+    ``None`` without a config."""
+    codec = ac3_audio_codec(info)
+    if codec is None:
+        return None
+    rate, channels = int(info["sample_rate"]), int(info["channels"])
+    entry = _box(codec.encode(), struct.pack(">6xH8xHHHHI", 1, channels, 16, 0, 0, rate << 16) + ac3_specific_box(info))
+    smhd = _full(b"smhd", 0, 0, bytes(4))
+    trex = struct.pack(">IIIII", AUDIO_TRACK, 1, AC3_FRAME_SAMPLES, 0, AUDIO_SAMPLE_FLAGS)
+    return _init(AUDIO_TRACK, rate, b"soun", b"SoundHandler", 0x0100, 0, 0, smhd, entry, trex)
+
+
 def _moof(sequence_number: int, tfhd: bytes, base: int, trun_flags: int, version: int, rows: np.ndarray) -> bytes:
     """``rows``: ``>u4[n, k]``, the trun's per-sample fields in box order."""
     mfhd = _full(b"mfhd", 0, 0, struct.pack(">I", sequence_number & 0xFFFFFFFF))

@@ -552,7 +552,10 @@ class MediaPipeline:
         boxes) adds one ``fragment_batch`` call behind it; then the two configuration calls.  Directly
         behind the remux stands one ``mpeg_audio_batch`` call (docs/MPEGAUDIO.md): the audio codec is
         only known on the device, so the launch is unconditional, and a segment whose audio is not
-        MPEG audio exits at once and keeps every byte of the remux."""
+        MPEG audio exits at once and keeps every byte of the remux.  Behind it stands one
+        ``ac3_audio_batch`` call (docs/AC3AUDIO.md) of the same shape for AC-3 / E-AC-3; its ``mpainfo``
+        holds the rows of both ops and is what ``fragment_batch`` takes."""
+        from ..ops import ac3audio as _ac3
         from ..ops import mpegaudio as _mpa
         from ..ops import remux as _rmx
 
@@ -574,12 +577,14 @@ class MediaPipeline:
                                      out_offs, audio_gap=gap, headroom=headroom)
         # in front of the copies to the host: the op rewrites rinfo and asamples of its segments
         g.ma = ma = _mpa.mpeg_audio_batch(g.res, rx, caps)
+        g.da = da = _ac3.ac3_audio_batch(g.res, rx, caps, mpeg_audio=ma)
         g.rinfo, g.vsamples, g.asamples = _to_host(rx.rinfo), _to_host(rx.vsamples), _to_host(rx.asamples)
         g.mpainfo = _to_host(ma.mpainfo)
+        g.ac3info = _to_host(da.ac3info)
         if fragment:
             fp = frag_params
             g.fr = fr = _frg.fragment_batch(rx, ix, fp[:, 0], time_base=fp[:, 1], time_ref=fp[:, 2],
-                                            anchor=fp[:, 3] != 0, mpeg_audio=ma)
+                                            anchor=fp[:, 3] != 0, mpeg_audio=da)
             g.finfo = _to_host(fr.finfo)
         # ... and what the init segments are built from: one ``config_batch`` call behind the
         # remux, its two tensors on the same way to the host (docs/INITSEGMENT.md)
@@ -1066,6 +1071,15 @@ class Fmp4Track(_View):
         cfg = self._f["config"]
         if name == "container":
             return "video/mp4" if self._video else "audio/mp4"
+        dolby = None if self._video else self._f._dolby()
+        if dolby is not None:  # an AC-3 / E-AC-3 track: the four come from its ac3info row
+            if name == "init":
+                if self._init is self._UNBUILT:
+                    self._init = _fmp4.ac3_audio_init(dolby)
+                return self._init
+            if name == "codec":
+                return _fmp4.ac3_audio_codec(dolby)
+            return dolby["channels" if name == "channelCount" else "sample_rate"]
         mpa = None if self._video else self._f._mpa()
         if mpa is not None:  # an MPEG audio track: the four come from its mpainfo row
             if name == "init":
@@ -1113,9 +1127,8 @@ class Fmp4Track(_View):
             if self._video:
                 data = _fmp4.video_moof(sequence_number, f._rinfo("video_base_dts"), self._host_rows())
             else:
-                mpa = f._mpa()
                 data = _fmp4.audio_moof(sequence_number, f._rinfo("audio_base_pts"), f._audio_rate(), self._host_rows(),
-                                        mpa["frame_samples"] if mpa is not None else _fmp4.AAC_FRAME_SAMPLES)
+                                        f._frame_samples())
             self._moofs[sequence_number] = data
         return data
 
@@ -1142,8 +1155,7 @@ class Fmp4Track(_View):
         if name == "duration":
             if self._video:
                 return int(self._host_rows()[:, 2].sum(dtype=np.int64))
-            mpa = f._mpa()
-            return (mpa["frame_samples"] if mpa is not None else _fmp4.AAC_FRAME_SAMPLES) * self["nb"]
+            return f._frame_samples() * self["nb"]
         if name == "moof":
             return self.moof
         if name in ("fragment", "moof_view", "tfdt") and f._fragment:
@@ -1176,10 +1188,12 @@ class Fmp4(_View):
     ``hinfo`` fields (:data:`ops.hevcconfig.HINFO`) plus ``vps`` / ``sps`` / ``pps``, and
     ``mpeg_audio``: the ``mpainfo`` fields by name (:data:`ops.mpegaudio.MPAINFO`); where that has a
     config (neither ``not_mpeg_audio`` nor ``no_audio_config``) the audio track is an MPEG audio
-    track and takes its time scale, frame length, init segment and codec from there.  For a job that
+    track and takes its time scale, frame length, init segment and codec from there.  ``ac3_audio``
+    is the same of the ``ac3info`` fields (:data:`ops.ac3audio.AC3INFO`) for an AC-3 / E-AC-3 track; it is
+    listed among the keys of a segment whose audio type is Dolby audio.  For a job that
     asked for its moof boxes also ``time_base``: the 90 kHz base its ``tfdt`` values are relative to."""
 
-    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc", "_fragment", "_mpeg")
+    __slots__ = ("_g", "_k", "_rate", "_tracks", "_config", "_hevc", "_fragment", "_mpeg", "_ac3")
 
     def __init__(self, group, k: int, sinfo_row, fragment: bool = False) -> None:
         from ..ops.esindex import SINFO
@@ -1192,6 +1206,7 @@ class Fmp4(_View):
         self._config: Any = None
         self._hevc: Any = None
         self._mpeg: Any = None
+        self._ac3: Any = None
 
     def _mpa(self):
         """The ``mpeg_audio`` mapping where it has a config, else ``None``."""
@@ -1200,8 +1215,27 @@ class Fmp4(_View):
         m = self["mpeg_audio"]
         return None if m["status"] & NO_CONFIG else m
 
-    def _audio_rate(self) -> int:
+    def _dolby(self):
+        """The ``ac3_audio`` mapping where it has a config, else ``None``."""
+        from ..ops.ac3audio import NO_CONFIG
+
+        m = self["ac3_audio"]
+        return None if m["status"] & NO_CONFIG else m
+
+    def _frames(self):
+        """The mapping of the audio track's frame codec (MPEG audio or Dolby audio) where one has a
+        config, else ``None``: an ADTS track."""
         m = self._mpa()
+        return m if m is not None else self._dolby()
+
+    def _frame_samples(self) -> int:
+        from . import fmp4 as _fmp4
+
+        m = self._frames()
+        return _fmp4.AAC_FRAME_SAMPLES if m is None else m["frame_samples"]
+
+    def _audio_rate(self) -> int:
+        m = self._frames()
         return self._rate if m is None else m["sample_rate"]
 
     def _rinfo(self, name: str) -> int:
@@ -1247,15 +1281,26 @@ class Fmp4(_View):
                 row = _np(self._g.mpainfo)[self._k]
                 self._mpeg = MappingProxyType({k: int(row[v]) for k, v in MPAINFO.items()})
             return self._mpeg
+        if name == "ac3_audio":
+            if self._ac3 is None:
+                from ..ops.ac3audio import AC3INFO
+
+                row = _np(self._g.ac3info)[self._k]
+                self._ac3 = MappingProxyType({k: int(row[v]) for k, v in AC3INFO.items()})
+            return self._ac3
         raise KeyError(name)
 
     def keys(self):
         from ..ops.remux import RINFO
 
-        return ["video", "audio", *RINFO, "config", "hevc", "mpeg_audio"] + (["time_base"] if self._fragment else [])
+        from ..ops.ac3audio import AC3STATUS
+
+        dolby = [] if self["ac3_audio"]["status"] & AC3STATUS["not_dolby_audio"] else ["ac3_audio"]
+        return ["video", "audio", *RINFO, "config", "hevc", "mpeg_audio"] + dolby \
+            + (["time_base"] if self._fragment else [])
 
     def __repr__(self) -> str:
-        views = ("video", "audio", "config", "hevc", "mpeg_audio")
+        views = ("video", "audio", "config", "hevc", "mpeg_audio", "ac3_audio")
         return f"Fmp4({ {k: self[k] for k in self.keys() if k not in views} })"
 
 
@@ -1329,6 +1374,8 @@ class _Group:
     hps: Any = None
     ma: Any = None  # MpegAudio, directly behind the remux, with ...
     mpainfo: Any = None  # ... its mpainfo rows on the host
+    da: Any = None  # Ac3Audio, behind the MPEG audio op, with ...
+    ac3info: Any = None  # ... its ac3info rows on the host
     painfo: Any = None  # the painfo rows of a packed-audio group on the host
     md: Any = None  # the Mp4Demux of a fragmented-MP4 group (of a cbcs or cenc group: over the decrypted copy) ...
     minfo: Any = None  # ... with its minfo rows and emsg table on the host; res / ix are its views

@@ -12,7 +12,7 @@ writes in place of the AAC one, and the MFMA CRC
 with HIP events and reports us / GB/s of input.
 Checks results against the host oracles once.
 
-    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20] [--only packedaudio|mpegaudio]
+    PYTHONPATH=. python tools/kernel_bench.py [--segs 64] [--iters 20] [--only packedaudio|mpegaudio|ac3audio]
 """
 import argparse
 import json
@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from hlsjs_p2p_wrapper_amd.net.origin import PRESET_1080P_6M, SyntheticHlsOrigin
-from hlsjs_p2p_wrapper_amd.ops import (aes, captions, cbcs, cenc, codecconfig, crc, esindex, fragment, hevcconfig,
-                                       mp4demux, mpegaudio, packedaudio, remux, sampleaes, segment, tsdemux)
+from hlsjs_p2p_wrapper_amd.ops import (ac3audio, aes, captions, cbcs, cenc, codecconfig, crc, esindex, fragment,
+                                       hevcconfig, mp4demux, mpegaudio, packedaudio, remux, sampleaes, segment, tsdemux)
 from hlsjs_p2p_wrapper_amd.ops._native import device, runtime
 from hlsjs_p2p_wrapper_amd.player import fmp4
 
@@ -258,10 +258,19 @@ def mp3_frames(n, seed):
     return out
 
 
-def mpegaudio_row(r, caps, iters, dev, per_pes=4):
-    """``mpeg_audio_batch`` (``docs/MPEGAUDIO.md``) on the demuxed batch ``r`` with every segment's AAC
-    track replaced by an MP3 track of 128 kbit/s at 44,100 Hz as long as its video, ``per_pes`` frames to
-    an audio PES: us per call of the op behind the remux, after segment 0 was checked against the host."""
+def ac3_frames(n, seed):
+    """``n`` AC-3 syncframes of 384 kbit/s at 48,000 Hz, 3/2 + LFE: 1,536 bytes each (payload bytes are
+    never 0B, so no syncword forms inside)."""
+    rng = np.random.default_rng(seed)
+    return [bytes([0x0B, 0x77, 0x5A, 0x5A, 0x1C, 0x40, 0xE1]) + rng.integers(0x10, 256, 1529, dtype=np.uint8).tobytes()
+            for _ in range(n)]
+
+
+def frame_audio_batches(r, caps, dev, atype, make_frames, rate, samples, per_pes):
+    """The demuxed batch ``r`` with every segment's AAC track replaced by a track of whole frames
+    (``make_frames(n, seed)``, ``samples`` samples at ``rate`` Hz each, PMT type ``atype``) as long as its
+    video, ``per_pes`` frames to an audio PES: ``(batch(device, rows) -> (res, rx, caps), frames in all)``
+    with ``batch`` indexed and remuxed."""
     info, pes, es = r.info.cpu().numpy().copy(), r.pes.cpu().numpy().copy(), r.es.cpu().numpy()
     I, B, max_pes = tsdemux.INFO, len(caps), pes.shape[2]
     parts, offs2, caps2, pos, frames_total = [], [], [], 0, 0
@@ -269,17 +278,17 @@ def mpegaudio_row(r, caps, iters, dev, per_pes=4):
         row = info[i]
         vb = int(row[I["video_bytes"]])
         span = int(row[I["video_last_pts"]] - row[I["video_first_pts"]])
-        n = min(max(1, span * 44100 // (90000 * 1152)), per_pes * max_pes)
-        frames = mp3_frames(n, 100 + i)
+        n = min(max(1, span * rate // (90000 * samples)), per_pes * max_pes)
+        frames = make_frames(n, 100 + i)
         groups = [frames[j:j + per_pes] for j in range(0, n, per_pes)]
         audio, first = b"".join(frames), int(row[I["video_first_pts"]])
         pes[i, 1:] = -1
         at = 0
         for k, g in enumerate(groups):
-            stamp = first + k * per_pes * 1152 * 90000 // 44100
+            stamp = first + k * per_pes * samples * 90000 // rate
             pes[i, 1, k] = (at, stamp, stamp)
             at += sum(map(len, g))
-        row[I["audio_type"]], row[I["audio_bytes"]], row[I["n_audio_pes"]] = 0x03, len(audio), len(groups)
+        row[I["audio_type"]], row[I["audio_bytes"]], row[I["n_audio_pes"]] = atype, len(audio), len(groups)
         row[I["audio_es_offset"]], row[I["id3_es_offset"]] = vb, vb + len(audio)
         row[I["id3_bytes"]], row[I["n_id3_pes"]], row[I["payload_bytes"]] = 0, 0, vb + len(audio)
         row[I["audio_first_pts"]], row[I["audio_last_pts"]] = first, int(pes[i, 1, len(groups) - 1, 1])
@@ -302,7 +311,15 @@ def mpegaudio_row(r, caps, iters, dev, per_pes=4):
         rx = remux.remux_batch(res, ix, cp, torch.zeros(size, dtype=torch.uint8, device=device_), oo)
         return res, rx, cp
 
-    res, rx, cp = batch(dev, list(range(B)))
+    return batch, frames_total
+
+
+def mpegaudio_row(r, caps, iters, dev, per_pes=4):
+    """``mpeg_audio_batch`` (``docs/MPEGAUDIO.md``) on the demuxed batch ``r`` with every segment's AAC
+    track replaced by an MP3 track of 128 kbit/s at 44,100 Hz as long as its video, ``per_pes`` frames to
+    an audio PES: us per call of the op behind the remux, after segment 0 was checked against the host."""
+    batch, frames_total = frame_audio_batches(r, caps, dev, 0x03, mp3_frames, 44100, 1152, per_pes)
+    res, rx, cp = batch(dev, list(range(len(caps))))
     ma = mpegaudio.mpeg_audio_batch(res, rx, cp)
     hres, hrx, hcp = batch("cpu", [0])
     hma = mpegaudio.mpeg_audio_batch(hres, hrx, hcp)
@@ -317,6 +334,29 @@ def mpegaudio_row(r, caps, iters, dev, per_pes=4):
     return {"mpegaudio_us": round(timed(lambda: mpegaudio.mpeg_audio_batch(res, rx, cp), iters), 1),
             "mpegaudio_frames": frames_total,
             "mpegaudio_bytes": int(rx.rinfo[:, remux.RINFO["audio_payload_bytes"]].sum().item())}
+
+
+def ac3audio_row(r, caps, iters, dev, per_pes=4):
+    """``ac3_audio_batch`` (``docs/AC3AUDIO.md``) on the demuxed batch ``r`` with every segment's AAC
+    track replaced by an AC-3 track of 384 kbit/s at 48,000 Hz as long as its video, ``per_pes`` frames to
+    an audio PES: us per call of the op behind the remux, after segment 0 was checked against the host."""
+    batch, frames_total = frame_audio_batches(r, caps, dev, 0x81, ac3_frames, 48000, 1536, per_pes)
+    res, rx, cp = batch(dev, list(range(len(caps))))
+    da = ac3audio.ac3_audio_batch(res, rx, cp)
+    hres, hrx, hcp = batch("cpu", [0])
+    hda = ac3audio.ac3_audio_batch(hres, hrx, hcp)
+    assert torch.equal(da.ac3info[0].cpu(), hda.ac3info[0]) and torch.equal(da.dframes[0].cpu(), hda.dframes[0]) \
+        and torch.equal(da.mpainfo[0].cpu(), hda.mpainfo[0]), "ac3audio mismatch"
+    assert torch.equal(rx.rinfo[0].cpu(), hrx.rinfo[0]) and torch.equal(rx.asamples[0].cpu(), hrx.asamples[0]), \
+        "ac3audio mismatch"
+    end = int(hrx.rinfo[0, remux.RINFO["audio_box_offset"]] + 8 + hrx.rinfo[0, remux.RINFO["audio_payload_bytes"]])
+    assert torch.equal(rx.out[int(rx.out_offs[0]):int(rx.out_offs[0]) + end].cpu(), hrx.out[:end]), "ac3audio mismatch"
+    ai = da.ac3info.cpu().numpy()
+    assert not ai[:, 0].any() and int(ai[:, 1].sum()) == frames_total and (ai[:, 2] == 48000).all() \
+        and (ai[:, 3] == 6).all() and (ai[:, 7] == 384000).all(), "ac3audio totals"
+    return {"ac3audio_us": round(timed(lambda: ac3audio.ac3_audio_batch(res, rx, cp), iters), 1),
+            "ac3audio_frames": frames_total,
+            "ac3audio_bytes": int(rx.rinfo[:, remux.RINFO["audio_payload_bytes"]].sum().item())}
 
 
 def cbcs_protect(seg, md):
@@ -443,7 +483,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--segs", type=int, default=64)
     ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--only", choices=["packedaudio", "mpegaudio"], default=None,
+    ap.add_argument("--only", choices=["packedaudio", "mpegaudio", "ac3audio"], default=None,
                     help="run that row alone (for a profiler)")
     args = ap.parse_args()
     dev = torch.device("cuda")
@@ -477,6 +517,9 @@ def main():
         "demux mismatch"
     if args.only == "mpegaudio":
         print(json.dumps(mpegaudio_row(r, caps, args.iters, dev)))
+        return
+    if args.only == "ac3audio":
+        print(json.dumps(ac3audio_row(r, caps, args.iters, dev)))
         return
     # the sample index over the ES the demux just wrote (count + prefix + emit + finish)
     ix = esindex.index_batch(r, caps)
@@ -618,6 +661,7 @@ def main():
     # the MPEG audio remux behind the remux (plan + copy) on the bench's video with an MP3 track in place
     # of the AAC one
     res.update(mpegaudio_row(r, caps, args.iters, dev))
+    res.update(ac3audio_row(r, caps, args.iters, dev))
     res["crc_us"] = timed(lambda: crc.crc32_batch(src, offs, lens), args.iters)
     got = crc.crc32_batch(src, offs, lens)[0].cpu().numpy().view(np.uint32)
     assert int(got[0]) == crc.crc32(pool.data[offs[0]:offs[0] + lens[0]].numpy()), "CRC mismatch"
